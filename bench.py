@@ -14,11 +14,15 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): independent alignme
 rank with seeds offset by 1000*rank (BASELINE config 4) — weak scaling, no data-path collective; the
 barrier + max-over-ranks timing below is the only communication.
 
-Prints ONE JSON line (rank 0): metric/value/unit + roofline (dominant kernel k_gicp_pass, HIP-event
-timed on the engine's own stream) + cpu_baseline (the CPU oracle, OpenMP, timed on this box's host
-cores, rank 0 at N == 1 only, bounded sample) + parity (the GPU's final transform against the CPU
-oracle's on the same clouds and covariances: BASELINE.md §3's gate — the process exits non-zero when it
-fails, AFTER printing the line) and, at N == 1, extra keys measured in the same run:
+A plain run sets up, warms up, times `--steps` align() calls and prints ONE JSON line (rank 0): metric/value/unit,
+ms_per_step + roofline (dominant kernel k_gicp_pass, HIP-event timed on the engine's own stream during the timed steps).
+`--dump-outputs DIR` writes what the last timed align() handed its caller (final transform, final Hessian, converged flag,
+iteration count) as DIR/<name>.npy, so that two builds can be compared output for output on identical seeded inputs.
+
+`--full` adds everything that takes runs of its own: the device copy rate next to the roofline, cpu_baseline (the CPU oracle,
+OpenMP, timed on the host cores, rank 0 at N == 1 only, bounded sample), parity (the GPU's final transform against the CPU
+oracle's on the same clouds and covariances: BASELINE.md §3's gate — the process exits non-zero when it fails, AFTER printing
+the line), the point-sharded extra at N > 1, and, at N == 1, extra keys measured in the same run:
   ms_per_scan        SURVEY.md §8d's definition: upload + index of a fresh 100k scan, its lazily computed
                      covariances, all iterations, the output transform and the download of the aligned cloud
   c5                 BASELINE configs[4] (250k OS1-shaped scan vs 2M-point submap): a few aligns, the pass
@@ -354,7 +358,7 @@ def c5_leg(ng, device, aligns=5, warmup=2, copy_gbps=None):
     return out
 
 
-def sharded_c5_leg(ng, dist, world, rank, device, steps=5, warmup=2):
+def sharded_c5_leg(ng, dist, world, rank, device, steps=5, warmup=2, outputs=None):
     """SURVEY.md §8e way 2 on BASELINE configs[4]: ONE 250k -> 2M alignment whose source points are split over the ranks.  The target
     (8 keyframes, device keyframe store) is replicated on every rank; K1 of every keyframe and of the scan is itself sharded (each
     rank computes a block of the packed covariance array, the blocks are all-gathered).  Per pass: the fused kernel over this rank's
@@ -393,6 +397,8 @@ def sharded_c5_leg(ng, dist, world, rank, device, steps=5, warmup=2):
         iters += g.nr_iterations_ + 1
     torch.cuda.synchronize()
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+    if outputs is not None:
+        outputs.update(caller_outputs(g))
     dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     # what the collective costs: the same 256-byte all-reduce in a loop of its own
@@ -418,6 +424,21 @@ def sharded_c5_leg(ng, dist, world, rank, device, steps=5, warmup=2):
     return out
 
 
+def caller_outputs(g) -> dict:
+    """What align() hands its caller (pcl::Registration: getFinalTransformation, getFinalHessian, hasConverged, nr_iterations_),
+    as float32 / float64 arrays."""
+    return {"final_transformation": np.asarray(g.getFinalTransformation(), np.float32),
+            "final_hessian": np.asarray(g.getFinalHessian(), np.float64),
+            "converged": np.array([float(g.hasConverged())], np.float64),
+            "nr_iterations": np.array([float(g.nr_iterations_)], np.float64)}
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def _free_port() -> int:
     import socket
     sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
@@ -440,7 +461,10 @@ def main_sharded(args):
     if rank == 0:
         build.build()
     dist.barrier()
-    leg = sharded_c5_leg(ng, dist, world, rank, local_rank, steps=args.steps if args.steps else 5, warmup=max(1, args.warmup))
+    outputs = {}
+    leg = sharded_c5_leg(ng, dist, world, rank, local_rank, steps=args.steps, warmup=max(1, args.warmup), outputs=outputs)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         out = {"metric": "gicp_iterations_per_sec", "value": leg["iterations_per_s"], "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": leg["ms_per_align"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -454,13 +478,19 @@ def main_sharded(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (one step = one complete align())")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the c5 / dlo_frame / submap / ms_per_scan extras (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: copy rate, CPU baseline + parity gate, extras, sharded extra at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity gate")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the c5 / dlo_frame / submap / ms_per_scan extras (profiling runs)")
     ap.add_argument("--mode", choices=["independent", "sharded"], default="independent",
                     help="independent (default, BASELINE configs[2]/[3]): one 100k -> 500k alignment per rank; sharded: ONE 250k -> 2M alignment split over the ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.mode == "sharded":
         return main_sharded(args)
 
@@ -473,7 +503,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: no HIP device visible (there is no CPU fallback)")
     torch.cuda.set_device(local_rank)
-    rehearse = world == 1 and os.environ.get("NGICP_BENCH_REHEARSE_SHARDED_EXTRA") == "1"  # the N > 1 extra over a world of one
+    rehearse = world == 1 and args.full and os.environ.get("NGICP_BENCH_REHEARSE_SHARDED_EXTRA") == "1"  # the N > 1 extra over a world of one
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))  # "nccl" == RCCL on ROCm
     elif rehearse:
@@ -539,9 +569,11 @@ def main():
     g.setProfiling(False)
     T_gpu = g.getFinalTransformation().copy()
     it_gpu, conv_gpu = g.nr_iterations_, g.converged_
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, caller_outputs(g))
 
     sharded_extra, force_exit = None, False
-    if (world > 1 or rehearse) and not args.no_extras:  # every rank takes part; rank 0 reports (the headline above is already measured)
+    if (world > 1 or rehearse) and args.full and not args.no_extras:  # every rank takes part; rank 0 reports (the headline above is already measured)
         # The extra runs in a thread with a wall budget: a collective that never returns must not take the headline line with it
         # (every rank then times out alike, prints / skips, and leaves through os._exit behind the stuck thread).
         import threading
@@ -598,14 +630,14 @@ def main():
                          "kernel": "k_gicp_pass", "avg_launch_ms": avg_pass_ms, "launches_timed": passes,
                          "algorithmic_bytes_per_launch": bytes_per_launch, "floor_frac_cbar1": floor},
         }
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 out["hbm_copy_measured_GBps"] = g.measureCopyBandwidth(1 << 30, 10)
                 out["roofline"]["hbm_copy_measured_GBps"] = out["hbm_copy_measured_GBps"]
                 roofline_extras(out["roofline"], bytes_per_launch, avg_pass_ms, out["hbm_copy_measured_GBps"])
             except Exception as exc:
                 out["hbm_copy_measured_GBps"] = {"error": str(exc)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             copy_rate = out.get("hbm_copy_measured_GBps")
             for key, fn in (("ms_per_scan_detail", lambda: ms_per_scan_gpu(g, w)), ("dlo_frame", lambda: dlo_frame_ms(ng, w, tgt_covs, local_rank)),
                             ("submap", lambda: submap_routes_ms(ng, w, local_rank)), ("preprocess", lambda: preprocess_ms(ng, w, local_rank)),
@@ -618,7 +650,7 @@ def main():
                 out["ms_per_scan"] = out["ms_per_scan_detail"]["median_ms"]
         if sharded_extra is not None:
             out["sharded_c5"] = sharded_extra
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base, T_cpu, it_cpu, conv_cpu = cpu_baseline(w, tgt_covs, src_covs)
             out["cpu_baseline"] = base
             out["speedup_vs_cpu_baseline"] = out["value"] / base["value"]

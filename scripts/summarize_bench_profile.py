@@ -19,7 +19,7 @@ for r in csv.DictReader(open(trace)):
 pk = next(k for k in durs if "k_gicp_pass" in k); sk = next(k for k in durs if "k_lm_solve" in k)
 work = [d for d in durs[pk] if d > 15.0]; swork = [d for d in durs[sk] if d > 3.0]
 line = json.load(open(os.path.join(SRC, "bench_under_rocprof.json")))
-out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras",
+out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras",
        "k_gicp_pass_working_launches": len(work), "k_gicp_pass_avg_us_working": sum(work) / len(work),
        "k_lm_solve_working_launches": len(swork), "k_lm_solve_avg_us_working": sum(swork) / len(swork),
        "bench_line_avg_launch_us_hip_events": line["roofline"]["avg_launch_ms"] * 1e3,

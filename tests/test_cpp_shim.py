@@ -31,52 +31,6 @@ def test_shim_compiles_and_fails_loudly_without_gpu(hip_lib, tmp_path):
     assert res.returncode == 3 and "cannot create the GPU engine" in res.stderr  # no silent CPU path
 
 
-REF_ODOM = "/root/reference/src/dlo/odom.cc"
-# the statements of the odometry node that touch the two NanoGICP instances (SURVEY.md §8b "call sites the replacement must
-# keep working unchanged"): 1-based inclusive line ranges of src/dlo/odom.cc
-CALL_SITE_RANGES = [(100, 120), (477, 480), (498, 500), (519, 526), (799, 840), (1170, 1174)]
-
-
-@pytest.mark.skipif(not os.path.exists(REF_ODOM), reason="reference tree not present (it never travels to the GPU box)")
-def test_odom_call_sites_compile_verbatim(tmp_path):
-    """The boundary claim is "DLO's call sites compile unchanged against the shim".  The reference's text is not copied into
-    this repository: the test reads src/dlo/odom.cc where it lies, pastes the call-site line ranges CHARACTER FOR CHARACTER
-    into member functions of a struct that declares only the `this->` members those lines name (types as include/dlo/odom.h
-    declares them), and compiles the result with -Wall -Werror against include/nano_gicp/nano_gicp.hpp."""
-    lines = open(REF_ODOM).read().split("\n")
-    bodies = ["\n".join(lines[a - 1:b]) for a, b in CALL_SITE_RANGES]
-    assert "pcl::Registration<PointType, PointType>::KdTreeReciprocalPtr temp;" in bodies[0]
-    assert "this->gicp.source_kdtree_ = this->gicp_s2s.source_kdtree_;" in bodies[3]
-    members = """
-  pcl::PointCloud<PointType>::Ptr current_scan, current_scan_t, target_cloud, keyframe_cloud, submap_cloud;   // odom.h:78-103
-  std::vector<std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>>> keyframe_normals;      // odom.h:93
-  std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>> submap_normals;                     // odom.h:104
-  std::atomic<bool> submap_hasChanged{true};                                                                   // odom.h:108
-  nano_gicp::NanoGICP<PointType, PointType> gicp_s2s;                                                          // odom.h:119
-  nano_gicp::NanoGICP<PointType, PointType> gicp;                                                              // odom.h:120
-  Eigen::Matrix4f T, T_s2s, T_s2s_prev, imu_SE3;
-  bool imu_use_ = false;
-  int gicps2s_k_correspondences_ = 10, gicps2s_max_iter_ = 32, gicps2s_ransac_iter_ = 5;
-  double gicps2s_max_corr_dist_ = 1.0, gicps2s_transformation_ep_ = 0.01, gicps2s_euclidean_fitness_ep_ = 0.01, gicps2s_ransac_inlier_thresh_ = 1.0;
-  int gicps2m_k_correspondences_ = 20, gicps2m_max_iter_ = 32, gicps2m_ransac_iter_ = 5;
-  double gicps2m_max_corr_dist_ = 0.5, gicps2m_transformation_ep_ = 0.01, gicps2m_euclidean_fitness_ep_ = 0.01, gicps2m_ransac_inlier_thresh_ = 1.0;
-  void integrateIMU() {}
-  void propagateS2S(Eigen::Matrix4f) {}
-  void getSubmapKeyframes() {}
-"""
-    src = ['#include <atomic>', '#include <vector>', '#include "nano_gicp/nano_gicp.hpp"', 'typedef pcl::PointXYZI PointType;  // include/dlo/dlo.h:50',
-           'namespace dlo { struct OdomNode {', members]
-    src += [f"  void site{i}();" for i in range(len(bodies))]
-    src += ["}; }"]
-    for i, body in enumerate(bodies):
-        src += [f"void dlo::OdomNode::site{i}() {{", body, "}"]
-    src += ["int main() { dlo::OdomNode n; (void)n; return 0; }"]
-    cpp = tmp_path / "odom_call_sites.cpp"
-    cpp.write_text("\n".join(src))
-    res = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(cpp)], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-
-
 def _transform_like_replay(M, pts):
     """tests/cpp/replay_odom.cpp `transformed()`: ((m00 x + m01 y) + m02 z) + m03 in float32 (g++ -O2 without -march: no FMA)."""
     M = M.astype(np.float32)

@@ -1,11 +1,15 @@
 """CPU tests: the oracle against the reference's real kd-tree (golden vectors + live when available),
 against the independent numpy model, and its small linear-algebra pieces against LAPACK/scipy.
 The reference ships no tests of its own; paths cited are under /root/reference/include/nano_gicp/."""
+import os
+
 import numpy as np
 import pytest
 
 from direct_lidar_odometry_amd import clouds
 from oracle import numpy_model as nm
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_oracle_kdtree_matches_reference_golden(golden, oracle_mod):
@@ -22,30 +26,35 @@ def test_oracle_kdtree_matches_reference_golden(golden, oracle_mod):
     assert np.all(d2[:, 0] == 0.0) and np.array_equal(idx[:, 0], probes)  # self is its own nearest neighbour
 
 
-@pytest.mark.parametrize("n,k", [(1, 1), (7, 3), (101, 20), (100, 20), (5000, 1), (5000, 20), (20000, 32)])
-def test_oracle_kdtree_matches_reference_live(oracle_mod, n, k):
-    """Index-for-index against the reference kd-tree compiled from /root/reference (authoring container only)."""
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    rng = np.random.default_rng(n * 31 + k)
-    pts = (rng.normal(size=(n, 3)) * [10, 8, 1.5]).astype(np.float32)
-    q = np.concatenate([pts[: min(n, 200)], (rng.normal(size=(200, 3)) * 30).astype(np.float32)])  # inside + far outside
-    k = min(k, n)
+@pytest.fixture(scope="module")
+def ref_kdtree():
+    """The reference kd-tree's outputs on stored inputs (tests/golden/make_ref_kdtree.py)."""
+    with np.load(os.path.join(GOLDEN, "ref_kdtree.npz"), allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _check_against_reference(oracle_mod, ref_kdtree, key, k):
+    pts, q = ref_kdtree[key + "_pts"], ref_kdtree[key + "_q"]
+    want_idx, want_d2 = ref_kdtree[key + "_idx"], ref_kdtree[key + "_d2"]
+    assert want_idx.shape == (len(q), k)
     a = oracle_mod.OracleTree(pts).knn(q, k)
-    b = oracle_mod.RefTree(pts).knn(q, k)
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert np.array_equal(a[1], want_d2) and np.array_equal(a[0], want_idx)
+    if oracle_mod.ref_available():  # where oracle/_ref is built, the live reference must still give the stored answer
+        b = oracle_mod.RefTree(pts).knn(q, k)
+        assert np.array_equal(b[1], want_d2) and np.array_equal(b[0], want_idx)
 
 
-def test_oracle_kdtree_ties_and_duplicates(oracle_mod):
+@pytest.mark.parametrize("n,k", [(1, 1), (7, 3), (101, 20), (100, 20), (5000, 1), (5000, 20), (20000, 32)])
+def test_oracle_kdtree_matches_reference_live(oracle_mod, ref_kdtree, n, k):
+    """Index-for-index against the reference kd-tree on seeded normal clouds (queries inside and far outside): the reference's
+    answers are stored with their inputs in tests/golden/ref_kdtree.npz."""
+    assert len(ref_kdtree[f"n{n}_k{k}_pts"]) == n
+    _check_against_reference(oracle_mod, ref_kdtree, f"n{n}_k{k}", min(k, n))
+
+
+def test_oracle_kdtree_ties_and_duplicates(oracle_mod, ref_kdtree):
     """Exact ties: traversal order decides (impl/nanoflann_impl.hpp:184-211); the restatement must agree with the reference."""
-    if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
-    g = np.stack(np.meshgrid(np.arange(12), np.arange(12), np.arange(6), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
-    pts = np.concatenate([g, g[:100]])  # lattice (many equal distances) + duplicates
-    q = g[::7] + np.float32(0.5)
-    a = oracle_mod.OracleTree(pts).knn(q, 8)
-    b = oracle_mod.RefTree(pts).knn(q, 8)
-    assert np.array_equal(a[1], b[1]) and np.array_equal(a[0], b[0])
+    _check_against_reference(oracle_mod, ref_kdtree, "ties", 8)
 
 
 def test_oracle_knn_vs_bruteforce(oracle_mod, golden):
