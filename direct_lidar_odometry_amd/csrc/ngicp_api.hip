@@ -1702,9 +1702,10 @@ int ngicp_compute_error(ngicp_t* h, const double T[16], double* err) {
     if (h->hook_valid != 1) throw ArgError{NGICP_ERR_STATE, "compute_error needs a preceding linearize"};
     LoopCtx c;
     prepare_loop(h, c);
-    // keep cur / have_lin, replace the trial pose
+    // keep cur / have_lin, replace the trial pose (read in stream order: behind everything this handle has enqueued)
     LmState st;
-    HIP_TRY(hipMemcpy(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     const Pose x = pose_from_colmajor_d(T);
     st.hot.xi = x;
     for (int r = 0; r < 3; ++r) {
@@ -1728,14 +1729,17 @@ int ngicp_get_correspondences(ngicp_t* h, int* corr_out, float* sqd_out) {
   return guarded(h, [&] {
     if (!corr_out) throw ArgError{NGICP_ERR_ARG, "null output"};
     if (!h->hook_valid) throw ArgError{NGICP_ERR_STATE, "no correspondences: call ngicp_linearize or ngicp_align first"};
+    // In stream order: align() returns when the solver has published `done`, and the (pass, solve) pairs it had enqueued ahead may
+    // still be on h->stream (a non-blocking stream: a null-stream copy would not wait for them).
     LmState st;
-    HIP_TRY(hipMemcpy(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t n = h->src.dev->n;
     h->knn_idx.ensure(n * sizeof(int));
     h->knn_d2.ensure(n * sizeof(float));
     LmState* dst = h->state.as<LmState>();
     hipLaunchKernelGGL(k_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->tpt[st.hot.cur].as<float4>(), h->src.dev->qpts.as<float4>(),
-                       h->src.dev->pts(), h->tgt.dev->pts(), (int)n, h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->xi_f);
+                       h->src.dev->pts(), h->tgt.dev->pts(), (int)n, h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
     HIP_TRY(hipMemcpyAsync(corr_out, h->knn_idx.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (sqd_out) HIP_TRY(hipMemcpyAsync(sqd_out, h->knn_d2.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1785,7 +1789,8 @@ int ngicp_get_lm_trace(ngicp_t* h, double* rows, size_t max_rows, size_t* n_rows
   return guarded(h, [&] {
     if (h->trace_host.empty() && h->trace_rows_dev) {
       h->trace_host.resize(h->trace_rows_dev * kTraceCols);
-      HIP_TRY(hipMemcpy(h->trace_host.data(), h->trace.p, h->trace_host.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpyAsync(h->trace_host.data(), h->trace.p, h->trace_host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));  // (stream order)
+      HIP_TRY(hipStreamSynchronize(h->stream));
     }
     const size_t n = h->trace_host.size() / kTraceCols;
     if (n_rows) *n_rows = n;

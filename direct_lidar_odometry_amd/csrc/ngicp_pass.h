@@ -68,6 +68,7 @@ struct LmHot {
   int pending;    // k_gicp_head only: the rows of a finished pass wait for the next launch's head to step the optimiser with them
   double final_H[36];  // H of the last accepted step, row-major (final_hessian_, impl/lsq_registration_impl.hpp:155,203); identity until then
   unsigned long long t_first, t_done;  // 100 MHz counter at the start of the alignment's first pass / when the solver set `done`
+  float lin_f[12];  // float pose (rows of [R|t]) the CURRENT correspondences were searched with: xi_f of the pass that was adopted last
 };
 // What a pass needs of the state, as 64 dwords (256 bytes, two cache lines of their own).  The persistent kernel reads the view of pass p
 // from entry p of a RING of views that begins at LmState::view and continues behind the state (the solver that ends pass p - 1 stores
@@ -575,6 +576,14 @@ __device__ __forceinline__ void adopt_new(LmHot& L, const double* sums) {
   L.y0 = sums[27];
   L.cur ^= 1;
   L.have_lin = 1;
+  // (the pass that produced these sums searched with float(xi); later passes may have moved xi_f on - a trial that was not adopted, or
+  // the accepted step that ended the alignment - so the squared distances of the current correspondences are taken at this pose)
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) L.lin_f[r * 4 + c] = (float)L.xi.R[r * 3 + c];
+    L.lin_f[r * 4 + 3] = (float)L.xi.t[r];
+  }
 }
 
 // One step of LsqRegistration's optimiser on the register-resident state.  Returns true when H was
@@ -978,6 +987,13 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const bool finished_now = a.mode == 0 && L.done != 0;
+  if constexpr (!PERSIST) {
+    // The state image goes back BEFORE the progress word is released (and, at the end of an alignment, before the fence below): when
+    // the host sees `done`, the device state it may read next - cur, have_lin, the float pose - is the final one.
+    // (xi_f is not carried into the other buffer of k_gicp_head when the alignment ends: after `done` nothing reads it - the exported
+    // distances use hot.lin_f, and linearize, compute_error and the next align write xi_f afresh)
+    for (int w = lane; w < (int)(sizeof(LmHot) / 4); w += 64) reinterpret_cast<int*>(&sto->hot)[w] = reinterpret_cast<const int*>(&L)[w];
+  }
   // The end of an alignment goes to the host WITHOUT a copy or a stream synchronisation: the image is written to pinned memory
   // here, then (system-scope release) the done flag; the host, which polls that word anyway, reads the image as soon as it sees
   // it - the launches it had enqueued ahead return at once behind its back.
@@ -1008,10 +1024,6 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
       v = L.have_lin;
     }
     __hip_atomic_store(st->view + (size_t)L.passes * kViewWords + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (pass L.passes comes next)
-  } else {
-    for (int w = lane; w < (int)(sizeof(LmHot) / 4); w += 64) reinterpret_cast<int*>(&sto->hot)[w] = reinterpret_cast<const int*>(&L)[w];
-    // (a state that ends an alignment keeps the float pose of its last pass: k_corr_to_original reads it from wherever the state lies)
-    if (sto != st && L.done && lane < 12) sto->xi_f[lane] = st->xi_f[lane];
   }
   NG_SSTAMP(6);
 #undef NG_SSTAMP
@@ -1492,7 +1504,7 @@ namespace ngk {
 // map correspondences (sorted source slot -> sorted target position) back to ORIGINAL indices
 __global__ void __launch_bounds__(256) k_corr_to_original(const float4* __restrict__ tpt, const float4* __restrict__ qpts, const float4* __restrict__ src_sorted,
                                                            const float4* __restrict__ tgt_sorted, int n, int* __restrict__ out_corr, float* __restrict__ out_sqd,
-                                                           const float* __restrict__ xi_f) {
+                                                           const float* __restrict__ lin_f) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 sp = qpts[i];
@@ -1502,9 +1514,9 @@ __global__ void __launch_bounds__(256) k_corr_to_original(const float4* __restri
   if (out_sqd) {
     float d = __builtin_inff();
     if (j >= 0) {
-      const float qx = ((xi_f[0] * sp.x + xi_f[1] * sp.y) + xi_f[2] * sp.z) + xi_f[3];
-      const float qy = ((xi_f[4] * sp.x + xi_f[5] * sp.y) + xi_f[6] * sp.z) + xi_f[7];
-      const float qz = ((xi_f[8] * sp.x + xi_f[9] * sp.y) + xi_f[10] * sp.z) + xi_f[11];
+      const float qx = ((lin_f[0] * sp.x + lin_f[1] * sp.y) + lin_f[2] * sp.z) + lin_f[3];
+      const float qy = ((lin_f[4] * sp.x + lin_f[5] * sp.y) + lin_f[6] * sp.z) + lin_f[7];
+      const float qz = ((lin_f[8] * sp.x + lin_f[9] * sp.y) + lin_f[10] * sp.z) + lin_f[11];
       d = sqdist(qx, qy, qz, tgt_sorted[j]);
     }
     out_sqd[o] = d;

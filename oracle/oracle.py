@@ -246,7 +246,9 @@ class OracleGICP:
     def shareSourceIndexFrom(self, other): self.L.orc_gicp_share_source_index(self.h, other.h)
     def copySourceCovariancesFrom(self, other): self.L.orc_gicp_copy_source_covs(self.h, other.h)
     def clearSourceCovariances(self): self.L.orc_gicp_clear_source_covs(self.h)
-    def swapSourceAndTarget(self): self.L.orc_gicp_swap_source_target(self.h)
+    def swapSourceAndTarget(self):
+        self.L.orc_gicp_swap_source_target(self.h)
+        self._keep["src"], self._keep["tgt"] = self._keep.get("tgt"), self._keep.get("src")  # (correspondences() sizes by the source)
 
     def calculateSourceCovariances(self):
         rc = self.L.orc_gicp_compute_source_covs(self.h)

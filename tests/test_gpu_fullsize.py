@@ -79,6 +79,27 @@ def _compare_linearisation(g, o, T, src, tgt, cs, ct):
     return len(differ)
 
 
+def _check_last_pass(g, o, guess, tg, src, tgt, cs, ct):
+    """g has just aligned from `guess`: its correspondences are those of the pass at the float pose x0 had when the last iteration began -
+    the returned pose itself when the alignment ended on rejected trials, else the pose one iteration shorter alignment returns."""
+    # (the per-pass check lives in test_gpu_passes.py, the module that documents it; pytest puts tests/ on sys.path, and the suite has
+    # no conftest helpers of its own to hold it)
+    from test_gpu_passes import check_pass
+    cg, sg = g.correspondences()
+    n, T = g.nr_iterations_ + 1, g.getFinalTransformation().copy()
+    if len(tg) and tg[-1, 7] == 0:
+        P = T
+    elif n == 1:
+        P = np.asarray(guess, np.float32)
+    else:
+        max_iter = g._p["max_iter"]
+        g.setMaximumIterations(n - 1)
+        g.align(guess)
+        P = g.getFinalTransformation().copy()
+        g.setMaximumIterations(max_iter)
+    return check_pass(f"last pass ({n})", P, cg, sg, o, src, tgt, cs, ct)["ties"]
+
+
 def _run_case(ng, orc, w, k, gate, settings, guess, tgt_sizes=None):
     g, o = ng.NanoGICP(), orc.OracleGICP()
     o.setNumThreads(16)
@@ -104,6 +125,7 @@ def _run_case(ng, orc, w, k, gate, settings, guess, tgt_sizes=None):
     o.setSourceCovariances(cs); o.setTargetCovariances(ct)
     n_tie0 = _compare_linearisation(g, o, np.asarray(guess, np.float64), w.source, w.target, cs, ct)
     g.align(guess); o.align(guess)
+    s, iters = g.stats(), g.nr_iterations_
     Tg, To = g.getFinalTransformation(), o.getFinalTransformation()
     dt, dr = clouds.pose_error(Tg, To)
     assert dt <= 1e-4 and dr <= 1e-4, (dt, dr)
@@ -119,9 +141,11 @@ def _run_case(ng, orc, w, k, gate, settings, guess, tgt_sizes=None):
         assert np.allclose(tg[:, 2:4], to[:, 2:4], rtol=1e-6)
         cg, _ = g.correspondences(); co, _ = o.correspondences()    # correspondences_ after align(): the last linearisation's
         assert np.array_equal(cg >= 0, co >= 0) and (cg != co).mean() < 1e-3
+    # The correspondences align() leaves behind are those of its last adopted linearisation, a WARM pass: checked exactly against a cold
+    # oracle search at the GPU's own float pose of that pass (test_gpu_passes.py's per-pass check), with either settings
+    n_tie_last = _check_last_pass(g, o, guess, tg, w.source, w.target, cs, ct)
     n_tie1 = _compare_linearisation(g, o, Tg.astype(np.float64), w.source, w.target, cs, ct)   # and at the final pose, distances bit for bit
-    s = g.stats()
-    return dict(dt=dt, dr=dr, ties=(n_tie0, n_tie1), iters=g.nr_iterations_, cand=s["mean_candidates"])
+    return dict(dt=dt, dr=dr, ties=(n_tie0, n_tie_last, n_tie1), iters=iters, cand=s["mean_candidates"])
 
 
 @pytest.mark.parametrize("gate", [1.0, None])

@@ -157,3 +157,46 @@ def test_oracle_zero_correspondences(oracle_mod, golden):
     o.setInputSource(golden["source"][:200]); o.setInputTarget(golden["target"][:200] + np.float32(50))
     T = o.align()
     assert np.array_equal(T, np.eye(4, dtype=np.float32)) and o.converged and o.nr_iterations == 0
+
+
+@pytest.mark.parametrize("which", ["golden", "scan_to_scan_10k"])
+def test_per_pass_method_on_the_oracle(oracle_mod, golden, which):
+    """The method of test_gpu_passes.py, proven on the oracle alone: after align(max_iter=m), correspondences() are those of a cold
+    linearize() at the float pose that align(max_iter=m-1) returned (P_0 = the guess) - index for index, distance for distance - and the
+    trace is the first rows of the full run's.  So the GPU harness compares like with like."""
+    if which == "golden":
+        src, tgt, guess, gate = golden["source"], golden["target"], golden["guess"].astype(np.float32), float(golden["max_corr_dist"])
+        settings = dict(max_iter=64)
+    else:
+        w = clouds.scan_to_scan(10_000)
+        src, tgt, guess, gate = w.source, w.target, clouds.make_pose((0.3, -0.2, 0.05), (1.0, -1.0, 4.0)).astype(np.float32), 1.0
+        settings = dict(max_iter=20, eps=1e-12)
+
+    def handle():
+        o = oracle_mod.OracleGICP()
+        o.setNumThreads(1)  # (the oracle's OpenMP reduction order depends on the thread schedule: one thread makes the trace reproducible)
+        o.setMaxCorrespondenceDistance(gate)
+        if "eps" in settings:
+            o.setTransformationEpsilon(settings["eps"]); o.setRotationEpsilon(settings["eps"])
+        o.setInputSource(src); o.setInputTarget(tgt)
+        return o
+
+    a, b = handle(), handle()
+    a.setMaximumIterations(settings["max_iter"])
+    a.align(guess)
+    full_tr, n_full = a.lm_trace(), a.nr_iterations + 1
+    b.setSourceCovariances(a.getSourceCovariances()); b.setTargetCovariances(a.getTargetCovariances())
+    assert n_full >= 3
+    P = guess
+    for m in range(1, n_full + 1):
+        a.setMaximumIterations(m)
+        a.align(guess)
+        tr = a.lm_trace()
+        k = int(np.sum(full_tr[:, 0] < m))
+        assert tr.shape == (k, 8) and np.array_equal(tr, full_tr[:k]), m
+        ca, sa = a.correspondences()
+        b.linearize(P.astype(np.float64))
+        cb, sb = b.correspondences()
+        assert np.array_equal(ca, cb) and np.array_equal(sa, sb), m
+        assert (ca >= 0).mean() > 0.5
+        P = a.getFinalTransformation()
