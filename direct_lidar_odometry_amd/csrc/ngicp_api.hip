@@ -23,6 +23,7 @@
 #include "ngicp_pass.h"
 #include "ngicp_cloudops.h"
 #include "ngicp_filters.h"
+#include "ngicp_query.h"
 
 using namespace ngk;
 
@@ -303,6 +304,11 @@ struct ngicp {
   const void* order_src = nullptr;  // source index / group count the contents of grp_order were built for
   int order_groups = -1;
   DevBuf tpt[2], mahal[2], partials, state, trace, tfinal, out_xyz, scratch16, queries, knn_idx, knn_d2, sums, ticket;
+  // queries on the indexed clouds (ngicp_query.h): fitness score, radius search (results of the last search stay on the device)
+  DevBuf fit_T, fit_part, fit_out, rad_counts, rad_offsets, rad_keys, rad_long;
+  size_t rad_total = 0;
+  bool rad_valid = false;
+  hipEvent_t ev_q_a = nullptr, ev_q_b = nullptr;  // around the kernels of the last query call (ngicp_stats::query_ms)
   std::vector<hipEvent_t> prof_events;  // pairs around each pass launch when profiling is on
   int* h_progress = nullptr;  // pinned: {passes done | kProgressDone}, written by the solver (SolveArgs::progress_host)
   LmState* pin_state = nullptr;  // pinned [2]: the state image an align uploads / the one it reads back (no staging copies)
@@ -1385,6 +1391,68 @@ int set_cloud(ngicp* h, Slot& slot, const float* xyz, size_t n, size_t stride, u
   });
 }
 
+// ---- queries on the indexed clouds (ngicp_query.h) ----
+// which: 0 = source, 1 = target (as ngicp_covs_shard_*); the slot's cloud is uploaded and indexed if it was only registered
+DeviceCloud& query_cloud(ngicp* h, int which) {
+  Slot& s = which ? h->tgt : h->src;
+  ensure_slot_ready(h, s, which ? "target" : "source");
+  return *s.dev;
+}
+void check_which(int which) {
+  if (which != 0 && which != 1) throw ArgError{NGICP_ERR_ARG, "which must be 0 (source) or 1 (target)"};
+}
+
+// strided host points -> h->queries (float4 {x, y, z, 1})
+void upload_queries(ngicp* h, const float* q, size_t nq, size_t stride) {
+  std::vector<float> packed(nq * 4);
+  for (size_t i = 0; i < nq; ++i) {
+    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(q) + i * stride);
+    packed[i * 4 + 0] = p[0];
+    packed[i * 4 + 1] = p[1];
+    packed[i * 4 + 2] = p[2];
+    packed[i * 4 + 3] = 1.f;
+  }
+  h->queries.ensure(nq * sizeof(float4));
+  HIP_TRY(hipMemcpyAsync(h->queries.p, packed.data(), nq * sizeof(float4), hipMemcpyHostToDevice, h->stream));
+}
+
+void query_timing_done(ngicp* h) {  // after the stream has been synchronised behind ev_q_b
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, h->ev_q_a, h->ev_q_b));
+  h->stats.query_ms = ms;
+}
+
+// KdTreeFLANN::nearestKSearch (include/nano_gicp/nanoflann.hpp:141-152) on either index
+void knn_impl(ngicp* h, int which, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {
+  check_which(which);
+  if (!q || !idx || !d2) throw ArgError{NGICP_ERR_ARG, "null pointer"};
+  if (nq == 0) return;
+  if (stride < 12 || stride % 4) throw ArgError{NGICP_ERR_ARG, "bad stride"};
+  DeviceCloud& T = query_cloud(h, which);
+  if (k <= 0) throw ArgError{NGICP_ERR_ARG, "k must be positive"};
+  if (k > 32 || (size_t)k > T.n) throw ArgError{NGICP_ERR_K_TOO_LARGE, "k exceeds the cloud size or the engine limit of 32"};
+  upload_queries(h, q, nq, stride);
+  h->knn_idx.ensure(nq * k * sizeof(int));
+  h->knn_d2.ensure(nq * k * sizeof(float));
+  const dim3 grid((unsigned)((nq + kKnnPairs - 1) / kKnnPairs)), block(kKnnBlock);  // a pair of lanes per query
+  HIP_TRY(hipEventRecord(h->ev_q_a, h->stream));
+  if (k <= 10)
+    hipLaunchKernelGGL(k_knn_queries<10>, grid, block, 0, h->stream, T.pts(), T.cells(), T.grid, h->queries.as<float4>(), (int)nq, k,
+                       h->knn_idx.as<int>(), h->knn_d2.as<float>());
+  else if (k <= 20)
+    hipLaunchKernelGGL(k_knn_queries<20>, grid, block, 0, h->stream, T.pts(), T.cells(), T.grid, h->queries.as<float4>(), (int)nq, k,
+                       h->knn_idx.as<int>(), h->knn_d2.as<float>());
+  else
+    hipLaunchKernelGGL(k_knn_queries<32>, grid, block, 0, h->stream, T.pts(), T.cells(), T.grid, h->queries.as<float4>(), (int)nq, k,
+                       h->knn_idx.as<int>(), h->knn_d2.as<float>());
+  HIP_TRY(hipEventRecord(h->ev_q_b, h->stream));
+  HIP_TRY(hipMemcpyAsync(idx, h->knn_idx.p, nq * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(d2, h->knn_d2.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  query_timing_done(h);
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1416,6 +1484,8 @@ int ngicp_create(int device, ngicp_t** out) {
     HIP_TRY(hipEventCreate(&h->ev_cov_a));
     HIP_TRY(hipEventCreate(&h->ev_cov_b));
     HIP_TRY(hipEventCreateWithFlags(&h->ev_fence, hipEventDisableTiming));
+    HIP_TRY(hipEventCreate(&h->ev_q_a));
+    HIP_TRY(hipEventCreate(&h->ev_q_b));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_state), 2 * sizeof(LmState), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_final), sizeof(LmHot), hipHostMallocDefault));
     h->order_flag.ensure(64);
@@ -1498,6 +1568,8 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_cov_a) (void)hipEventDestroy(h->ev_cov_a);
   if (h->ev_cov_b) (void)hipEventDestroy(h->ev_cov_b);
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
+  if (h->ev_q_a) (void)hipEventDestroy(h->ev_q_a);
+  if (h->ev_q_b) (void)hipEventDestroy(h->ev_q_b);
   ngk_filter_free(&h->fws);
   hipStream_t s = h->stream;
   delete h;
@@ -1748,40 +1820,126 @@ int ngicp_get_correspondences(ngicp_t* h, int* corr_out, float* sqd_out) {
 }
 
 int ngicp_target_knn(ngicp_t* h, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {
+  return guarded(h, [&] { knn_impl(h, 1, q, nq, stride, k, idx, d2); });
+}
+
+// ---- queries on the indexed clouds (ngicp_query.h) ----
+int ngicp_knn_search(ngicp_t* h, int which, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {
+  return guarded(h, [&] { knn_impl(h, which, q, nq, stride, k, idx, d2); });
+}
+
+int ngicp_radius_search(ngicp_t* h, int which, const float* q, size_t nq, size_t stride, double radius, size_t* offsets, size_t* total) {
   return guarded(h, [&] {
-    if (!q || !idx || !d2) throw ArgError{NGICP_ERR_ARG, "null pointer"};
-    if (nq == 0) return;
-    if (stride < 12 || stride % 4) throw ArgError{NGICP_ERR_ARG, "bad stride"};
-    ensure_slot_ready(h, h->tgt, "target");
-    DeviceCloud& T = *h->tgt.dev;
-    if (k <= 0) throw ArgError{NGICP_ERR_ARG, "k must be positive"};
-    if (k > 32 || (size_t)k > T.n) throw ArgError{NGICP_ERR_K_TOO_LARGE, "k exceeds the cloud size or the engine limit of 32"};
-    std::vector<float> packed(nq * 4);
-    for (size_t i = 0; i < nq; ++i) {
-      const float* p = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(q) + i * stride);
-      packed[i * 4 + 0] = p[0];
-      packed[i * 4 + 1] = p[1];
-      packed[i * 4 + 2] = p[2];
-      packed[i * 4 + 3] = 1.f;
+    check_which(which);
+    if (!offsets || !total) throw ArgError{NGICP_ERR_ARG, "null output"};
+    if (nq && !q) throw ArgError{NGICP_ERR_ARG, "null pointer"};
+    if (nq && (stride < 12 || stride % 4)) throw ArgError{NGICP_ERR_ARG, "bad stride"};
+    if (nq > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "too many queries for int indices"};
+    h->rad_valid = false;
+    h->rad_total = 0;
+    *total = 0;
+    if (nq == 0) {
+      offsets[0] = 0;
+      h->rad_valid = true;
+      return;
     }
-    h->queries.ensure(nq * sizeof(float4));
-    h->knn_idx.ensure(nq * k * sizeof(int));
-    h->knn_d2.ensure(nq * k * sizeof(float));
-    HIP_TRY(hipMemcpyAsync(h->queries.p, packed.data(), nq * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-    const dim3 grid((unsigned)((nq + kKnnPairs - 1) / kKnnPairs)), block(kKnnBlock);  // a pair of lanes per query
-    if (k <= 10)
-      hipLaunchKernelGGL(k_knn_queries<10>, grid, block, 0, h->stream, T.pts(), T.cells(), T.grid, h->queries.as<float4>(), (int)nq, k,
-                         h->knn_idx.as<int>(), h->knn_d2.as<float>());
-    else if (k <= 20)
-      hipLaunchKernelGGL(k_knn_queries<20>, grid, block, 0, h->stream, T.pts(), T.cells(), T.grid, h->queries.as<float4>(), (int)nq, k,
-                         h->knn_idx.as<int>(), h->knn_d2.as<float>());
-    else
-      hipLaunchKernelGGL(k_knn_queries<32>, grid, block, 0, h->stream, T.pts(), T.cells(), T.grid, h->queries.as<float4>(), (int)nq, k,
-                         h->knn_idx.as<int>(), h->knn_d2.as<float>());
-    HIP_TRY(hipMemcpyAsync(idx, h->knn_idx.p, nq * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(d2, h->knn_d2.p, nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    DeviceCloud& C = query_cloud(h, which);
+    const float rf = (float)radius;  // RadiusResultSet<float,int> (nanoflann.hpp:161)
+    if (!(rf > 0.f)) {  // d2 < radius holds for no d2 >= 0
+      std::fill(offsets, offsets + nq + 1, (size_t)0);
+      h->rad_valid = true;
+      return;
+    }
+    // the cube the cell ranges must cover: sqrt(radius) rounded up, plus the grid's slack for the float cell assignment
+    const float reach = (float)(std::sqrt((double)rf) * (1.0 + 1e-6)) + C.grid.slack;
+    const int n = (int)nq;
+    upload_queries(h, q, nq, stride);
+    h->rad_counts.ensure(nq * sizeof(int));
+    h->rad_offsets.ensure((nq + 1) * sizeof(unsigned long long));
+    h->rad_long.ensure((nq + 1) * sizeof(int));  // {number of long segments, their queries}
+    const int ntiles = (n + kScanTile - 1) / kScanTile;
+    h->tile_sums.ensure((size_t)ntiles * sizeof(unsigned long long));
+    int* n_long_dev = h->rad_long.as<int>();
+    HIP_TRY(hipEventRecord(h->ev_q_a, h->stream));
+    HIP_TRY(hipMemsetAsync(n_long_dev, 0, sizeof(int), h->stream));
+    const dim3 wgrid((unsigned)((nq * kRadLanes + kRadBlock - 1) / kRadBlock));
+    hipLaunchKernelGGL(k_radius_walk<false>, wgrid, dim3(kRadBlock), 0, h->stream, C.pts(), C.cells(), C.grid, h->queries.as<float4>(), n, rf, reach,
+                       h->rad_counts.as<int>(), (const unsigned long long*)nullptr, (unsigned long long*)nullptr, n_long_dev + 1, n_long_dev);
+    hipLaunchKernelGGL(k_scan64_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, h->rad_counts.as<int>(), n, h->tile_sums.as<unsigned long long>());
+    hipLaunchKernelGGL(k_scan2_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<unsigned long long>(), ntiles);
+    hipLaunchKernelGGL(k_scan64_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, h->rad_counts.as<int>(), n, h->tile_sums.as<unsigned long long>(),
+                       h->rad_offsets.as<unsigned long long>());
+    // the one read-back inside the search: the offsets (the total sizes the key buffer) and the number of long segments
+    static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets are copied as they are");
+    int n_long = 0;
+    HIP_TRY(hipMemcpyAsync(offsets, h->rad_offsets.p, (nq + 1) * sizeof(size_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&n_long, n_long_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t tot = offsets[nq];
+    if (n_long > 0 && C.n > ((size_t)1 << 30)) throw ArgError{NGICP_ERR_ARG, "segments beyond 2^30 points are not sorted by this engine"};
+    if (tot > ((size_t)1 << 40) / sizeof(unsigned long long)) throw HipError{hipErrorOutOfMemory, "radius search result buffer", __FILE__, __LINE__};
+    if (tot) {
+      h->rad_keys.ensure(tot * sizeof(unsigned long long));
+      hipLaunchKernelGGL(k_radius_walk<true>, wgrid, dim3(kRadBlock), 0, h->stream, C.pts(), C.cells(), C.grid, h->queries.as<float4>(), n, rf, reach,
+                         (int*)nullptr, h->rad_offsets.as<unsigned long long>(), h->rad_keys.as<unsigned long long>(), (int*)nullptr, (int*)nullptr);
+      hipLaunchKernelGGL(k_seg_sort_short, dim3((unsigned)((nq + kSegBlock / 64 - 1) / (kSegBlock / 64))), dim3(kSegBlock), 0, h->stream,
+                         h->rad_offsets.as<unsigned long long>(), n, h->rad_keys.as<unsigned long long>());
+      if (n_long > 0)
+        hipLaunchKernelGGL(k_seg_sort_long, dim3((unsigned)n_long), dim3(kSegLongBlock), 0, h->stream, h->rad_offsets.as<unsigned long long>(), n_long_dev + 1,
+                           h->rad_keys.as<unsigned long long>());
+    }
+    HIP_TRY(hipEventRecord(h->ev_q_b, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipGetLastError());
+    query_timing_done(h);
+    h->rad_total = tot;
+    h->rad_valid = true;
+    *total = tot;
+  });
+}
+
+int ngicp_radius_fetch(ngicp_t* h, int* idx, float* sqd, size_t capacity) {
+  return guarded(h, [&] {
+    if (!idx || !sqd) throw ArgError{NGICP_ERR_ARG, "null output"};
+    if (!h->rad_valid) throw ArgError{NGICP_ERR_STATE, "no radius search to fetch"};
+    const size_t tot = h->rad_total;
+    if (capacity < tot) throw ArgError{NGICP_ERR_ARG, "capacity is smaller than the search's total"};
+    if (tot == 0) return;
+    h->knn_idx.ensure(tot * sizeof(int));
+    h->knn_d2.ensure(tot * sizeof(float));
+    hipLaunchKernelGGL(k_radius_unpack, dim3((unsigned)std::min<size_t>((tot + 255) / 256, 4096)), dim3(256), 0, h->stream, h->rad_keys.as<unsigned long long>(), tot,
+                       h->knn_idx.as<int>(), h->knn_d2.as<float>());
+    HIP_TRY(hipMemcpyAsync(idx, h->knn_idx.p, tot * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(sqd, h->knn_d2.p, tot * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+  });
+}
+
+int ngicp_fitness_score(ngicp_t* h, const float T_colmajor[16], double max_range, double* score, size_t* n_inliers) {
+  return guarded(h, [&] {
+    if (!score) throw ArgError{NGICP_ERR_ARG, "null output"};
+    DeviceCloud& S = query_cloud(h, 0);
+    DeviceCloud& T = query_cloud(h, 1);
+    const int n = (int)S.n;
+    const int nb = (n + kKnnPairs - 1) / kKnnPairs;
+    h->fit_T.ensure(16 * sizeof(float));
+    h->fit_part.ensure((size_t)nb * sizeof(double2));
+    h->fit_out.ensure(sizeof(double2));
+    HIP_TRY(hipMemcpyAsync(h->fit_T.p, T_colmajor ? T_colmajor : h->final_T, 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_q_a, h->stream));
+    hipLaunchKernelGGL(k_fitness, dim3((unsigned)nb), dim3(kKnnBlock), 0, h->stream, S.pts(), n, h->fit_T.as<float>(), T.pts(), T.cells(), T.grid, max_range,
+                       h->fit_part.as<double2>());
+    hipLaunchKernelGGL(k_fitness_final, dim3(1), dim3(kFitnessFinalBlock), 0, h->stream, h->fit_part.as<double2>(), nb, h->fit_out.as<double2>());
+    HIP_TRY(hipEventRecord(h->ev_q_b, h->stream));
+    double2 r;
+    HIP_TRY(hipMemcpyAsync(&r, h->fit_out.p, sizeof(r), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    query_timing_done(h);
+    const size_t cnt = (size_t)r.y;
+    *score = cnt ? r.x / r.y : std::numeric_limits<double>::max();
+    if (n_inliers) *n_inliers = cnt;
   });
 }
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import enum
 import os
+import sys
 
 import numpy as np
 
@@ -52,7 +53,7 @@ class Stats(C.Structure):
                 ("outer_iterations", C.c_int), ("lm_trials", C.c_int), ("mean_candidates", C.c_double), ("valid_fraction", C.c_double),
                 ("index_build_ms", C.c_double), ("covariance_ms", C.c_double), ("upload_ms", C.c_double), ("voxel_size", C.c_double),
                 ("grid_dims", C.c_int * 3), ("lanes_per_query", C.c_int), ("passes_timed", C.c_int), ("n_src", C.c_longlong), ("n_tgt", C.c_longlong), ("staged_fraction", C.c_double), ("submap_ms", C.c_double),
-                ("device_allocs", C.c_longlong), ("host_wait_spins", C.c_longlong)]
+                ("device_allocs", C.c_longlong), ("host_wait_spins", C.c_longlong), ("query_ms", C.c_double)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -74,6 +75,7 @@ EXPORTS = [
     "ngicp_submap_set", "ngicp_get_target_points", "ngicp_transform_source", "ngicp_transform_cloud", "ngicp_measure_copy_bandwidth",
     "ngicp_preprocess_scan", "ngicp_set_source_preprocessed", "ngicp_map_add", "ngicp_map_voxel_filter", "ngicp_map_size", "ngicp_map_get",
     "ngicp_map_clear", "ngicp_math_selftest", "ngicp_set_host_wait", "ngicp_covs_shard_begin", "ngicp_covs_shard_compute", "ngicp_covs_shard_commit",
+    "ngicp_knn_search", "ngicp_radius_search", "ngicp_radius_fetch", "ngicp_fitness_score",
 ]
 
 _lib = None
@@ -121,6 +123,10 @@ def load_library() -> C.CDLL:
     L.ngicp_compute_error.argtypes = [vp, c_f64p, c_f64p]
     L.ngicp_get_correspondences.argtypes = [vp, c_i32p, c_f32p]
     L.ngicp_target_knn.argtypes = [vp, c_f32p, C.c_size_t, C.c_size_t, C.c_int, c_i32p, c_f32p]
+    L.ngicp_knn_search.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, C.c_int, c_i32p, c_f32p]
+    L.ngicp_radius_search.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ngicp_radius_fetch.argtypes = [vp, c_i32p, c_f32p, C.c_size_t]
+    L.ngicp_fitness_score.argtypes = [vp, c_f32p, C.c_double, c_f64p, C.POINTER(C.c_size_t)]
     L.ngicp_get_lm_trace.argtypes = [vp, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ngicp_set_profiling.argtypes = [vp, C.c_int]
@@ -366,6 +372,40 @@ class NanoGICP:
         idx = np.empty((q.shape[0], k), dtype=np.int32); d2 = np.empty((q.shape[0], k), dtype=np.float32)
         self._ck(self._L.ngicp_target_knn(self._h, _p(q, c_f32p), q.shape[0], q.strides[0], k, _p(idx, c_i32p), _p(d2, c_f32p)))
         return idx, d2
+
+    # ---- the search surface of the reference's trees and of pcl::Registration (include/ngicp.h "queries") ----
+    _WHICH = {"source": 0, "target": 1}
+
+    def fitness(self, max_range: float = sys.float_info.max, T=None):
+        """-> (score, n_inliers): pcl::Registration::getFitnessScore(max_range) over the source transformed by T (None: the last
+        align's final_transformation_, identity before any).  max_range is a SQUARED distance; score is DBL_MAX when no point counts."""
+        t = None if T is None else _colmajor16(T, np.float32)
+        score, n = C.c_double(0), C.c_size_t(0)
+        self._ck(self._L.ngicp_fitness_score(self._h, None if t is None else _p(t, c_f32p), float(max_range), C.byref(score), C.byref(n)))
+        return score.value, n.value
+
+    def getFitnessScore(self, max_range: float = sys.float_info.max, T=None) -> float:
+        return self.fitness(max_range, T)[0]
+
+    def nearestKSearch(self, queries, k: int, which: str = "target"):
+        """source_kdtree_ / target_kdtree_ ->nearestKSearch for every row of `queries`: (idx (nq, k), d2 (nq, k)), ascending."""
+        q = _cloud(queries)
+        idx = np.empty((q.shape[0], k), dtype=np.int32); d2 = np.empty((q.shape[0], k), dtype=np.float32)
+        self._ck(self._L.ngicp_knn_search(self._h, self._WHICH[which], _p(q, c_f32p), q.shape[0], q.strides[0], k, _p(idx, c_i32p), _p(d2, c_f32p)))
+        return idx, d2
+
+    def radiusSearch(self, queries, radius: float, which: str = "target"):
+        """->radiusSearch for every row of `queries`: (offsets (nq + 1,), idx, d2); query i's hits are [offsets[i], offsets[i+1]),
+        d2 < float(radius) (radius is a SQUARED distance), in ascending (d2, index) order."""
+        q = _cloud(queries)
+        nq = q.shape[0]
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        total = C.c_size_t(0)
+        self._ck(self._L.ngicp_radius_search(self._h, self._WHICH[which], _p(q, c_f32p), nq, q.strides[0], float(radius),
+                                             offsets.ctypes.data_as(C.POINTER(C.c_size_t)), C.byref(total)))
+        idx = np.empty(total.value, dtype=np.int32); d2 = np.empty(total.value, dtype=np.float32)
+        self._ck(self._L.ngicp_radius_fetch(self._h, _p(idx, c_i32p), _p(d2, c_f32p), total.value))
+        return offsets.astype(np.int64), idx, d2
 
     def lm_trace(self) -> np.ndarray:
         n = C.c_size_t(0)

@@ -95,11 +95,74 @@ class NanoGICP {
   using KdTreeReciprocalPtr = typename KdTreeReciprocal::Ptr;
 
   // ---- proxies for the public data members DLO assigns to ----
-  struct IndexRef {  // stands for std::shared_ptr<nanoflann::KdTreeFLANN<PointSource>> source_kdtree_
+  struct IndexRef {  // stands for std::shared_ptr<nanoflann::KdTreeFLANN<PointSource>> source_kdtree_ / target_kdtree_
     NanoGICP* owner = nullptr;
+    bool source = true;  // which index: the source's or the target's
     IndexRef& operator=(const IndexRef& o) {
       if (owner && o.owner && owner != o.owner) owner->check(ngicp_share_source_index(owner->h_, o.owner->h_), "share_source_index");
       return *this;
+    }
+    // `gicp.target_kdtree_->radiusSearch(...)` as with the reference's shared_ptr
+    IndexRef* operator->() { return this; }
+    const IndexRef* operator->() const { return this; }
+    // KdTreeFLANN::nearestKSearch / radiusSearch (include/nano_gicp/nanoflann.hpp:141-175): same signatures and return values (the
+    // number found).  radius is a SQUARED distance and a hit is d2 < (float)radius, as in the reference; the hits come in ascending
+    // (d2, index) order where the reference's unsorted trees give kd-tree visiting order.  The index is always the slot's current
+    // cloud.  A single point is a GPU round trip (tens of microseconds): for many points use the batched forms below.
+    template <class PointT>
+    int nearestKSearch(const PointT& point, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) const {
+      k_indices.resize(k > 0 ? k : 0);
+      k_sqr_distances.resize(k_indices.size());
+      if (!owner->check(ngicp_knn_search(owner->h_, source ? 0 : 1, point.data, 1, 12, k, k_indices.data(), k_sqr_distances.data()), "nearestKSearch")) {
+        k_indices.clear();
+        k_sqr_distances.clear();
+        return 0;
+      }
+      return k;
+    }
+    template <class PointT>
+    int radiusSearch(const PointT& point, double radius, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) const {
+      std::vector<size_t> offsets;
+      return (int)search_radius(point.data, 1, 12, radius, offsets, k_indices, k_sqr_distances);
+    }
+    // batched: every point of `queries`; k_indices / k_sqr_distances are row-major [queries.size()][k].  Returns queries.size() * k.
+    template <class P>
+    size_t nearestKSearch(const types::Cloud<P>& queries, int k, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances) const {
+      const size_t nq = queries.size(), m = k > 0 ? nq * (size_t)k : 0;
+      k_indices.resize(m);
+      k_sqr_distances.resize(m);
+      if (nq && !owner->check(ngicp_knn_search(owner->h_, source ? 0 : 1, queries.points[0].data, nq, sizeof(P), k, k_indices.data(), k_sqr_distances.data()),
+                              "nearestKSearch")) {
+        k_indices.clear();
+        k_sqr_distances.clear();
+        return 0;
+      }
+      return m;
+    }
+    // batched: query i's hits are [offsets[i], offsets[i + 1]) of the flat vectors (offsets has queries.size() + 1 entries).  Returns
+    // the total number of hits.
+    template <class P>
+    size_t radiusSearch(const types::Cloud<P>& queries, double radius, std::vector<size_t>& offsets, std::vector<int>& k_indices,
+                        std::vector<float>& k_sqr_distances) const {
+      return search_radius(queries.size() ? queries.points[0].data : nullptr, queries.size(), sizeof(P), radius, offsets, k_indices, k_sqr_distances);
+    }
+
+   private:
+    size_t search_radius(const float* xyz, size_t nq, size_t stride, double radius, std::vector<size_t>& offsets, std::vector<int>& idx,
+                         std::vector<float>& d2) const {
+      offsets.assign(nq + 1, 0);
+      size_t total = 0;
+      bool ok = owner->check(ngicp_radius_search(owner->h_, source ? 0 : 1, xyz, nq, stride, radius, offsets.data(), &total), "radiusSearch");
+      idx.resize(ok ? total : 0);
+      d2.resize(idx.size());
+      if (ok && total && !owner->check(ngicp_radius_fetch(owner->h_, idx.data(), d2.data(), total), "radiusSearch")) ok = false;
+      if (!ok) {
+        offsets.assign(nq + 1, 0);
+        idx.clear();
+        d2.clear();
+        return 0;
+      }
+      return total;
     }
   };
   struct CovRef {  // stands for std::vector<Eigen::Matrix4d> source_covs_ / target_covs_
@@ -136,6 +199,8 @@ class NanoGICP {
       h_ = nullptr;
     }
     source_kdtree_.owner = target_kdtree_.owner = this;
+    source_kdtree_.source = true;
+    target_kdtree_.source = false;
     source_covs_.owner = target_covs_.owner = this;
     source_covs_.source = true;
     target_covs_.source = false;
@@ -268,6 +333,15 @@ class NanoGICP {
   bool hasConverged() const { return converged_; }
   const types::Matrix6d& getFinalHessian() const { return final_hessian_; }
   int getNrIterations() const { return nr_iterations_; }
+  // pcl::Registration::getFitnessScore(max_range): the mean squared 1-NN distance of the source transformed by
+  // final_transformation_ over the points with a squared distance <= max_range (a SQUARED distance); DBL_MAX when none counts.
+  // Computed on the GPU from the device-resident clouds (csrc/ngicp_query.h).  The reference would dereference the null search tree
+  // DLO hands PCL (odom.cc:116-120); this returns what PCL computes with a built tree.
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) {
+    double score = std::numeric_limits<double>::max();
+    if (h_) check(ngicp_fitness_score(h_, final_transformation_.data(), max_range, &score, nullptr), "getFitnessScore");
+    return score;
+  }
   ngicp_t* handle() { return h_; }
 
   // ---- extensions with no reference counterpart (include/ngicp.h "keyframe store", "rigid transform"): the keyframes and the

@@ -141,6 +141,29 @@ int ngicp_get_correspondences(ngicp_t* h, int* corr_n, float* sq_dist_n_or_null)
 /* exact k-NN of arbitrary query points in the TARGET cloud (KdTreeFLANN::nearestKSearch,
  * include/nano_gicp/nanoflann.hpp:141-152): original target indices + float squared distances, ascending. */
 int ngicp_target_knn(ngicp_t* h, const float* queries_xyz, size_t nq, size_t stride_bytes, int k, int* idx_nq_k, float* sqd_nq_k);
+/* --- queries on the indexed clouds (the public search surface of the reference's trees and of pcl::Registration) ---
+ * which: 0 = source index, 1 = target index (as ngicp_covs_shard_*).  The index is always the slot's CURRENT cloud (a registered
+ * source is uploaded and indexed first); the reference's source_kdtree_ can still index the previous cloud after registerInputSource
+ * without a tree assignment (impl/nano_gicp_impl.hpp:113-118).  Exact searches (eps = 0, like the reference).
+ *
+ * ngicp_knn_search: source_kdtree_ / target_kdtree_ ->nearestKSearch (include/nano_gicp/nanoflann.hpp:141-152): ngicp_target_knn's
+ * contract on either index (original indices + float squared distances, ascending; k <= 32 and k <= n, else NGICP_ERR_K_TOO_LARGE). */
+int ngicp_knn_search(ngicp_t* h, int which, const float* queries_xyz, size_t nq, size_t stride_bytes, int k, int* idx_nq_k, float* sqd_nq_k);
+/* ->radiusSearch (nanoflann.hpp:155-175): the points whose float squared distance is STRICTLY below (float)radius - radius is a
+ * squared distance, as in RadiusResultSet<float,int> (impl/nanoflann_impl.hpp:239-262), so radius <= 0 finds nothing.  The reference's
+ * trees are unsorted (nanoflann.hpp:68,113-117) and return kd-tree visiting order; the engine returns the same set in ascending
+ * (d2, original index) order.  ngicp_radius_search runs the search and writes offsets[0..nq] (query i's results are
+ * [offsets[i], offsets[i+1])) and *total = offsets[nq]; the results stay on the device until ngicp_radius_fetch copies them
+ * (capacity >= total, else NGICP_ERR_ARG).  A result too large for the device is NGICP_ERR_HIP. */
+int ngicp_radius_search(ngicp_t* h, int which, const float* queries_xyz, size_t nq, size_t stride_bytes, double radius,
+                        size_t* offsets_nq_plus_1, size_t* total);
+int ngicp_radius_fetch(ngicp_t* h, int* idx, float* sqd, size_t capacity);
+/* pcl::Registration::getFitnessScore(max_range) (PCL, not under the reference tree; restated in csrc/ngicp_query.h): the source
+ * transformed by T (pcl::transformPointCloud), each point's exact 1-NN squared distance d2 in the target, the mean of the d2 with
+ * (double)d2 <= max_range (a SQUARED distance; DBL_MAX = PCL's default), DBL_MAX when none counts.
+ * T_colmajor_or_null: NULL = final_transformation_ of the last align (identity before any, as PCL).  Where the reference would
+ * dereference the null search tree DLO hands PCL (src/dlo/odom.cc:116-120), this returns what PCL computes with a built tree. */
+int ngicp_fitness_score(ngicp_t* h, const float T_colmajor_or_null[16], double max_range, double* score, size_t* n_inliers_or_null);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
@@ -176,6 +199,7 @@ typedef struct ngicp_stats {
   long long device_allocs;  /* hipMalloc calls made by this process's engine buffers so far (a call that grows a buffer in the middle of
                                a frame shows up as a latency outlier: two readings around a call attribute it) */
   long long host_wait_spins; /* polls of the solver's progress word during the last ngicp_align() (busy or yielding, see below) */
+  double query_ms;          /* device time (HIP events on the handle's stream) of the kernels of the last knn / radius / fitness query */
 } ngicp_stats;
 int ngicp_get_stats(ngicp_t* h, ngicp_stats* out);
 /* HIP-event timing of the k_gicp_pass launches inside align (two event records per timed launch; off by default).
