@@ -258,11 +258,12 @@ __device__ __forceinline__ void knn_search(const Grid& g, const float4* __restri
     const float frac = fminf(fmaxf((qx - (g.ox + (float)xa * g.h)) / ((float)(xb + 1 - xa) * g.h), 0.f), 1.f);
     // lower bounds of |dx| to the two end cells of an inner row (cells cx-r and cx+r)
     const float xl = fmaxf(qx - (g.ox + (float)(cx - r + 1) * g.h) - g.slack, 0.f), xr = fmaxf((g.ox + (float)(cx + r) * g.h) - qx - g.slack, 0.f);
-    const int side = 2 * r + 1;
-    for (int t = 0; t < side * side; ++t) {
-      const int dz = t / side - r, dy = t % side - r;
-      const int y = cy + dy, z = cz + dz;
-      if (y < 0 || y >= g.ny || z < 0 || z >= g.nz) continue;
+    // the window's rows inside the grid, z-major (a walk over all (2r+1)^2 rows of the window would cost O(r^3) per query on a grid
+    // that is long in x and one cell thick: a query far from it needs r up to nx)
+    const int za = max(cz - r, 0), zb = min(cz + r, g.nz - 1), ya = max(cy - r, 0), yb = min(cy + r, g.ny - 1);
+    for (int z = za; z <= zb; ++z)
+    for (int y = ya; y <= yb; ++y) {
+      const int dz = z - cz, dy = y - cy;
       const float gap = row_gap_sq(g, y, z, cy, cz, qy, qz);
       if (gap >= worst) continue;
       const int row = (z * g.ny + y) * g.nx;

@@ -82,9 +82,9 @@ def _compare_linearisation(g, o, T, src, tgt, cs, ct):
 def _check_last_pass(g, o, guess, tg, src, tgt, cs, ct):
     """g has just aligned from `guess`: its correspondences are those of the pass at the float pose x0 had when the last iteration began -
     the returned pose itself when the alignment ended on rejected trials, else the pose one iteration shorter alignment returns."""
-    # (the per-pass check lives in test_gpu_passes.py, the module that documents it; pytest puts tests/ on sys.path, and the suite has
-    # no conftest helpers of its own to hold it)
-    from test_gpu_passes import check_pass
+    # (the per-pass check lives in tests/_pass_check.py, shared with test_gpu_passes.py, the module that documents it; pytest puts
+    # tests/ on sys.path)
+    from _pass_check import check_pass
     cg, sg = g.correspondences()
     n, T = g.nr_iterations_ + 1, g.getFinalTransformation().copy()
     if len(tg) and tg[-1, 7] == 0:
