@@ -24,6 +24,7 @@
 #include "ngicp_cloudops.h"
 #include "ngicp_filters.h"
 #include "ngicp_query.h"
+#include "ngicp_batch.h"
 
 using namespace ngk;
 
@@ -257,6 +258,25 @@ struct Params {
   int num_threads = 0;
 };
 
+// Working set of ngicp_align_batch: everything an alignment writes, once per lane, in buffers of its own - the
+// handle's single-alignment state is not touched.  Grow-only, reused from call to call.
+struct BatchWs {
+  DevBuf recs;      // the lane records, one upload per call: [cap] LmState images, then [cap] PassArgs, then [cap] SolveArgs
+  DevBuf tpt, mahal;  // [lanes][2][n_src] float4 / [lanes][2][n_src][6] double
+  DevBuf partials, order, cost, far, trace;  // [lanes][groups][32]; [lanes][groups] launch order / cost; [lanes][batches]; [lanes][rows][8]
+  DevBuf flags;     // [lanes] x {order flag, ticket, -, -}
+  DevBuf fit_T, fit_part, fit_out;  // ngicp_fitness_score_batch
+  unsigned char* pin_recs = nullptr;  // pinned image of `recs` (kBatchMaxLanes lanes)
+  int* pin_progress = nullptr;        // pinned [kBatchMaxLanes] x kProgressStride: a lane's {passes done | kProgressDone}
+  LmHot* pin_final = nullptr;         // pinned [kBatchMaxLanes]: a lane's state image when it is done
+  const void* order_src = nullptr;    // source index / group count / lanes the launch orders on the device were built for
+  int order_groups = -1, order_lanes = 0;
+  int lanes = 0;                      // lanes of the last call (ngicp_batch_get_lm_trace)
+  size_t trace_stride = 0;            // doubles between two lanes' traces
+  std::vector<size_t> trace_rows;     // rows of each lane's trace on the device
+  static constexpr int kProgressStride = 16;  // a 64-byte line per lane's word
+};
+
 }  // namespace
 
 struct ngicp {
@@ -324,6 +344,8 @@ struct ngicp {
   std::vector<double> trace_host;
   size_t trace_rows_dev = 0;  // rows of the last align's LM trace still on the device
   ngicp_stats stats{};
+
+  BatchWs batch;  // ngicp_align_batch / ngicp_fitness_score_batch
 
   // sharded stepping
   bool sharded_active = false;
@@ -767,7 +789,10 @@ struct LoopCtx {
   int nblocks;
 };
 
-void prepare_loop(ngicp* h, LoopCtx& c) {
+// own_buffers false (ngicp_align_batch): slots and covariances are readied and the fields every lane shares are filled in, but none of
+// the handle's single-alignment buffers is sized or referred to (the caller supplies every per-alignment pointer) and no stats field is
+// written: what the getters of the last ngicp_align read stays where it is.
+void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true) {
   ensure_slot_ready(h, h->src, "source");
   ensure_slot_ready(h, h->tgt, "target");
   // lazy covariances (impl/nano_gicp_impl.hpp:163-168)
@@ -776,33 +801,37 @@ void prepare_loop(ngicp* h, LoopCtx& c) {
   DeviceCloud& S = *h->src.dev;
   DeviceCloud& T = *h->tgt.dev;
   const size_t n = S.n;
-  for (int i = 0; i < 2; ++i) {
-    h->tpt[i].ensure(n * sizeof(float4));
-    h->mahal[i].ensure(n * 6 * sizeof(double));
-  }
   const int nblocks = std::max(1, (S.n_batches + 3) / 4);  // one block per group of four batches
-  h->partials.ensure((size_t)kNumSlots * nblocks * sizeof(double));
-  h->grp_order.ensure((size_t)nblocks * sizeof(int));
-  h->grp_order_alt.ensure((size_t)nblocks * sizeof(int));
-  h->grp_cost.ensure((size_t)nblocks * sizeof(int));
-  {
-    // (the persistent kernel's ring of per-pass views continues behind the state: one 256-byte entry per possible pass)
-    const long ring = (long)std::max(1, h->p.max_iter) * std::max(1, h->p.lm_max_iter) + 2;
-    h->state.ensure(sizeof(LmState) + (ring <= kMaxPersistPasses ? (size_t)ring * kViewWords * sizeof(int) : 0));
-  }
   const int max_rows = std::max(1, h->p.max_iter) * std::max(1, h->p.lm_max_iter) + 1;
-  if (h->trace.ensure_grew((size_t)max_rows * kTraceCols * sizeof(double))) h->trace_rows_dev = 0;  // an unfetched trace went with the old buffer
-  h->sums.ensure(kPartialStride * sizeof(double));
+  if (own_buffers) {
+    for (int i = 0; i < 2; ++i) {
+      h->tpt[i].ensure(n * sizeof(float4));
+      h->mahal[i].ensure(n * 6 * sizeof(double));
+    }
+    h->partials.ensure((size_t)kNumSlots * nblocks * sizeof(double));
+    h->grp_order.ensure((size_t)nblocks * sizeof(int));
+    h->grp_order_alt.ensure((size_t)nblocks * sizeof(int));
+    h->grp_cost.ensure((size_t)nblocks * sizeof(int));
+    {
+      // (the persistent kernel's ring of per-pass views continues behind the state: one 256-byte entry per possible pass)
+      const long ring = (long)std::max(1, h->p.max_iter) * std::max(1, h->p.lm_max_iter) + 2;
+      h->state.ensure(sizeof(LmState) + (ring <= kMaxPersistPasses ? (size_t)ring * kViewWords * sizeof(int) : 0));
+    }
+    if (h->trace.ensure_grew((size_t)max_rows * kTraceCols * sizeof(double))) h->trace_rows_dev = 0;  // an unfetched trace went with the old buffer
+    h->sums.ensure(kPartialStride * sizeof(double));
+    h->batch_far.ensure((size_t)S.n_batches + 16);
+    h->gen_lines.ensure((size_t)kGenLines * kGenStride * sizeof(int));
+  }
 
   PassArgs& a = c.pa;
   a.qpts = S.qpts.as<float4>();
   a.batches = S.batches.as<int2>();
   a.batch_boxes = S.batch_boxes.as<float>();
-  int* const order_buf[2] = {h->grp_order.as<int>(), h->grp_order_alt.as<int>()};
-  int* const ctl = h->order_flag.as<int>();  // {order flag 0, ticket, gen, order flag 1}
-  int* const order_flag[2] = {ctl, ctl + 3};
+  int* const order_buf[2] = {own_buffers ? h->grp_order.as<int>() : nullptr, own_buffers ? h->grp_order_alt.as<int>() : nullptr};
+  int* const ctl = own_buffers ? h->order_flag.as<int>() : nullptr;  // {order flag 0, ticket, gen, order flag 1}
+  int* const order_flag[2] = {ctl, ctl ? ctl + 3 : nullptr};
   a.grp_order = order_buf[h->order_sel];
-  a.grp_cost = h->grp_cost.as<int>();
+  a.grp_cost = own_buffers ? h->grp_cost.as<int>() : nullptr;
   a.n_batches = S.n_batches;
   a.cov_src = covs_for(h, h->src_covs, h->src.dev);
   a.n_src = (int)n;
@@ -814,8 +843,8 @@ void prepare_loop(ngicp* h, LoopCtx& c) {
   a.cov_tgt = covs_for(h, h->tgt_covs, h->tgt.dev);
   a.grid = T.grid;
   for (int i = 0; i < 2; ++i) {
-    a.tpt[i] = h->tpt[i].as<float4>();
-    a.mahal[i] = h->mahal[i].as<double>();
+    a.tpt[i] = own_buffers ? h->tpt[i].as<float4>() : nullptr;
+    a.mahal[i] = own_buffers ? h->mahal[i].as<double>() : nullptr;
   }
   a.gate_sq = h->p.max_corr_dist * h->p.max_corr_dist;
   {
@@ -823,10 +852,9 @@ void prepare_loop(ngicp* h, LoopCtx& c) {
     if ((double)f < a.gate_sq) f = std::nextafter(f, std::numeric_limits<float>::infinity());
     a.gate_sq_f = f;
   }
-  h->batch_far.ensure((size_t)S.n_batches + 16);
-  a.batch_far = h->batch_far.as<unsigned char>();
-  a.st = h->state.as<LmState>();
-  a.partials = h->partials.as<double>();
+  a.batch_far = own_buffers ? h->batch_far.as<unsigned char>() : nullptr;
+  a.st = own_buffers ? h->state.as<LmState>() : nullptr;
+  a.partials = own_buffers ? h->partials.as<double>() : nullptr;
   a.mode = 3;
   a.dbg_stamps = nullptr;
   a.dbg_qstats = nullptr;
@@ -837,9 +865,8 @@ void prepare_loop(ngicp* h, LoopCtx& c) {
   a.persist = 0;
   a.first_pass = 0;
   a.max_passes = 0;
-  a.ticket = ctl + 1;
-  h->gen_lines.ensure((size_t)kGenLines * kGenStride * sizeof(int));
-  a.gen = h->gen_lines.as<int>();
+  a.ticket = ctl ? ctl + 1 : nullptr;
+  a.gen = own_buffers ? h->gen_lines.as<int>() : nullptr;
   {
     // rings worth staging: enough to cover the distance gate (the search never looks farther), at most kStageMaxGrow
     int need = kStageMaxGrow;
@@ -858,8 +885,8 @@ void prepare_loop(ngicp* h, LoopCtx& c) {
   s.partials = a.partials;
   s.nblocks = nblocks;
   s.grp_order = order_buf[h->order_sel];
-  s.grp_cost = h->grp_cost.as<int>();
-  s.trace = h->trace.as<double>();
+  s.grp_cost = a.grp_cost;
+  s.trace = own_buffers ? h->trace.as<double>() : nullptr;
   s.max_trace_rows = max_rows;
   s.mode = 0;
   s.sums_out = nullptr;
@@ -877,6 +904,7 @@ void prepare_loop(ngicp* h, LoopCtx& c) {
   a.cluster_ticket = nullptr;
   a.done_flag = nullptr;
   c.nblocks = nblocks;
+  if (!own_buffers) return;
   h->stats.lanes_per_query = 2;
   h->stats.voxel_size = T.grid.h;
   h->stats.grid_dims[0] = T.grid.nx;
@@ -1344,6 +1372,185 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
   s.align_ms = now_ms() - t_begin;
 }
 
+// ------------------------------------------------------------------------------------------
+// Batched registration: several initial guesses on one source / target pair
+// ------------------------------------------------------------------------------------------
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+void ensure_batch_pinned(ngicp* h) {
+  BatchWs& w = h->batch;
+  if (!w.pin_recs) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w.pin_recs), (size_t)kBatchMaxLanes * (sizeof(LmState) + sizeof(PassArgs) + sizeof(SolveArgs)), hipHostMallocDefault));
+  if (!w.pin_progress) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w.pin_progress), (size_t)kBatchMaxLanes * BatchWs::kProgressStride * sizeof(int), hipHostMallocDefault));
+  if (!w.pin_final) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w.pin_final), (size_t)kBatchMaxLanes * sizeof(LmHot), hipHostMallocDefault));
+}
+
+// The batch always takes the default route: walks in global memory (k_gicp_pass_batch), a solver launch of its own (k_lm_solve_batch).
+// NGICP_PERSIST, NGICP_HEAD, NGICP_FUSED, NGICP_QUEUE, NGICP_PASS_IMPL and NGICP_ORDER do not apply to it.
+void do_align_batch(ngicp* h, int B, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* hessians) {
+  BatchWs& w = h->batch;
+  const int max_rows = std::max(1, h->p.max_iter) * std::max(1, h->p.lm_max_iter) + 1;
+  // (slots, lazy covariances, the shared fields - and none of the handle's single-alignment buffers: what the getters of the last
+  // ngicp_align read is neither resized nor written)
+  LoopCtx c;
+  prepare_loop(h, c, false);
+  c.pa.mode = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? 2 : 3;
+  if (h->prev_staged_fraction < 0.0 || h->prev_staged_fraction >= 0.12) c.pa.mode |= 32;  // (the decision an align on this handle would take now: do_align)
+
+  const size_t n = h->src.dev->n;
+  const int nblocks = c.nblocks, n_batches = c.pa.n_batches;
+  const size_t tpt_stride = round_up(n * sizeof(float4), 256), mahal_stride = round_up(n * 6 * sizeof(double), 256);
+  const size_t part_stride = (size_t)nblocks * kNumSlots * sizeof(double);
+  const size_t ord_stride = round_up((size_t)nblocks * sizeof(int), 256), far_stride = round_up((size_t)n_batches + 16, 256);
+  const size_t trace_stride = (size_t)max_rows * kTraceCols;
+  const size_t off_pass = (size_t)B * sizeof(LmState), off_solve = off_pass + round_up((size_t)B * sizeof(PassArgs), 16);
+  const size_t recs_bytes = off_solve + (size_t)B * sizeof(SolveArgs);
+  w.lanes = 0;  // (the traces of the previous call go with the buffers)
+  w.trace_rows.clear();
+  // (a call that fails half way - an allocation, say - must not leave a description of launch orders that a replaced buffer no longer holds)
+  const bool order_described = w.order_src == h->src.dev.get() && w.order_groups == nblocks && w.order_lanes >= B;
+  const int lanes_before = w.order_lanes;
+  w.order_src = nullptr;
+  w.order_lanes = 0;
+  ensure_batch_pinned(h);
+  w.recs.ensure(recs_bytes);
+  w.tpt.ensure((size_t)B * 2 * tpt_stride);
+  w.mahal.ensure((size_t)B * 2 * mahal_stride);
+  w.partials.ensure((size_t)B * part_stride);
+  bool order_kept = order_described;
+  if (w.order.ensure_grew((size_t)B * ord_stride)) order_kept = false;
+  w.cost.ensure((size_t)B * ord_stride);
+  if (w.flags.ensure_grew((size_t)kBatchMaxLanes * 4 * sizeof(int))) order_kept = false;
+  if (w.far.ensure_grew((size_t)B * far_stride)) HIP_TRY(hipMemsetAsync(w.far.p, 0, w.far.cap, h->stream));
+  w.trace.ensure((size_t)B * trace_stride * sizeof(double));
+  // a lane's launch order of the previous call is still a good guess when the source index is the same one (do_align)
+  if (!order_kept) HIP_TRY(hipMemsetAsync(w.flags.p, 0, (size_t)kBatchMaxLanes * 4 * sizeof(int), h->stream));
+
+  // ---- the lane records: state image, pass arguments, solver arguments ----
+  LmState* const st_host = reinterpret_cast<LmState*>(w.pin_recs);
+  PassArgs* const pa_host = reinterpret_cast<PassArgs*>(w.pin_recs + off_pass);
+  SolveArgs* const sa_host = reinterpret_cast<SolveArgs*>(w.pin_recs + off_solve);
+  unsigned char* const recs_dev = w.recs.as<unsigned char>();
+  for (int g = 0; g < B; ++g) {
+    init_state_from_pose(st_host[g], pose_from_colmajor_f(guesses + (size_t)g * 16));
+    if (h->p.max_iter <= 0) st_host[g].hot.done = 1;
+    PassArgs pa = c.pa;
+    pa.st = reinterpret_cast<LmState*>(recs_dev) + g;
+    for (int i = 0; i < 2; ++i) {
+      pa.tpt[i] = reinterpret_cast<float4*>(w.tpt.as<unsigned char>() + ((size_t)g * 2 + i) * tpt_stride);
+      pa.mahal[i] = reinterpret_cast<double*>(w.mahal.as<unsigned char>() + ((size_t)g * 2 + i) * mahal_stride);
+    }
+    pa.partials = reinterpret_cast<double*>(w.partials.as<unsigned char>() + (size_t)g * part_stride);
+    pa.grp_order = reinterpret_cast<int*>(w.order.as<unsigned char>() + (size_t)g * ord_stride);
+    pa.grp_cost = reinterpret_cast<int*>(w.cost.as<unsigned char>() + (size_t)g * ord_stride);
+    pa.batch_far = w.far.as<unsigned char>() + (size_t)g * far_stride;
+    pa.order_valid = w.flags.as<int>() + (size_t)g * 4;
+    pa.ticket = w.flags.as<int>() + (size_t)g * 4 + 1;
+    pa.t_first = nullptr;
+    SolveArgs sa = c.sa;
+    sa.st = pa.st;
+    sa.partials = pa.partials;
+    sa.grp_order = const_cast<int*>(pa.grp_order);
+    sa.grp_cost = pa.grp_cost;
+    sa.trace = w.trace.as<double>() + (size_t)g * trace_stride;
+    sa.progress_host = w.pin_progress + (size_t)g * BatchWs::kProgressStride;
+    sa.final_host = w.pin_final + g;
+    sa.order_valid = const_cast<int*>(pa.order_valid);
+    sa.t_first = nullptr;
+    pa.sa = sa;
+    pa_host[g] = pa;
+    sa_host[g] = sa;
+    *sa.progress_host = 0;
+  }
+  const long max_passes = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? (long)h->p.max_iter : (long)h->p.max_iter * std::max(1, h->p.lm_max_iter) + 1;
+  std::vector<LmHot> result((size_t)B);
+  if (h->p.max_iter <= 0) {
+    for (int g = 0; g < B; ++g) result[(size_t)g] = st_host[g].hot;  // every lane returns its guess, as ngicp_align does; nothing is launched
+  } else {
+    HIP_TRY(hipMemcpyAsync(recs_dev, w.pin_recs, recs_bytes, hipMemcpyHostToDevice, h->stream));  // ONE upload
+    BatchLaunch bl;
+    bl.pass = reinterpret_cast<const PassArgs*>(recs_dev + off_pass);
+    bl.solve = reinterpret_cast<const SolveArgs*>(recs_dev + off_solve);
+    for (int i = 0; i < kBatchMaxLanes; ++i) bl.lane[i] = 0;
+    // The feeding discipline of do_align: (pass, solve) pairs kept `depth` ahead of the slowest live lane's progress word.  A lane that
+    // reports done leaves the list; its blocks in the launches already enqueued return at their head.
+    const int depth = h->chunk_pairs;
+    const double t_loop = now_ms();
+    unsigned long spins = 0;
+    bool idle_seen = false;
+    // Every so many polls the stream is asked for its status: an asynchronous error comes out as its HIP error, not as the timeout.
+    // true: the stream has nothing left to run.
+    auto look_at_stream = [&]() -> bool {
+      const hipError_t q = hipStreamQuery(h->stream);
+      if (q == hipErrorNotReady) {
+        (void)hipGetLastError();
+      } else if (q != hipSuccess) {
+        throw HipError{q, "hipStreamQuery(h->stream)", __FILE__, __LINE__};
+      }
+      if (now_ms() - t_loop > 30000.0) throw ArgError{NGICP_ERR_HIP, "the batched registration loop did not finish within 30 s"};
+      return q == hipSuccess;
+    };
+    auto relax = [&]() {
+      // (idle at the last look: every launch enqueued had run, so the words the caller has just read again were final)
+      if (idle_seen) throw ArgError{NGICP_ERR_HIP, "the batched registration loop: the stream is idle but a lane has not reported"};
+      if ((++spins & (h->host_wait ? 0xff : 0xfff)) == 0 && look_at_stream()) {
+        idle_seen = true;
+        return;
+      }
+      if (h->host_wait) sched_yield(); else __builtin_ia32_pause();
+    };
+    long launched = 0;
+    int n_live = B;
+    std::vector<int> live((size_t)B);
+    for (int g = 0; g < B; ++g) live[(size_t)g] = g;
+    for (;;) {
+      long min_prog = std::numeric_limits<long>::max();
+      int keep_n = 0;
+      for (int i = 0; i < n_live; ++i) {
+        const int g = live[(size_t)i];
+        const int prog = __atomic_load_n(w.pin_progress + (size_t)g * BatchWs::kProgressStride, __ATOMIC_ACQUIRE);
+        if (prog & kProgressDone) {
+          result[(size_t)g] = w.pin_final[g];  // (stored before the flag: lm_solve_body)
+          continue;
+        }
+        live[(size_t)keep_n++] = g;
+        min_prog = std::min(min_prog, (long)(prog & kProgressMask));
+      }
+      n_live = keep_n;
+      if (n_live == 0) break;
+      if (launched >= max_passes || launched - min_prog >= depth) {  // enough in flight (or nothing left to launch: the last possible pass sets done)
+        relax();
+        continue;
+      }
+      idle_seen = false;
+      for (int i = 0; i < n_live; ++i) bl.lane[i] = live[(size_t)i];
+      const bool four = (long)nblocks * n_live > 2L * h->pass_slots;  // launch_pass's rule on the whole grid
+      if (four)
+        hipLaunchKernelGGL((k_gicp_pass_batch<2, 4>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, bl);
+      else
+        hipLaunchKernelGGL((k_gicp_pass_batch<2, 3>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, bl);
+      hipLaunchKernelGGL(k_lm_solve_batch, dim3((unsigned)n_live), dim3(kSolveThreads), 0, h->stream, bl);
+      ++launched;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  for (int g = 0; g < B; ++g) {
+    const LmHot& r = result[(size_t)g];
+    pose_to_colmajor_f(r.x0, T_out + (size_t)g * 16);
+    if (converged) converged[g] = r.converged;
+    if (nr_iterations) nr_iterations[g] = r.nr_iterations;
+    if (hessians)
+      for (int rr = 0; rr < 6; ++rr)
+        for (int cc = 0; cc < 6; ++cc) hessians[(size_t)g * 36 + cc * 6 + rr] = r.final_H[rr * 6 + cc];
+    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");  // impl/lsq_registration_impl.hpp:106
+    w.trace_rows.push_back((size_t)r.n_trace);
+  }
+  w.lanes = B;
+  w.trace_stride = trace_stride;
+  w.order_src = h->src.dev.get();
+  w.order_groups = nblocks;
+  w.order_lanes = std::max(order_kept ? lanes_before : 0, B);
+}
+
 template <class F>
 int guarded(ngicp* h, F&& f) {
   if (!h) return NGICP_ERR_ARG;
@@ -1561,6 +1768,9 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->pin_ticks) (void)hipHostFree(h->pin_ticks);
   if (h->h_progress) (void)hipHostFree(h->h_progress);
   if (h->h_shard_done) (void)hipHostFree(h->h_shard_done);
+  if (h->batch.pin_recs) (void)hipHostFree(h->batch.pin_recs);
+  if (h->batch.pin_progress) (void)hipHostFree(h->batch.pin_progress);
+  if (h->batch.pin_final) (void)hipHostFree(h->batch.pin_final);
   for (auto& e : h->ev_shard)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_a) (void)hipEventDestroy(h->ev_a);
@@ -1742,6 +1952,65 @@ int ngicp_align(ngicp_t* h, const float guess[16], float T_out[16], int* converg
     if (final_hessian) std::memcpy(final_hessian, h->final_hessian, sizeof(h->final_hessian));
   }
   return rc;
+}
+
+int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
+  return guarded(h, [&] {
+    if (n_guesses == 0) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: n_guesses is 0"};
+    if (n_guesses > (size_t)NGICP_BATCH_MAX_LANES) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: more than NGICP_BATCH_MAX_LANES (64) guesses in one call"};
+    if (!guesses) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: null guesses"};
+    if (!T_out || !converged || !nr_iterations) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: null output"};
+    do_align_batch(h, (int)n_guesses, guesses, T_out, converged, nr_iterations, final_hessians);
+  });
+}
+
+int ngicp_batch_get_lm_trace(ngicp_t* h, size_t lane, double* rows, size_t max_rows, size_t* n_rows) {
+  return guarded(h, [&] {
+    BatchWs& w = h->batch;
+    if (lane >= (size_t)w.lanes) throw ArgError{NGICP_ERR_ARG, "ngicp_batch_get_lm_trace: no such lane in the last ngicp_align_batch"};
+    const size_t n = w.trace_rows[lane];
+    if (n_rows) *n_rows = n;
+    const size_t take = std::min(n, max_rows);
+    if (rows && take) {
+      HIP_TRY(hipMemcpyAsync(rows, w.trace.as<double>() + lane * w.trace_stride, take * kTraceCols * sizeof(double), hipMemcpyDeviceToHost, h->stream));  // (stream order)
+      HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+  });
+}
+
+int ngicp_fitness_score_batch(ngicp_t* h, size_t n, const float* T_colmajor, double max_range, double* scores, size_t* n_inliers) {
+  return guarded(h, [&] {
+    if (n == 0) throw ArgError{NGICP_ERR_ARG, "ngicp_fitness_score_batch: n is 0"};
+    if (!T_colmajor) throw ArgError{NGICP_ERR_ARG, "ngicp_fitness_score_batch: null transforms"};
+    if (!scores) throw ArgError{NGICP_ERR_ARG, "null output"};
+    DeviceCloud& S = query_cloud(h, 0);
+    DeviceCloud& T = query_cloud(h, 1);
+    BatchWs& w = h->batch;
+    const int np = (int)S.n;
+    const int nb = (np + kKnnPairs - 1) / kKnnPairs;
+    std::vector<double2> r(n);
+    // (any number of transforms: the lane dimension of a launch is cut at the grid's limit)
+    constexpr size_t kChunk = 4096;
+    const size_t chunk = std::min(n, kChunk);
+    w.fit_T.ensure(chunk * 16 * sizeof(float));
+    w.fit_part.ensure(chunk * (size_t)nb * sizeof(double2));
+    w.fit_out.ensure(chunk * sizeof(double2));
+    for (size_t at = 0; at < n; at += chunk) {
+      const size_t m = std::min(chunk, n - at);
+      HIP_TRY(hipMemcpyAsync(w.fit_T.p, T_colmajor + at * 16, m * 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(k_fitness_batch, dim3((unsigned)nb, (unsigned)m), dim3(kKnnBlock), 0, h->stream, S.pts(), np, w.fit_T.as<float>(), T.pts(), T.cells(), T.grid, max_range,
+                         w.fit_part.as<double2>());
+      hipLaunchKernelGGL(k_fitness_final_batch, dim3((unsigned)m), dim3(kFitnessFinalBlock), 0, h->stream, w.fit_part.as<double2>(), nb, w.fit_out.as<double2>());
+      HIP_TRY(hipMemcpyAsync(r.data() + at, w.fit_out.p, m * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    HIP_TRY(hipGetLastError());
+    for (size_t i = 0; i < n; ++i) {
+      const size_t cnt = (size_t)r[i].y;
+      scores[i] = cnt ? r[i].x / r[i].y : std::numeric_limits<double>::max();
+      if (n_inliers) n_inliers[i] = cnt;
+    }
+  });
 }
 
 int ngicp_linearize(ngicp_t* h, const double T[16], double H[36], double b[6], double* err) {

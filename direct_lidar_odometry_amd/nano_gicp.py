@@ -76,7 +76,10 @@ EXPORTS = [
     "ngicp_preprocess_scan", "ngicp_set_source_preprocessed", "ngicp_map_add", "ngicp_map_voxel_filter", "ngicp_map_size", "ngicp_map_get",
     "ngicp_map_clear", "ngicp_math_selftest", "ngicp_set_host_wait", "ngicp_covs_shard_begin", "ngicp_covs_shard_compute", "ngicp_covs_shard_commit",
     "ngicp_knn_search", "ngicp_radius_search", "ngicp_radius_fetch", "ngicp_fitness_score",
+    "ngicp_align_batch", "ngicp_batch_get_lm_trace", "ngicp_fitness_score_batch",
 ]
+
+BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
 
 _lib = None
 
@@ -128,6 +131,9 @@ def load_library() -> C.CDLL:
     L.ngicp_radius_fetch.argtypes = [vp, c_i32p, c_f32p, C.c_size_t]
     L.ngicp_fitness_score.argtypes = [vp, c_f32p, C.c_double, c_f64p, C.POINTER(C.c_size_t)]
     L.ngicp_get_lm_trace.argtypes = [vp, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ngicp_align_batch.argtypes = [vp, C.c_size_t, c_f32p, c_f32p, c_i32p, c_i32p, c_f64p]
+    L.ngicp_batch_get_lm_trace.argtypes = [vp, C.c_size_t, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ngicp_fitness_score_batch.argtypes = [vp, C.c_size_t, c_f32p, C.c_double, c_f64p, C.POINTER(C.c_size_t)]
     L.ngicp_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ngicp_set_profiling.argtypes = [vp, C.c_int]
     L.ngicp_sharded_begin.argtypes = [vp, c_f32p]
@@ -344,6 +350,38 @@ class NanoGICP:
                 print("--- LM optimization ---\n%5s %15s %15s %15s %15s %15s %5s" % ("i", "y0", "yi", "rho", "lambda", "|delta|", "dec"))
             print("%5d %15g %15g %15g %15g %15g %5c" % (int(trial), y0, yi, rho, lam, dn, "x" if rho > 0.0 else " "))
 
+    def alignBatch(self, guesses):
+        """Several initial guesses on the current source / target pair in the same launches (ngicp_align_batch; no counterpart in
+        the reference).  guesses: (B, 4, 4).  -> (T (B, 4, 4) float32, converged (B,) bool, iterations (B,) int32, H (B, 6, 6) float64);
+        lane g is bit for bit what align(guesses[g]) gives.  Leaves final_transformation_ and the other results of align() alone."""
+        g = np.asarray(guesses)
+        if g.ndim != 3 or g.shape[1:] != (4, 4):
+            raise NgicpError(-2, "alignBatch: guesses must be (B, 4, 4)")
+        B = g.shape[0]
+        gc = np.ascontiguousarray(np.transpose(g, (0, 2, 1)), dtype=np.float32).reshape(B, 16)  # column-major per lane
+        T = np.empty((B, 16), dtype=np.float32)
+        H = np.empty((B, 36), dtype=np.float64)
+        conv = np.zeros(B, dtype=np.int32)
+        nit = np.zeros(B, dtype=np.int32)
+        self._ck(self._L.ngicp_align_batch(self._h, B, _p(gc, c_f32p) if B else None, _p(T, c_f32p) if B else None,
+                                           _p(conv, c_i32p) if B else None, _p(nit, c_i32p) if B else None, _p(H, c_f64p) if B else None))
+        return (np.ascontiguousarray(np.transpose(T.reshape(B, 4, 4), (0, 2, 1))), conv.astype(bool), nit,
+                np.ascontiguousarray(np.transpose(H.reshape(B, 6, 6), (0, 2, 1))))
+
+    def fitnessBatch(self, Ts, max_range: float = sys.float_info.max):
+        """fitness() for every transform of Ts (B, 4, 4) in one launch -> (scores (B,) float64, n_inliers (B,) int64), bit for bit
+        what B calls of fitness(max_range, T) give."""
+        t = np.asarray(Ts)
+        if t.ndim != 3 or t.shape[1:] != (4, 4):
+            raise NgicpError(-2, "fitnessBatch: Ts must be (B, 4, 4)")
+        B = t.shape[0]
+        tc = np.ascontiguousarray(np.transpose(t, (0, 2, 1)), dtype=np.float32).reshape(B, 16)
+        scores = np.empty(B, dtype=np.float64)
+        cnt = np.zeros(B, dtype=np.uint64)
+        self._ck(self._L.ngicp_fitness_score_batch(self._h, B, _p(tc, c_f32p) if B else None, float(max_range), _p(scores, c_f64p) if B else None,
+                                                   cnt.ctypes.data_as(C.POINTER(C.c_size_t))))
+        return scores, cnt.astype(np.int64)
+
     def getFinalTransformation(self): return self.final_transformation_
     def hasConverged(self) -> bool: return self.converged_
     def getFinalHessian(self): return self.final_hessian_
@@ -407,8 +445,15 @@ class NanoGICP:
         self._ck(self._L.ngicp_radius_fetch(self._h, _p(idx, c_i32p), _p(d2, c_f32p), total.value))
         return offsets.astype(np.int64), idx, d2
 
-    def lm_trace(self) -> np.ndarray:
+    def lm_trace(self, lane=None) -> np.ndarray:
+        """LM trace of the last align() (lane None), or of lane `lane` of the last alignBatch()."""
         n = C.c_size_t(0)
+        if lane is not None:
+            self._ck(self._L.ngicp_batch_get_lm_trace(self._h, int(lane), None, 0, C.byref(n)))
+            out = np.empty((n.value, 8))
+            if n.value:
+                self._ck(self._L.ngicp_batch_get_lm_trace(self._h, int(lane), _p(out, c_f64p), n.value, C.byref(n)))
+            return out
         self._ck(self._L.ngicp_get_lm_trace(self._h, None, 0, C.byref(n)))
         out = np.empty((n.value, 8))
         if n.value:

@@ -344,6 +344,46 @@ class NanoGICP {
   }
   ngicp_t* handle() { return h_; }
 
+  // ---- more than one candidate pose (no counterpart in the reference; include/ngicp.h "more than one initial guess") ----
+  // alignBatch: every guess aligned on the current source / target pair in the same kernel launches; result g is bit for bit what
+  // alignPoseOnly(guesses[g]) leaves in the getters.  The getters themselves (getFinalTransformation, hasConverged, ...) keep the
+  // results of the last align().  getFitnessScores: getFitnessScore for each transform, one launch.  Recipe: INTEGRATION.md.
+  struct BatchResult {
+    Matrix4 transformation;
+    bool converged = false;
+    int nr_iterations = 0;
+    types::Matrix6d hessian;
+  };
+  std::vector<BatchResult> alignBatch(const std::vector<Matrix4>& guesses) {
+    std::vector<BatchResult> out;
+    if (!h_ || !input_ || !(target_ || device_target_) || guesses.empty()) return out;
+    const size_t n = guesses.size();
+    std::vector<float> g(n * 16), T(n * 16);
+    std::vector<int> conv(n), nit(n);
+    std::vector<double> H(n * 36);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&g[i * 16], guesses[i].data(), 16 * sizeof(float));
+    if (ngicp_align_batch(h_, n, g.data(), T.data(), conv.data(), nit.data(), H.data()) != NGICP_OK) {
+      std::fprintf(stderr, "[NanoGICP] alignBatch(): %s\n", ngicp_last_error(h_));
+      return out;
+    }
+    out.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      std::memcpy(out[i].transformation.data(), &T[i * 16], 16 * sizeof(float));
+      out[i].converged = conv[i] != 0;
+      out[i].nr_iterations = nit[i];
+      std::memcpy(out[i].hessian.data(), &H[i * 36], 36 * sizeof(double));
+    }
+    return out;
+  }
+  std::vector<double> getFitnessScores(const std::vector<Matrix4>& transforms, double max_range = std::numeric_limits<double>::max()) {
+    std::vector<double> scores(transforms.size(), std::numeric_limits<double>::max());
+    if (!h_ || transforms.empty()) return scores;
+    std::vector<float> T(transforms.size() * 16);
+    for (size_t i = 0; i < transforms.size(); ++i) std::memcpy(&T[i * 16], transforms[i].data(), 16 * sizeof(float));
+    check(ngicp_fitness_score_batch(h_, transforms.size(), T.data(), max_range, scores.data(), nullptr), "getFitnessScores");
+    return scores;
+  }
+
   // ---- extensions with no reference counterpart (include/ngicp.h "keyframe store", "rigid transform"): the keyframes and the
   //      submap stay on the GPU.  In DLO they replace odom.cc:1174 (`keyframe_normals.push_back(gicp_s2s.getSourceCovariances())`)
   //      and odom.cc:830-833 (`setInputTarget(submap_cloud); setTargetCovariances(submap_normals)`); see INTEGRATION.md ----

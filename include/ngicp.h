@@ -168,6 +168,31 @@ int ngicp_fitness_score(ngicp_t* h, const float T_colmajor_or_null[16], double m
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
 
+/* --- more than one initial guess on the same source / target pair (no counterpart in the reference) ------------------------------
+ * ngicp_align_batch: n_guesses alignments on this handle at once.  They share the source, the target, both indices, both covariance
+ * sets and every parameter; each has its own initial guess.  One kernel launch per pass serves every guess still running, one solver
+ * launch steps every optimiser (csrc/ngicp_batch.h).  guesses and T_out: n_guesses x 16 floats, column-major; converged and
+ * nr_iterations: n_guesses ints; final_hessians_or_null: n_guesses x 36 doubles, column-major.  Guess g's outputs are bit-identical to
+ * what ngicp_align(h, guesses + 16 g, ...) returns on the same handle state.  The call changes nothing an existing getter returns -
+ * final transformation, convergence flag, correspondences, LM trace, Hessian and ngicp_get_stats stay those of the last ngicp_align -
+ * except that it computes missing covariances, exactly as ngicp_align would.  max_iter <= 0: every guess comes back as it is.
+ * Errors: as ngicp_align for a missing source or target; NGICP_ERR_ARG for n_guesses == 0, n_guesses > NGICP_BATCH_MAX_LANES, null
+ * guesses, T_out, converged or nr_iterations.  The working set is ~128 bytes x source points per guess, kept and reused by the handle;
+ * an allocation that fails is NGICP_ERR_HIP and leaves the handle usable.
+ * When it pays (MI355X): for two or more guesses at every size measured, 10k -> 10k to 250k -> 2M points - eight guesses
+ * take 1.2x the time of one at 10k points, 3.4x at 100k -> 500k, 4.2x at 250k -> 2M.  No size was found from which a loop of
+ * ngicp_align calls serves the caller better; a single guess is 4-5 % faster through ngicp_align. */
+#define NGICP_BATCH_MAX_LANES 64
+int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses_n16_colmajor, float* T_out_n16_colmajor, int* converged_n, int* nr_iterations_n,
+                      double* final_hessians_n36_colmajor_or_null);
+/* LM trace of guess `lane` of the last ngicp_align_batch: rows as ngicp_get_lm_trace.  Valid until the next ngicp_align_batch or a change
+ * of the source or target. */
+int ngicp_batch_get_lm_trace(ngicp_t* h, size_t lane, double* rows8_or_null, size_t max_rows, size_t* n_rows);
+/* ngicp_fitness_score for n transforms in one launch (n x 16 floats, column-major): scores[i] and n_inliers[i] are bit-identical to
+ * ngicp_fitness_score(h, T + 16 i, max_range, ...).  The recipe for several candidate poses: align the batch, score the results, take
+ * the lowest score. */
+int ngicp_fitness_score_batch(ngicp_t* h, size_t n, const float* T_n16_colmajor, double max_range, double* scores_n, size_t* n_inliers_n_or_null);
+
 /* The small FP64 routines of the engine evaluated on the device, one problem per thread (unit-test hook): which = 0 so3_exp
  * (gicp/so3.hpp:99-118 followed by Quaternion::toRotationMatrix; in: 3 doubles, out: R row-major 9), 1 the 6x6 LDLT solve that
  * stands in for Eigen::LDLT (impl/lsq_registration_impl.hpp:147-148,172-173; in: A row-major 36 + rhs 6, out: 6), 2 the
