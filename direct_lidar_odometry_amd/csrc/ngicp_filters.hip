@@ -11,7 +11,18 @@
 //               min_b / max_b from the bounding box of the input, div_b = max_b - min_b + 1; voxel index
 //               (i - min_b.x) + (j - min_b.y) * div.x + (k - min_b.z) * div.x * div.y; one output point per occupied voxel,
 //               in ascending voxel index, = the centroid of ALL fields (x, y, z, intensity: downsample_all_data), float sums
-//               divided by the count; if div.x * div.y * div.z overflows int32 PCL warns and returns the input unfiltered.
+//               divided by the count.
+//               Overflow rule (restated from memory of PCL like the rest; the engine, the oracle and tests/_filter_model.py state
+//               it alike).  PCL warns ("Leaf size is too small for the input dataset") and returns its input when the voxel
+//               indices would not fit an int.  Three tests, in this order, and nothing is converted to int before the first two
+//               have passed (out of range that conversion is undefined in C++, INT_MIN on x86, saturating on the GPU):
+//                 (1) PCL's extent test, in float and int64: inv_leaf must be finite, and per axis ext = (max - min) * inv_leaf
+//                     must be finite and below 2^31; d = int64(ext) + 1; overflow when dx * dy * dz > INT_MAX;
+//                 (2) floor(min * inv_leaf) and floor(max * inv_leaf) must fit an int32 on every axis (a small cloud far from
+//                     the origin; PCL is undefined there, returning the input is the conservative reading);
+//                 (3) div.x * div.y * div.z > INT_MAX, as before (it can differ from (1) by a voxel per axis).
+//               "Its input" is the VoxelGrid stage's input, i.e. what removeNaN / CropBox left: with remove_nan = 0 the
+//               non-finite rows are still in it (a map that holds NaN rows stays entirely unchanged).
 //               PCL adds the points of a voxel in the order std::sort leaves them (unspecified among equal indices); here
 //               they are added in input order (a stable radix sort), so sums may differ from PCL's in the last bits.
 // Built with -ffp-contract=off like the rest (no FMA).  Every kernel is written out below (round 2 called hipCUB for the sort), and
@@ -61,8 +72,8 @@ __global__ void __launch_bounds__(256) k_filter_flags(const float4* __restrict__
   const float4 p = pts[i];
   bool k = true;
   if (drop_nonfinite && !(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) k = false;
-  // pcl::CropBox, negative: a point INSIDE [min, max] (inclusive) is removed
-  if (k && crop > 0.f && !(p.x < -crop || p.y < -crop || p.z < -crop || p.x > crop || p.y > crop || p.z > crop)) k = false;
+  // pcl::CropBox, negative: a point INSIDE [min, max] (inclusive) is removed (a NaN coordinate is not inside: with remove_nan = 0 it stays)
+  if (k && crop > 0.f && p.x >= -crop && p.x <= crop && p.y >= -crop && p.y <= crop && p.z >= -crop && p.z <= crop) k = false;
   keep[i] = k ? 1 : 0;
 }
 
@@ -114,7 +125,7 @@ struct Lattice {
 struct FilterState {
   int n_surv;    // points that survive removeNaN / CropBox
   int n_vox;     // occupied voxels
-  int overflow;  // div.x * div.y * div.z does not fit an int: PCL warns and returns its input
+  int overflow;  // the voxel indices would not fit an int (the overflow rule of the header comment): PCL warns and returns its input
   int bits;      // significant bits of a voxel index
   Lattice L;
 };
@@ -151,21 +162,42 @@ __global__ void __launch_bounds__(256) k_lattice(const int* __restrict__ n_surv_
     r.overflow = 0;
     r.bits = 1;
     r.L.inv_leaf = leaf > 0.f ? 1.0f / leaf : 0.f;
-    long long cells = 1;
+    float lo[3], hi[3];
     for (int d = 0; d < 3; ++d) {
-      float lo = lds[0][d], hi = lds[0][3 + d];
+      lo[d] = lds[0][d];
+      hi[d] = lds[0][3 + d];
       for (int w = 1; w < 4; ++w) {
-        lo = fminf(lo, lds[w][d]);
-        hi = fmaxf(hi, lds[w][3 + d]);
+        lo[d] = fminf(lo[d], lds[w][d]);
+        hi[d] = fmaxf(hi[d], lds[w][3 + d]);
       }
-      if (r.n_surv <= 0 || !(leaf > 0.f)) lo = hi = 0.f;
-      r.L.min_b[d] = (int)floorf(lo * r.L.inv_leaf);
-      const int max_b = (int)floorf(hi * r.L.inv_leaf);
-      r.L.div[d] = max_b - r.L.min_b[d] + 1;
-      if (!r.overflow) {
-        cells *= (long long)r.L.div[d];
-        if (cells > 0x7fffffffll) r.overflow = 1;
+      if (r.n_surv <= 0 || !(leaf > 0.f)) lo[d] = hi[d] = 0.f;
+      r.L.min_b[d] = 0;
+      r.L.div[d] = 1;
+    }
+    // the overflow rule (header comment), all in float / int64: nothing is converted to int before both tests have passed
+    const float inv = r.L.inv_leaf;
+    long long cells = 1;
+    if (!isfinite(inv)) r.overflow = 1;
+    for (int d = 0; d < 3 && !r.overflow; ++d) {  // (1) PCL's extent test
+      const float ext = (hi[d] - lo[d]) * inv;
+      if (!isfinite(ext) || !(ext < 2147483648.f)) {
+        r.overflow = 1;
+        break;
       }
+      cells *= (long long)ext + 1;  // (each factor <= 2^31, the running product <= 2^31 - 1 before it: no int64 overflow)
+      if (cells > 0x7fffffffll) r.overflow = 1;
+    }
+    for (int d = 0; d < 3 && !r.overflow; ++d) {  // (2) the lattice coordinates themselves fit an int32
+      const float flo = floorf(lo[d] * inv), fhi = floorf(hi[d] * inv);
+      if (!(flo >= -2147483648.f && fhi < 2147483648.f)) r.overflow = 1;
+    }
+    cells = 1;
+    for (int d = 0; d < 3 && !r.overflow; ++d) {  // (3) the product of div_b, as before
+      r.L.min_b[d] = (int)floorf(lo[d] * inv);
+      const long long dv = (long long)(int)floorf(hi[d] * inv) - (long long)r.L.min_b[d] + 1;
+      cells *= dv;
+      if (cells > 0x7fffffffll) r.overflow = 1;
+      else r.L.div[d] = (int)dv;
     }
     if (!r.overflow)
       while ((1ll << r.bits) < cells && r.bits < 32) ++r.bits;
@@ -379,6 +411,9 @@ static int filter_cloud_impl(hipStream_t s, FilterWorkspace* ws, const float4* i
   if (!voxel || hs.n_surv == 0) return 0;
   if (hs.overflow) {
     std::fprintf(stderr, "[VoxelGrid] Leaf size is too small for the input dataset. Integer indices would overflow.\n");  // PCL: output = input
+    // "its input" is the VoxelGrid stage's input: with remove_nan = 0 the non-finite rows (dropped above for the lattice) belong to it.
+    // Rare path: the flag / scan / compact stage is simply enqueued again without the voxel stage (and without its non-finite drop).
+    if (!remove_nan) return filter_cloud_impl(s, ws, in_dev, n, 0, crop_half, 0.f, out_dev, n_out, err, errlen, false);
     return 0;
   }
   ws->last_bits = hs.bits;

@@ -305,6 +305,12 @@ int ngicp_transform_cloud(ngicp_t* h, const float* xyz, size_t n, size_t stride_
  * xyz at byte 0 and (optionally) a float intensity at intensity_offset_bytes (16 for pcl::PointXYZI; -1: none).  Output:
  * 16 bytes per point {x, y, z, intensity}, written to out_xyzi (capacity in points; may be NULL) and kept on the device.
  * PCL's sources are not under /root/reference: the rules are restated from memory (see csrc/ngicp_filters.hip).
+ * Overflow rule (restated from memory of PCL as well): when the voxel indices would not fit an int, VoxelGrid warns on stderr
+ * and returns ITS input - what removeNaN / CropBox left, so with remove_nan = 0 the non-finite rows are still in it.  That is
+ * the case when (1) 1 / leaf is not finite, or on an axis (max - min) / leaf is not finite or >= 2^31, or the product over the
+ * axes of int64((max - min) / leaf) + 1 exceeds INT_MAX (PCL's extent test, made in float and int64 before anything is
+ * converted to int); (2) floor(min / leaf) or floor(max / leaf) does not fit an int32 on an axis (a small cloud far from the
+ * origin: undefined in PCL, the input is returned here); (3) the product of the lattice's extents div_b exceeds INT_MAX.
  * ngicp_set_source_preprocessed makes the filtered cloud (still on the device) the handle's source: setInputSource
  * (odom.cc:519) without the download / upload pair. */
 int ngicp_preprocess_scan(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, long intensity_offset_bytes, int remove_nan, float crop_half_extent,
@@ -314,7 +320,8 @@ int ngicp_set_source_preprocessed(ngicp_t* h, uint64_t host_identity);
 /* --- map accumulation + voxel filter ---------------------------------- */
 /* dlo::MapNode (src/dlo/map.cc:100-131): `*dlo_map += *keyframe` per keyframe (ngicp_map_add: the keyframe is appended to
  * a device-resident map), and on the publish timer `voxelgrid.filter(*dlo_map)` with a cubic leaf (ngicp_map_voxel_filter:
- * the map is replaced by its voxel centroids, same rules as above); ngicp_map_get downloads it for publishing
+ * the map is replaced by its voxel centroids, same rules as above - on overflow the map, NaN rows included, stays entirely
+ * unchanged; leaf <= 0 is a no-op); ngicp_map_get downloads it for publishing
  * ({x, y, z, intensity}, 16 bytes per point). */
 int ngicp_map_add(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, long intensity_offset_bytes);
 int ngicp_map_voxel_filter(ngicp_t* h, float leaf, size_t* n_out_or_null);

@@ -1101,24 +1101,39 @@ double orc_gicp_lambda(const orc_gicp* g) { return g->lm_lambda; }
 // voxel index (i - min_b.x) + (j - min_b.y) div.x + (k - min_b.z) div.x div.y; points sorted by index; per voxel the
 // centroid of all fields = float sums / count (pcl::CentroidPoint), output in ascending index.  PCL's std::sort leaves the
 // order inside a voxel unspecified; here the sort is stable (input order), which only affects the last bits of the sums.
-// If the index would overflow int32 PCL warns and returns the input unchanged.
+// If the index would overflow int32 PCL warns and returns its input unchanged.  The rule, restated from memory of PCL like the rest
+// and stated alike in csrc/ngicp_filters.hip (header comment) and tests/_filter_model.py - nothing is converted to int before
+// tests (1) and (2) have passed (out of range that conversion is undefined; x86 yields INT_MIN):
+//   (1) PCL's extent test: inv_leaf finite; per axis ext = (max - min) * inv_leaf (float) finite and < 2^31; d = int64(ext) + 1;
+//       overflow when dx * dy * dz > INT_MAX;
+//   (2) floor(min * inv_leaf) and floor(max * inv_leaf) fit an int32 on every axis (PCL is undefined there);
+//   (3) div.x * div.y * div.z > INT_MAX.
+// "Its input" is the VoxelGrid stage's input (after removeNaN / CropBox): with remove_nan = 0 it still holds the non-finite rows.
 // ----------------------------------------------------------------------------
 size_t orc_filter_cloud(const float* pts, size_t n, size_t stride_floats, long ioff, int remove_nan, float crop_half, float leaf, float* out_xyzi) {
-  std::vector<float> cur;  // packed survivors
-  cur.reserve(n * 4);
+  std::vector<float> stage_in;  // packed input of the VoxelGrid stage: what removeNaN (if asked for) and CropBox left
+  stage_in.reserve(n * 4);
   const bool voxel = leaf > 0.f;
   for (size_t i = 0; i < n; ++i) {
     const float* p = pts + i * stride_floats;
     const float x = p[0], y = p[1], z = p[2], it = ioff >= 0 ? p[ioff] : 0.f;
-    if ((remove_nan || voxel) && !(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) continue;
-    if (crop_half > 0.f && !(x < -crop_half || y < -crop_half || z < -crop_half || x > crop_half || y > crop_half || z > crop_half)) continue;
-    cur.push_back(x); cur.push_back(y); cur.push_back(z); cur.push_back(it);
+    if (remove_nan && !(std::isfinite(x) && std::isfinite(y) && std::isfinite(z))) continue;
+    if (crop_half > 0.f && x >= -crop_half && x <= crop_half && y >= -crop_half && y <= crop_half && z >= -crop_half && z <= crop_half) continue;  // (NaN is not inside)
+    stage_in.push_back(x); stage_in.push_back(y); stage_in.push_back(z); stage_in.push_back(it);
   }
-  size_t m = cur.size() / 4;
-  if (!voxel || m == 0) {
-    std::memcpy(out_xyzi, cur.data(), cur.size() * sizeof(float));
-    return m;
+  const auto give_input = [&]() {
+    std::memcpy(out_xyzi, stage_in.data(), stage_in.size() * sizeof(float));
+    return stage_in.size() / 4;
+  };
+  if (!voxel) return give_input();
+  std::vector<float> cur;  // VoxelGrid itself skips the non-finite points
+  cur.reserve(stage_in.size());
+  for (size_t i = 0; i < stage_in.size() / 4; ++i) {
+    const float* p = &stage_in[i * 4];
+    if (std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])) cur.insert(cur.end(), p, p + 4);
   }
+  const size_t m = cur.size() / 4;
+  if (m == 0) return 0;
   float mn[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mx[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (size_t i = 0; i < m; ++i)
     for (int d = 0; d < 3; ++d) {
@@ -1126,16 +1141,28 @@ size_t orc_filter_cloud(const float* pts, size_t n, size_t stride_floats, long i
       mx[d] = std::max(mx[d], cur[i * 4 + d]);
     }
   const float inv = 1.0f / leaf;
-  int min_b[3], div[3];
+  const long long int_max = (long long)std::numeric_limits<int>::max();
+  // "Leaf size is too small for the input dataset": output = input.  (1) the extent test, (2) the range test - both in float / int64
+  if (!std::isfinite(inv)) return give_input();
   long long cells = 1;
   for (int d = 0; d < 3; ++d) {
+    const float ext = (mx[d] - mn[d]) * inv;
+    if (!std::isfinite(ext) || !(ext < 2147483648.f)) return give_input();
+    cells *= (long long)ext + 1;
+    if (cells > int_max) return give_input();
+  }
+  for (int d = 0; d < 3; ++d) {
+    const float flo = std::floor(mn[d] * inv), fhi = std::floor(mx[d] * inv);
+    if (!(flo >= -2147483648.f && fhi < 2147483648.f)) return give_input();
+  }
+  int min_b[3], div[3];
+  cells = 1;
+  for (int d = 0; d < 3; ++d) {  // (3) the product of div_b
     min_b[d] = (int)std::floor(mn[d] * inv);
-    div[d] = (int)std::floor(mx[d] * inv) - min_b[d] + 1;
-    cells *= (long long)div[d];
-    if (cells > (long long)std::numeric_limits<int>::max()) {  // "Leaf size is too small for the input dataset": output = input
-      std::memcpy(out_xyzi, cur.data(), cur.size() * sizeof(float));
-      return m;
-    }
+    const long long dv = (long long)(int)std::floor(mx[d] * inv) - (long long)min_b[d] + 1;
+    cells *= dv;
+    if (cells > int_max) return give_input();
+    div[d] = (int)dv;
   }
   std::vector<std::pair<unsigned int, unsigned int>> idx(m);
   for (size_t i = 0; i < m; ++i) {
