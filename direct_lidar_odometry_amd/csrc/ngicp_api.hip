@@ -24,6 +24,7 @@
 #include "ngicp_cloudops.h"
 #include "ngicp_filters.h"
 #include "ngicp_query.h"
+#include "ngicp_range.h"
 #include "ngicp_batch.h"
 
 using namespace ngk;
@@ -328,6 +329,7 @@ struct ngicp {
   DevBuf fit_T, fit_part, fit_out, rad_counts, rad_offsets, rad_keys, rad_long;
   size_t rad_total = 0;
   bool rad_valid = false;
+  DevBuf range_ws;  // ngicp_range_select (ngicp_range.h): three rounds' histograms + the record; nothing else lives here
   hipEvent_t ev_q_a = nullptr, ev_q_b = nullptr;  // around the kernels of the last query call (ngicp_stats::query_ms)
   std::vector<hipEvent_t> prof_events;  // pairs around each pass launch when profiling is on
   int* h_progress = nullptr;  // pinned: {passes done | kProgressDone}, written by the solver (SolveArgs::progress_host)
@@ -1660,6 +1662,47 @@ void knn_impl(ngicp* h, int which, const float* q, size_t nq, size_t stride, int
   query_timing_done(h);
 }
 
+// ---- range select (ngicp_range.h) ----
+// which: 0 = source, 1 = target, 2 = the preprocessed scan still on the device.  median: rank = n / 2.
+void range_select_impl(ngicp* h, int which, size_t rank, bool median, float* value, size_t* n_out) {
+  if (!value) throw ArgError{NGICP_ERR_ARG, "null output"};
+  if (which < 0 || which > 2) throw ArgError{NGICP_ERR_ARG, "which must be 0 (source), 1 (target) or 2 (preprocessed scan)"};
+  const float4* pts = nullptr;
+  size_t n = 0;
+  if (which == 2) {
+    if (!h->filt_out || h->filt_n <= 0) throw ArgError{NGICP_ERR_STATE, "no preprocessed cloud: call ngicp_preprocess_scan first"};
+    pts = h->filt_out;
+    n = (size_t)h->filt_n;
+  } else {
+    DeviceCloud& C = query_cloud(h, which);
+    pts = C.pts();  // the real points: the sentinel frame lies outside [pts, pts + n)
+    n = C.n;
+  }
+  if (n == 0) throw ArgError{NGICP_ERR_STATE, "the cloud is empty"};
+  if (n > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "cloud too large for int counters"};
+  if (n_out) *n_out = n;
+  if (median) rank = n / 2;
+  if (rank >= n) throw ArgError{NGICP_ERR_ARG, "rank must be below the number of points"};
+  constexpr size_t kHistBytes = 3 * kRangeBins * sizeof(int);
+  h->range_ws.ensure(kHistBytes + sizeof(RangeRec));
+  int* hist = h->range_ws.as<int>();
+  RangeRec* rec = reinterpret_cast<RangeRec*>(h->range_ws.as<unsigned char>() + kHistBytes);
+  const int blocks = pick_blocks(n, 4 * kRangeBlock, kRangeMaxBlocks);
+  HIP_TRY(hipEventRecord(h->ev_q_a, h->stream));
+  HIP_TRY(hipMemsetAsync(hist, 0, kHistBytes, h->stream));
+  for (int round = 0; round < 3; ++round) {
+    hipLaunchKernelGGL(k_range_hist, dim3(blocks), dim3(kRangeBlock), 0, h->stream, pts, (int)n, round, (const RangeRec*)rec, hist + round * kRangeBins);
+    hipLaunchKernelGGL(k_range_pick, dim3(1), dim3(kRangeBlock), 0, h->stream, (const int*)(hist + round * kRangeBins), round, (int)rank, rec);
+  }
+  HIP_TRY(hipEventRecord(h->ev_q_b, h->stream));
+  unsigned int bits = 0;
+  HIP_TRY(hipMemcpyAsync(&bits, &rec->value, sizeof(bits), hipMemcpyDeviceToHost, h->stream));  // the one read-back
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  query_timing_done(h);
+  std::memcpy(value, &bits, sizeof(bits));
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -2210,6 +2253,14 @@ int ngicp_fitness_score(ngicp_t* h, const float T_colmajor[16], double max_range
     *score = cnt ? r.x / r.y : std::numeric_limits<double>::max();
     if (n_inliers) *n_inliers = cnt;
   });
+}
+
+int ngicp_range_select(ngicp_t* h, int which, size_t rank, float* value, size_t* n_points) {
+  return guarded(h, [&] { range_select_impl(h, which, rank, false, value, n_points); });
+}
+
+int ngicp_range_median(ngicp_t* h, int which, float* value, size_t* n_points) {
+  return guarded(h, [&] { range_select_impl(h, which, 0, true, value, n_points); });
 }
 
 int ngicp_get_lm_trace(ngicp_t* h, double* rows, size_t max_rows, size_t* n_rows) {

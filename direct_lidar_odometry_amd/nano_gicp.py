@@ -77,6 +77,7 @@ EXPORTS = [
     "ngicp_map_clear", "ngicp_math_selftest", "ngicp_set_host_wait", "ngicp_covs_shard_begin", "ngicp_covs_shard_compute", "ngicp_covs_shard_commit",
     "ngicp_knn_search", "ngicp_radius_search", "ngicp_radius_fetch", "ngicp_fitness_score",
     "ngicp_align_batch", "ngicp_batch_get_lm_trace", "ngicp_fitness_score_batch",
+    "ngicp_range_select", "ngicp_range_median",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -130,6 +131,8 @@ def load_library() -> C.CDLL:
     L.ngicp_radius_search.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ngicp_radius_fetch.argtypes = [vp, c_i32p, c_f32p, C.c_size_t]
     L.ngicp_fitness_score.argtypes = [vp, c_f32p, C.c_double, c_f64p, C.POINTER(C.c_size_t)]
+    L.ngicp_range_select.argtypes = [vp, C.c_int, C.c_size_t, c_f32p, C.POINTER(C.c_size_t)]
+    L.ngicp_range_median.argtypes = [vp, C.c_int, c_f32p, C.POINTER(C.c_size_t)]
     L.ngicp_get_lm_trace.argtypes = [vp, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_align_batch.argtypes = [vp, C.c_size_t, c_f32p, c_f32p, c_i32p, c_i32p, c_f64p]
     L.ngicp_batch_get_lm_trace.argtypes = [vp, C.c_size_t, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -444,6 +447,30 @@ class NanoGICP:
         idx = np.empty(total.value, dtype=np.int32); d2 = np.empty(total.value, dtype=np.float32)
         self._ck(self._L.ngicp_radius_fetch(self._h, _p(idx, c_i32p), _p(d2, c_f32p), total.value))
         return offsets.astype(np.int64), idx, d2
+
+    # ---- range select: DLO's spaciousness median without downloading the scan (include/ngicp.h "range select") ----
+    _RANGE_WHICH = {"source": 0, "target": 1, "preprocessed": 2}
+
+    def _range_which(self, which) -> int:
+        if which not in self._RANGE_WHICH:
+            raise NgicpError(-2, f"which must be one of {sorted(self._RANGE_WHICH)}, not {which!r}")
+        return self._RANGE_WHICH[which]
+
+    def rangeSelect(self, rank: int, which: str = "source") -> np.float32:
+        """The range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order, NaN after
+        +inf.  which: "source" | "target" | "preprocessed" (the scan preprocessScan left on the device)."""
+        w = self._range_which(which)
+        if rank < 0:
+            raise NgicpError(-2, "rank must not be negative")
+        v = C.c_float(0)
+        self._ck(self._L.ngicp_range_select(self._h, w, int(rank), C.byref(v), None))
+        return np.float32(v.value)
+
+    def medianRange(self, which: str = "source") -> np.float32:
+        """rangeSelect(n // 2): the median_curr of computeSpaciousness (odom.cc:1000-1002)."""
+        v = C.c_float(0)
+        self._ck(self._L.ngicp_range_median(self._h, self._range_which(which), C.byref(v), None))
+        return np.float32(v.value)
 
     def lm_trace(self, lane=None) -> np.ndarray:
         """LM trace of the last align() (lane None), or of lane `lane` of the last alignBatch()."""

@@ -72,6 +72,26 @@ using CovVector = std::vector<ngicp_compat::Matrix4d>;
 
 namespace nano_gicp {
 
+// The low-pass state of computeSpaciousness (odom.cc:1003-1005): `static float median_prev = median_curr;
+// float median_lpf = 0.95*median_prev + 0.05*median_curr; median_prev = median_lpf;` - the state is a float seeded with the first
+// median, the update is evaluated in double (the literals are doubles) and narrowed to float.  Host only.  With it the call site is
+//     float median_curr = this->gicp_s2s.medianRange();
+//     this->metrics.spaciousness.push_back(this->spaciousness_lpf.update(median_curr));
+struct SpaciousnessFilter {
+  bool seeded = false;
+  float median_prev = 0.f;
+  float update(float median_curr) {
+    if (!seeded) {
+      median_prev = median_curr;
+      seeded = true;
+    }
+    const float median_lpf = 0.95 * median_prev + 0.05 * median_curr;
+    median_prev = median_lpf;
+    return median_lpf;
+  }
+  void reset() { seeded = false; }
+};
+
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };  // gicp/gicp_settings.hpp:47
 enum class LSQ_OPTIMIZER_TYPE { GaussNewton, LevenbergMarquardt };                         // lsq_registration.hpp:54
 
@@ -343,6 +363,21 @@ class NanoGICP {
     return score;
   }
   ngicp_t* handle() { return h_; }
+
+  // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
+  // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN
+  // after +inf); medianRange: rank n / 2, the reference's median_curr.  which: 0 = the input source, 1 = the target, 2 = the scan
+  // preprocessPoints left on the device.  NaN (and a line on stderr) on failure.  Computed on the GPU (csrc/ngicp_range.h).
+  float rangeSelect(size_t rank, int which = 0) {
+    float v = std::numeric_limits<float>::quiet_NaN();
+    if (h_) check(ngicp_range_select(h_, which, rank, &v, nullptr), "rangeSelect");
+    return v;
+  }
+  float medianRange(int which = 0) {
+    float v = std::numeric_limits<float>::quiet_NaN();
+    if (h_) check(ngicp_range_median(h_, which, &v, nullptr), "medianRange");
+    return v;
+  }
 
   // ---- more than one candidate pose (no counterpart in the reference; include/ngicp.h "more than one initial guess") ----
   // alignBatch: every guess aligned on the current source / target pair in the same kernel launches; result g is bit for bit what

@@ -164,6 +164,23 @@ int ngicp_radius_fetch(ngicp_t* h, int* idx, float* sqd, size_t capacity);
  * T_colmajor_or_null: NULL = final_transformation_ of the last align (identity before any, as PCL).  Where the reference would
  * dereference the null search tree DLO hands PCL (src/dlo/odom.cc:116-120), this returns what PCL computes with a built tree. */
 int ngicp_fitness_score(ngicp_t* h, const float T_colmajor_or_null[16], double max_range, double* score, size_t* n_inliers_or_null);
+/* --- range select: the spaciousness metric's median (dlo::OdomNode::computeSpaciousness, src/dlo/odom.cc:990-1010) -------------
+ * The range of a point is d = (float) sqrt((double)x*x + (double)y*y + (double)z*z), summed left to right in double - odom.cc:996
+ * bit for bit.  Ranges are ordered ascending by value; a NaN range (a NaN coordinate) sorts AFTER +inf and is returned as the quiet
+ * NaN 0x7fc00000.  ngicp_range_select: *value = the range of 0-based rank `rank` of the cloud's n ranges, computed on the device by
+ * an exact radix select (csrc/ngicp_range.h: integer counts only, so the result is deterministic); ngicp_range_median: the same for
+ * rank n / 2, the element std::nth_element(ds.begin(), ds.begin() + ds.size() / 2, ds.end()) leaves at ds[ds.size() / 2].  (The
+ * reference's loop runs `i <= size()`: it reads one point past the end and takes rank (n + 1) / 2 of n + 1 values, one of them
+ * indeterminate.  The engine implements the n-value median the loop evidently intends: INTEGRATION.md, divergences.)
+ * which: 0 = source, 1 = target (the slot's CURRENT cloud; a registered source is uploaded first, as for the queries above),
+ *        2 = the preprocessed scan ngicp_preprocess_scan left on the device (non-finite rows that remove_nan = 0 left in it count).
+ * *n_points_or_null = n, written as soon as the cloud is known (also when the rank is then refused).
+ * Errors: NGICP_ERR_STATE for a missing or empty cloud - for which = 2 also once a later call has consumed the filter workspace,
+ * exactly when ngicp_set_source_preprocessed would refuse; NGICP_ERR_ARG for rank >= n, which outside 0..2 or a null value.
+ * One 4-byte read-back and one synchronisation per call.  Changes nothing any other getter returns (scratch of its own);
+ * ngicp_stats.query_ms is the device time of its kernels. */
+int ngicp_range_select(ngicp_t* h, int which, size_t rank, float* value, size_t* n_points_or_null);
+int ngicp_range_median(ngicp_t* h, int which, float* value, size_t* n_points_or_null);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
@@ -224,7 +241,7 @@ typedef struct ngicp_stats {
   long long device_allocs;  /* hipMalloc calls made by this process's engine buffers so far (a call that grows a buffer in the middle of
                                a frame shows up as a latency outlier: two readings around a call attribute it) */
   long long host_wait_spins; /* polls of the solver's progress word during the last ngicp_align() (busy or yielding, see below) */
-  double query_ms;          /* device time (HIP events on the handle's stream) of the kernels of the last knn / radius / fitness query */
+  double query_ms;          /* device time (HIP events on the handle's stream) of the kernels of the last knn / radius / fitness / range query */
 } ngicp_stats;
 int ngicp_get_stats(ngicp_t* h, ngicp_stats* out);
 /* HIP-event timing of the k_gicp_pass launches inside align (two event records per timed launch; off by default).
