@@ -26,6 +26,7 @@
 #include "ngicp_query.h"
 #include "ngicp_range.h"
 #include "ngicp_batch.h"
+#include "ngicp_voxel.h"
 
 using namespace ngk;
 
@@ -372,6 +373,27 @@ struct ngicp {
   std::vector<Keyframe> keyframes;
   std::vector<int> submap_ids;           // keyframes of the submap that is the current target (valid while submap_cloud is the target)
   const DeviceCloud* submap_cloud = nullptr;
+
+  // voxelized GICP (ngicp_voxel.h)
+  double voxel_res = 0.0;  // ngicp_set_voxel_resolution: > 0 selects the mode
+  struct VoxelMap {
+    bool valid = false;
+    double res = 0.0;                    // the resolution it was built with
+    std::shared_ptr<DeviceCloud> cloud;  // the target and the covariance set it was built from, HELD: a recycled object cannot take their addresses
+    std::shared_ptr<DevBuf> covs;
+    size_t n_vox = 0;
+    unsigned int mask = 0;               // hash table slots - 1
+    DevBuf rec, vkeys, table;            // [n_vox][kVoxRec] doubles, [n_vox] keys, [mask + 1] {key, voxel number}
+    void invalidate() {
+      valid = false;
+      cloud.reset();
+      covs.reset();
+      n_vox = 0;
+    }
+  } vmap;
+  FilterWorkspace vox_ws;                // the radix sort's scratch (its own: a preprocess result lives in fws)
+  DevBuf vox_keys, vox_vals, vox_scan, vox_flag, vox_corr[2];
+  hipEvent_t ev_vox_a = nullptr, ev_vox_b = nullptr;
 };
 
 namespace {
@@ -985,6 +1007,52 @@ void download_transformed(ngicp* h, DeviceCloud& dc, const float T_colmajor[16],
   download_xyz(h, n, out, out_stride);
 }
 
+// ---- what do_align and do_align_voxel share: the host's wait on the device's progress, and what an alignment leaves on the handle ----
+// One turn of the wait for the solver's published progress: give up after 30 s, otherwise yield or pause.
+inline void wait_for_the_loop(ngicp* h, unsigned long& spins, double t_loop) {
+  if ((++spins & (h->host_wait ? 0xfff : 0xfffff)) == 0 && now_ms() - t_loop > 30000.0) throw ArgError{NGICP_ERR_HIP, "the registration loop did not finish within 30 s"};
+  if (h->host_wait) sched_yield(); else __builtin_ia32_pause();
+}
+
+// The final state's results, the transformed cloud if asked for, and the statistics that do not depend on the pass kernel.
+void publish_alignment(ngicp* h, const LmState& st, float loop_ms, float* aligned, size_t out_stride) {
+  pose_to_colmajor_f(st.hot.x0, h->final_T);
+  h->converged = st.hot.converged;
+  h->nr_iterations = st.hot.nr_iterations;
+  for (int r = 0; r < 6; ++r)
+    for (int cc = 0; cc < 6; ++cc) h->final_hessian[cc * 6 + r] = st.hot.final_H[r * 6 + cc];
+  if (st.hot.lm_failed) std::fprintf(stderr, "lm not converged!!\n");  // impl/lsq_registration_impl.hpp:106
+  h->trace_host.clear();  // fetched on demand (ngicp_get_lm_trace): a diagnostic should not cost every align a synchronous copy
+  h->trace_rows_dev = (size_t)st.hot.n_trace;
+  if (aligned) download_transformed(h, *h->src.dev, h->final_T, aligned, out_stride);  // K5: pcl::transformPointCloud(*input_, output, final_transformation_)
+  if (st.hot.have_lin) h->hook_valid = 2;  // ngicp_get_correspondences: the correspondences of the last adopted linearisation
+  ngicp_stats& s = h->stats;
+  s.loop_ms = loop_ms;
+  s.passes = st.hot.passes;
+  s.outer_iterations = st.hot.nr_iterations + 1;
+  s.lm_trials = st.hot.n_trace;
+  s.mean_candidates = st.hot.passes > 0 ? st.hot.cand_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
+  s.valid_fraction = st.hot.passes > 0 ? st.hot.valid_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
+  s.pass_ms_total = 0.0;
+  s.passes_timed = 0;
+}
+
+// With profiling on: HIP events on the handle's own stream around every prof_stride-th pass launch that did work.
+void sum_event_pass_times(ngicp* h, long passes) {
+  if (!h->profiling) return;
+  ngicp_stats& s = h->stats;
+  const long timed = std::min<long>(passes, (long)h->prof_events.size() / 2);
+  int counted = 0;
+  for (long i = h->prof_stride / 2; i < timed; i += h->prof_stride) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->prof_events[2 * i], h->prof_events[2 * i + 1]) == hipSuccess) {
+      s.pass_ms_total += ms;
+      ++counted;
+    }
+  }
+  s.passes_timed = counted;
+}
+
 void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride) {
   const double t_begin = now_ms();
   h->hook_valid = 0;
@@ -1193,8 +1261,7 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
     const int prog = *reinterpret_cast<volatile int*>(h->h_progress);
     if (prog & kProgressDone) break;
     if (launched - (long)(prog & kProgressMask) >= depth) {  // enough in flight: wait for the device to catch up
-      if ((++spins & (h->host_wait ? 0xfff : 0xfffff)) == 0 && now_ms() - t_loop > 30000.0) throw ArgError{NGICP_ERR_HIP, "the registration loop did not finish within 30 s"};
-      if (h->host_wait) sched_yield(); else __builtin_ia32_pause();
+      wait_for_the_loop(h, spins, t_loop);
       continue;
     }
     const bool timed = h->profiling && launched % h->prof_stride == h->prof_stride / 2 && (size_t)(2 * launched + 1) < h->prof_events.size();
@@ -1254,8 +1321,7 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
       const int prog = __atomic_load_n(h->h_progress, __ATOMIC_ACQUIRE);
       if (prog & kProgressDone) break;
       if (launched >= max_launches && launched - (long)(prog & kProgressMask) <= 0) break;  // (cannot happen: the last possible pass sets done)
-      if ((++spins & (h->host_wait ? 0xfff : 0xfffff)) == 0 && now_ms() - t_loop > 30000.0) throw ArgError{NGICP_ERR_HIP, "the registration loop did not finish within 30 s"};
-      if (h->host_wait) sched_yield(); else __builtin_ia32_pause();
+      wait_for_the_loop(h, spins, t_loop);
     }
     st.hot = *h->pin_final;
     loop_ms = (float)((double)(st.hot.t_done - st.hot.t_first) * 1e-5);  // 100 MHz ticks -> ms
@@ -1307,29 +1373,12 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
       std::fclose(f);
     }
   }
-  pose_to_colmajor_f(st.hot.x0, h->final_T);
-  h->converged = st.hot.converged;
-  h->nr_iterations = st.hot.nr_iterations;
-  for (int r = 0; r < 6; ++r)
-    for (int cc = 0; cc < 6; ++cc) h->final_hessian[cc * 6 + r] = st.hot.final_H[r * 6 + cc];
-  if (st.hot.lm_failed) std::fprintf(stderr, "lm not converged!!\n");  // impl/lsq_registration_impl.hpp:106
-  h->trace_host.clear();  // fetched on demand (ngicp_get_lm_trace): a diagnostic should not cost every align a synchronous copy
-  h->trace_rows_dev = (size_t)st.hot.n_trace;
-
-  if (aligned) download_transformed(h, *h->src.dev, h->final_T, aligned, out_stride);  // K5: pcl::transformPointCloud(*input_, output, final_transformation_)
+  publish_alignment(h, st, loop_ms, aligned, out_stride);
   ngicp_stats& s = h->stats;
-  s.loop_ms = loop_ms;
-  if (st.hot.have_lin) h->hook_valid = 2;  // ngicp_get_correspondences: the correspondences of the last adopted linearisation
   h->order_src = h->src.dev.get();  // (what the order flag on the device, if set, refers to)
   h->order_groups = c.sa.nblocks;
-  s.passes = st.hot.passes;
-  s.outer_iterations = st.hot.nr_iterations + 1;
-  s.lm_trials = st.hot.n_trace;
-  s.mean_candidates = st.hot.passes > 0 ? st.hot.cand_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
-  s.valid_fraction = st.hot.passes > 0 ? st.hot.valid_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
   s.staged_fraction = st.hot.passes > 0 ? st.hot.staged_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
   if (st.hot.passes > 1) h->prev_staged_fraction = s.staged_fraction;
-  s.pass_ms_total = 0.0;
   if (h->profiling && persist_done) {
     // the persistent kernel's own stamps (100 MHz): a pass lasts from its release (the first: the alignment's first stamp) to the arrival
     // of its last block; the optimiser's step and the release that follows are not part of it
@@ -1353,21 +1402,201 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
       }
       std::fprintf(stderr, "\n");
     }
-  } else if (h->profiling) {
-    // HIP events on the handle's own stream around every pass launch that did work
-    const long timed = std::min<long>(st.hot.passes, (long)h->prof_events.size() / 2);
-    int counted = 0;
-    for (long i = h->prof_stride / 2; i < timed; i += h->prof_stride) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, h->prof_events[2 * i], h->prof_events[2 * i + 1]) == hipSuccess) {
-        s.pass_ms_total += ms;
-        ++counted;
-      }
-    }
-    s.passes_timed = counted;
   } else {
-    s.passes_timed = 0;
+    sum_event_pass_times(h, st.hot.passes);
   }
+  s.n_src = (long long)h->src.dev->n;
+  s.n_tgt = (long long)h->tgt.dev->n;
+  s.host_wait_spins = (long long)spins;
+  s.align_ms = now_ms() - t_begin;
+}
+
+// ------------------------------------------------------------------------------------------
+// Voxelized GICP (ngicp_voxel.h): a mode the caller selects with ngicp_set_voxel_resolution
+// ------------------------------------------------------------------------------------------
+void refuse_if_voxelized(ngicp* h, const char* entry) {
+  if (h->voxel_res > 0.0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": not available with a voxelized target (ngicp_set_voxel_resolution(h, 0) selects exact GICP)"};
+}
+
+// The target, or its covariances, changed: the voxel map goes, and while the mode is on so do the correspondences, which are its voxel
+// numbers (ngicp_get_correspondences would read the next map's records with them).  Exact GICP's correspondences are left as they were.
+void drop_voxel_map(ngicp* h) {
+  h->vmap.invalidate();
+  if (h->voxel_res > 0.0) h->hook_valid = 0;
+}
+
+// The voxel map of the current target, its covariances (computed if missing, as for align) and the resolution: built at the first use
+// after any of the three changed.  Two host synchronisations (the voxel count sizes the map; the build time).
+void ensure_voxel_map(ngicp* h) {
+  ensure_slot_ready(h, h->tgt, "target");
+  if (h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
+  const double* covs = covs_for(h, h->tgt_covs, h->tgt.dev);
+  ngicp::VoxelMap& m = h->vmap;
+  if (m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data) return;
+  m.invalidate();
+  DeviceCloud& T = *h->tgt.dev;
+  const int n = (int)T.n;
+  const float inv_res = 1.0f / (float)h->voxel_res;
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  const int ntiles = (n + kScanTile - 1) / kScanTile;
+  // (every buffer is sized before the first launch: growing one frees it, and freeing waits for the device)
+  h->vox_keys.ensure((size_t)n * 2 * sizeof(unsigned long long));
+  h->vox_vals.ensure((size_t)n * 2 * sizeof(int));
+  h->vox_scan.ensure(((size_t)n * 3 + 2 + kCellPad) * sizeof(int));
+  h->vox_flag.ensure(64);
+  h->tile_sums.ensure((size_t)ntiles * sizeof(int));
+  unsigned long long* keys_a = h->vox_keys.as<unsigned long long>();
+  unsigned long long* keys_b = keys_a + n;
+  int* vals_a = h->vox_vals.as<int>();
+  int* vals_b = vals_a + n;
+  int* head = h->vox_scan.as<int>();
+  int* vox_of = head + n;                    // n + 1 + kCellPad
+  int* seg_start = vox_of + n + 1 + kCellPad;  // n + 1
+  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+  HIP_TRY(hipMemsetAsync(h->vox_flag.p, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_voxel_map_keys, dim3(blocks), dim3(256), 0, h->stream, T.pts(), n, inv_res, keys_a, vals_a, h->vox_flag.as<int>());
+  char err[256] = {0};
+  int in_a = 1;
+  if (ngk_sort_pairs_u64(h->stream, &h->vox_ws, keys_a, keys_b, vals_a, vals_b, n, kVoxKeyBits, &in_a, err, sizeof(err))) throw ArgError{NGICP_ERR_HIP, err};
+  const unsigned long long* keys = in_a ? keys_a : keys_b;
+  const int* order = in_a ? vals_a : vals_b;
+  hipLaunchKernelGGL(k_voxel_map_heads, dim3(blocks), dim3(256), 0, h->stream, keys, n, head);
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)head, n, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)head, n, (const int*)h->tile_sums.as<int>(), vox_of);
+  hipLaunchKernelGGL(k_voxel_map_starts, dim3(blocks), dim3(256), 0, h->stream, (const int*)head, (const int*)vox_of, n, seg_start);
+  int n_vox = 0, bad = 0;
+  HIP_TRY(hipMemcpyAsync(&n_vox, vox_of + n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (bad) throw ArgError{NGICP_ERR_ARG, "voxelized target: a point lies 2^20 voxels or more from the origin on some axis (or is not finite); use a coarser resolution"};
+  if (n_vox <= 0 || n_vox > n) throw ArgError{NGICP_ERR_HIP, "voxel map build: inconsistent voxel count"};
+  size_t slots = 64;
+  while (slots < 2 * (size_t)n_vox) slots <<= 1;
+  m.rec.ensure((size_t)n_vox * kVoxRec * sizeof(double));
+  m.vkeys.ensure((size_t)n_vox * sizeof(unsigned long long));
+  m.table.ensure(slots * sizeof(ulonglong2));
+  HIP_TRY(hipMemsetAsync(m.table.p, 0xff, slots * sizeof(ulonglong2), h->stream));
+  hipLaunchKernelGGL(k_voxel_map_fill, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, h->stream, keys, order, (const int*)seg_start, n_vox, T.pts(), covs, m.rec.as<double>(),
+                     m.vkeys.as<unsigned long long>(), m.table.as<ulonglong2>(), (unsigned int)(slots - 1));
+  HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
+  HIP_TRY(hipEventSynchronize(h->ev_vox_b));
+  HIP_TRY(hipGetLastError());
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess) h->stats.voxelmap_ms = ms;
+  m.n_vox = (size_t)n_vox;
+  m.mask = (unsigned int)(slots - 1);
+  m.res = h->voxel_res;
+  m.cloud = h->tgt.dev;
+  m.covs = h->tgt_covs.data;
+  m.valid = true;
+}
+
+struct VoxelCtx {
+  VoxelPassArgs pa;
+  SolveArgs sa;
+  int nblocks;
+};
+
+// prepare_loop readies the slots, the covariances, the state, the trace and the solver's arguments exactly as for the exact path; the
+// voxelized pass then brings its own grid (256 source points per block), its own rows and correspondence buffers.  The launch order of
+// the exact pass's groups (grp_order, its flag) is neither read nor written.
+void prepare_voxel_loop(ngicp* h, VoxelCtx& v) {
+  LoopCtx c;
+  prepare_loop(h, c);
+  ensure_voxel_map(h);
+  DeviceCloud& S = *h->src.dev;
+  const size_t n = S.n;
+  const int nblocks = std::max(1, (int)((n + kVoxBlock - 1) / kVoxBlock));
+  h->partials.ensure((size_t)kNumSlots * nblocks * sizeof(double));
+  for (int i = 0; i < 2; ++i) h->vox_corr[i].ensure(n * sizeof(int));
+  VoxelPassArgs& a = v.pa;
+  a.src = S.pts();
+  a.cov_src = covs_for(h, h->src_covs, h->src.dev);
+  a.n_src = (int)n;
+  a.table = h->vmap.table.as<ulonglong2>();
+  a.mask = h->vmap.mask;
+  a.rec = h->vmap.rec.as<double>();
+  a.n_vox = (int)h->vmap.n_vox;
+  a.inv_res = 1.0f / (float)h->voxel_res;
+  for (int i = 0; i < 2; ++i) {
+    a.corr[i] = h->vox_corr[i].as<int>();
+    a.mahal[i] = h->mahal[i].as<double>();
+  }
+  a.st = h->state.as<LmState>();
+  a.partials = h->partials.as<double>();
+  a.mode = 3;
+  a.t_first = nullptr;
+  v.sa = c.sa;
+  v.sa.partials = a.partials;
+  v.sa.nblocks = nblocks;
+  v.sa.grp_order = nullptr;  // (the solver sorts nothing)
+  v.sa.grp_cost = nullptr;
+  v.sa.order_valid = nullptr;
+  v.nblocks = nblocks;
+}
+
+// do_align for a voxelized target: the same loop - state upload, (pass, solve) pairs fed `chunk_pairs` ahead of the solver's published
+// progress, the final state read from pinned memory - with k_vgicp_pass in k_gicp_pass's place.  None of the exact path's kernel-variant
+// switches applies.
+void do_align_voxel(ngicp* h, const float guess[16], float* aligned, size_t out_stride) {
+  const double t_begin = now_ms();
+  h->hook_valid = 0;
+  h->converged = 0;
+  h->nr_iterations = 0;
+  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::memcpy(h->final_T, I, sizeof(I));
+  VoxelCtx c;
+  prepare_voxel_loop(h, c);
+  LmState st;
+  init_state_from_pose(st, pose_from_colmajor_f(guess));
+  c.pa.mode = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? 2 : 3;
+  if (h->p.max_iter <= 0) st.hot.done = 1;
+  h->pin_state[0] = st;
+  HIP_TRY(hipMemcpyAsync(h->state.p, &h->pin_state[0], sizeof(st), hipMemcpyHostToDevice, h->stream));
+  const long max_passes = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? (long)h->p.max_iter : (long)h->p.max_iter * std::max(1, h->p.lm_max_iter) + 1;
+  const int depth = h->chunk_pairs;
+  *h->h_progress = 0;
+  c.sa.progress_host = h->h_progress;
+  c.sa.final_host = h->pin_final;
+  c.sa.t_first = h->t_first.as<unsigned long long>();
+  c.pa.t_first = h->t_first.as<unsigned long long>();
+  long launched = 0;
+  const bool finished = (h->p.max_iter <= 0);
+  const double t_loop = now_ms();
+  unsigned long spins = 0;
+  while (!finished && launched < max_passes) {
+    const int prog = *reinterpret_cast<volatile int*>(h->h_progress);
+    if (prog & kProgressDone) break;
+    if (launched - (long)(prog & kProgressMask) >= depth) {
+      wait_for_the_loop(h, spins, t_loop);
+      continue;
+    }
+    const bool timed = h->profiling && launched % h->prof_stride == h->prof_stride / 2 && (size_t)(2 * launched + 1) < h->prof_events.size();
+    hipExtLaunchKernelGGL(k_vgicp_pass, dim3((unsigned)c.nblocks), dim3(kVoxBlock), 0, h->stream, timed ? h->prof_events[2 * launched] : nullptr,
+                          timed ? h->prof_events[2 * launched + 1] : nullptr, 0, c.pa);
+    hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, c.sa);
+    ++launched;
+  }
+  float loop_ms = 0.f;
+  if (finished) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  } else {
+    for (;;) {
+      const int prog = __atomic_load_n(h->h_progress, __ATOMIC_ACQUIRE);
+      if (prog & kProgressDone) break;
+      if (launched >= max_passes && launched - (long)(prog & kProgressMask) <= 0) break;
+      wait_for_the_loop(h, spins, t_loop);
+    }
+    st.hot = *h->pin_final;
+    loop_ms = (float)((double)(st.hot.t_done - st.hot.t_first) * 1e-5);
+  }
+  HIP_TRY(hipGetLastError());
+  publish_alignment(h, st, loop_ms, aligned, out_stride);  // (mean_candidates: this mode tests no target point, it counts the hash-table slots looked at)
+  ngicp_stats& s = h->stats;
+  s.staged_fraction = 0.0;
+  sum_event_pass_times(h, st.hot.passes);
   s.n_src = (long long)h->src.dev->n;
   s.n_tgt = (long long)h->tgt.dev->n;
   s.host_wait_spins = (long long)spins;
@@ -1736,6 +1965,8 @@ int ngicp_create(int device, ngicp_t** out) {
     HIP_TRY(hipEventCreateWithFlags(&h->ev_fence, hipEventDisableTiming));
     HIP_TRY(hipEventCreate(&h->ev_q_a));
     HIP_TRY(hipEventCreate(&h->ev_q_b));
+    HIP_TRY(hipEventCreate(&h->ev_vox_a));
+    HIP_TRY(hipEventCreate(&h->ev_vox_b));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_state), 2 * sizeof(LmState), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_final), sizeof(LmHot), hipHostMallocDefault));
     h->order_flag.ensure(64);
@@ -1823,7 +2054,11 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_fence) (void)hipEventDestroy(h->ev_fence);
   if (h->ev_q_a) (void)hipEventDestroy(h->ev_q_a);
   if (h->ev_q_b) (void)hipEventDestroy(h->ev_q_b);
+  if (h->ev_vox_a) (void)hipEventDestroy(h->ev_vox_a);
+  if (h->ev_vox_b) (void)hipEventDestroy(h->ev_vox_b);
+  h->vmap.invalidate();
   ngk_filter_free(&h->fws);
+  ngk_filter_free(&h->vox_ws);
   hipStream_t s = h->stream;
   delete h;
   if (s) (void)hipStreamDestroy(s);
@@ -1878,6 +2113,7 @@ int ngicp_set_target(ngicp_t* h, const float* xyz, size_t n, size_t stride_bytes
   if (!same) {  // the target is no longer the submap assembled by ngicp_submap_set (a recycled index object may reuse its address)
     h->submap_cloud = nullptr;
     h->submap_ids.clear();
+    drop_voxel_map(h);
   }
   return rc;
 }
@@ -1893,6 +2129,7 @@ int ngicp_clear_target(ngicp_t* h) {
     h->tgt_covs.clear();
     h->submap_cloud = nullptr;
     h->submap_ids.clear();
+    drop_voxel_map(h);
   });
 }
 
@@ -1921,6 +2158,7 @@ int ngicp_swap_source_target(ngicp_t* h) {
     h->hook_valid = 0;  // correspondences_.clear(); sq_distances_.clear();
     h->submap_cloud = nullptr;
     h->submap_ids.clear();
+    drop_voxel_map(h);
   });
 }
 
@@ -1928,7 +2166,10 @@ int ngicp_compute_source_covs(ngicp_t* h) {
   return guarded(h, [&] { compute_covs(h, h->src, h->src_covs, "source"); });
 }
 int ngicp_compute_target_covs(ngicp_t* h) {
-  return guarded(h, [&] { compute_covs(h, h->tgt, h->tgt_covs, "target"); });
+  return guarded(h, [&] {
+    drop_voxel_map(h);
+    compute_covs(h, h->tgt, h->tgt_covs, "target");
+  });
 }
 
 int ngicp_copy_source_covs(ngicp_t* dst, ngicp_t* src) {
@@ -1951,7 +2192,10 @@ int ngicp_clear_source_covs(ngicp_t* h) {
   return guarded(h, [&] { h->src_covs.clear(); });
 }
 int ngicp_clear_target_covs(ngicp_t* h) {
-  return guarded(h, [&] { h->tgt_covs.clear(); });
+  return guarded(h, [&] {
+    h->tgt_covs.clear();
+    drop_voxel_map(h);
+  });
 }
 int ngicp_source_covs_size(const ngicp_t* h, size_t* n) {
   if (!h || !n) return NGICP_ERR_ARG;
@@ -1979,14 +2223,18 @@ int ngicp_set_source_covs(ngicp_t* h, const double* in, size_t n) {
   return guarded(h, [&] { set_covs(h, h->src, h->src_covs, in, n, "source"); });
 }
 int ngicp_set_target_covs(ngicp_t* h, const double* in, size_t n) {
-  return guarded(h, [&] { set_covs(h, h->tgt, h->tgt_covs, in, n, "target"); });
+  return guarded(h, [&] {
+    drop_voxel_map(h);
+    set_covs(h, h->tgt, h->tgt_covs, in, n, "target");
+  });
 }
 
 int ngicp_align(ngicp_t* h, const float guess[16], float T_out[16], int* converged, int* nr_iterations, double final_hessian[36], float* aligned, size_t out_stride_bytes) {
   int rc = guarded(h, [&] {
     const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     if (aligned && (out_stride_bytes < 12 || out_stride_bytes % 4)) throw ArgError{NGICP_ERR_ARG, "bad out_stride_bytes"};
-    do_align(h, guess ? guess : I, aligned, out_stride_bytes);
+    if (h->voxel_res > 0.0) do_align_voxel(h, guess ? guess : I, aligned, out_stride_bytes);
+    else do_align(h, guess ? guess : I, aligned, out_stride_bytes);
   });
   if (h) {
     if (T_out) std::memcpy(T_out, h->final_T, sizeof(h->final_T));
@@ -1999,6 +2247,7 @@ int ngicp_align(ngicp_t* h, const float guess[16], float T_out[16], int* converg
 
 int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_align_batch");
     if (n_guesses == 0) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: n_guesses is 0"};
     if (n_guesses > (size_t)NGICP_BATCH_MAX_LANES) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: more than NGICP_BATCH_MAX_LANES (64) guesses in one call"};
     if (!guesses) throw ArgError{NGICP_ERR_ARG, "ngicp_align_batch: null guesses"};
@@ -2060,12 +2309,21 @@ int ngicp_linearize(ngicp_t* h, const double T[16], double H[36], double b[6], d
   return guarded(h, [&] {
     if (!T) throw ArgError{NGICP_ERR_ARG, "null pose"};
     LoopCtx c;
-    prepare_loop(h, c);
+    VoxelCtx vc;
+    const bool vox = h->voxel_res > 0.0;
+    if (vox) prepare_voxel_loop(h, vc);
+    else prepare_loop(h, c);
     LmState st;
     init_state_from_pose(st, pose_from_colmajor_d(T));
     HIP_TRY(hipMemcpyAsync(h->state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+    if (vox) {
+      vc.pa.mode = 2 | 4;
+      hipLaunchKernelGGL(k_vgicp_pass, dim3((unsigned)vc.nblocks), dim3(kVoxBlock), 0, h->stream, vc.pa);
+      c.sa = vc.sa;
+    } else {
       c.pa.mode = 2 | 4;
-    launch_pass(h, c.pa, c.nblocks, h->stream);
+      launch_pass(h, c.pa, c.nblocks, h->stream);
+    }
     c.sa.mode = 1;
     hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, c.sa);
     HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
@@ -2085,7 +2343,10 @@ int ngicp_compute_error(ngicp_t* h, const double T[16], double* err) {
     if (!T) throw ArgError{NGICP_ERR_ARG, "null pose"};
     if (h->hook_valid != 1) throw ArgError{NGICP_ERR_STATE, "compute_error needs a preceding linearize"};
     LoopCtx c;
-    prepare_loop(h, c);
+    VoxelCtx vc;
+    const bool vox = h->voxel_res > 0.0;
+    if (vox) prepare_voxel_loop(h, vc);
+    else prepare_loop(h, c);
     // keep cur / have_lin, replace the trial pose (read in stream order: behind everything this handle has enqueued)
     LmState st;
     HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
@@ -2097,8 +2358,14 @@ int ngicp_compute_error(ngicp_t* h, const double T[16], double* err) {
       st.xi_f[r * 4 + 3] = (float)x.t[r];
     }
     HIP_TRY(hipMemcpyAsync(h->state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
-    c.pa.mode = 1 | 4;
-    launch_pass(h, c.pa, c.nblocks, h->stream);
+    if (vox) {
+      vc.pa.mode = 1 | 4;
+      hipLaunchKernelGGL(k_vgicp_pass, dim3((unsigned)vc.nblocks), dim3(kVoxBlock), 0, h->stream, vc.pa);
+      c.sa = vc.sa;
+    } else {
+      c.pa.mode = 1 | 4;
+      launch_pass(h, c.pa, c.nblocks, h->stream);
+    }
     c.sa.mode = 2;
     hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, c.sa);
     LmState st2;
@@ -2122,12 +2389,60 @@ int ngicp_get_correspondences(ngicp_t* h, int* corr_out, float* sqd_out) {
     h->knn_idx.ensure(n * sizeof(int));
     h->knn_d2.ensure(n * sizeof(float));
     LmState* dst = h->state.as<LmState>();
+    if (h->voxel_res > 0.0)  // voxel numbers; distances to (float)mean_v
+      hipLaunchKernelGGL(k_voxel_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->vox_corr[st.hot.cur].as<int>(), h->src.dev->pts(), (int)n,
+                         (const double*)h->vmap.rec.as<double>(), h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
+    else
     hipLaunchKernelGGL(k_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->tpt[st.hot.cur].as<float4>(), h->src.dev->qpts.as<float4>(),
                        h->src.dev->pts(), h->tgt.dev->pts(), (int)n, h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
     HIP_TRY(hipMemcpyAsync(corr_out, h->knn_idx.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (sqd_out) HIP_TRY(hipMemcpyAsync(sqd_out, h->knn_d2.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipGetLastError());
+  });
+}
+
+int ngicp_set_voxel_resolution(ngicp_t* h, double res) {
+  return guarded(h, [&] {
+    if (!std::isfinite(res) || res < 0.0) throw ArgError{NGICP_ERR_ARG, "voxel resolution must be finite and >= 0 (0 selects exact GICP)"};
+    if (res > 0.0 && !((float)res > 0.f && std::isfinite((float)res) && std::isfinite(1.0f / (float)res)))
+      throw ArgError{NGICP_ERR_ARG, "voxel resolution: neither it nor its inverse may leave the float range"};
+    if (res == h->voxel_res) return;
+    h->voxel_res = res;
+    h->vmap.invalidate();  // (rebuilt at the next use; with res == 0 its memory stays with the handle, its holds on the target are dropped)
+    h->hook_valid = 0;     // correspondences of the other mode, or voxel numbers of another lattice
+  });
+}
+
+int ngicp_voxelmap_size(ngicp_t* h, size_t* n_voxels) {
+  return guarded(h, [&] {
+    if (!n_voxels) throw ArgError{NGICP_ERR_ARG, "null output"};
+    if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "no voxel resolution set (ngicp_set_voxel_resolution)"};
+    ensure_voxel_map(h);
+    *n_voxels = h->vmap.n_vox;
+  });
+}
+
+int ngicp_voxelmap_get(ngicp_t* h, int* ijk_n3, double* mean_n3, double* cov_n6, int* count_n) {
+  return guarded(h, [&] {
+    if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "no voxel resolution set (ngicp_set_voxel_resolution)"};
+    ensure_voxel_map(h);
+    const size_t nv = h->vmap.n_vox;
+    std::vector<double> rec(nv * kVoxRec);
+    std::vector<unsigned long long> keys(nv);
+    HIP_TRY(hipMemcpyAsync(rec.data(), h->vmap.rec.p, rec.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(keys.data(), h->vmap.vkeys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t v = 0; v < nv; ++v) {
+      if (ijk_n3) {
+        ijk_n3[3 * v + 0] = (int)(keys[v] & 0x1fffffull) - kVoxBias;
+        ijk_n3[3 * v + 1] = (int)((keys[v] >> 21) & 0x1fffffull) - kVoxBias;
+        ijk_n3[3 * v + 2] = (int)((keys[v] >> 42) & 0x1fffffull) - kVoxBias;
+      }
+      if (mean_n3) std::memcpy(mean_n3 + 3 * v, &rec[v * kVoxRec], 3 * sizeof(double));
+      if (cov_n6) std::memcpy(cov_n6 + 6 * v, &rec[v * kVoxRec + 3], 6 * sizeof(double));
+      if (count_n) count_n[v] = (int)rec[v * kVoxRec + 9];
+    }
   });
 }
 
@@ -2312,6 +2627,7 @@ int ngicp_set_profiling(ngicp_t* h, int on) {
 int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
   return guarded(h, [&] {
     const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    refuse_if_voxelized(h, "ngicp_sharded_begin");
     h->shard_ctx.reset(new LoopCtx);
     LoopCtx& c = *h->shard_ctx;
     prepare_loop(h, c);
@@ -2332,6 +2648,7 @@ int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
 
 int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_sharded_pass");
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -2348,6 +2665,7 @@ int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
 
 int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_null, int* done) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_sharded_step");
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -2377,6 +2695,7 @@ int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_nul
 
 int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_iterations, double final_hessian[36]) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_sharded_finish");
     if (!h->sharded_active) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     hipStream_t s = h->shard_stream ? h->shard_stream : h->stream;  // the steps were enqueued there
     HIP_TRY(hipMemcpyAsync(&h->pin_state[1], h->state.p, sizeof(LmState), hipMemcpyDeviceToHost, s));
@@ -2401,6 +2720,7 @@ int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_it
 // ---- K1 sharded over ranks: every rank computes a block of the packed covariance array, the caller all-gathers ----
 int ngicp_covs_shard_begin(ngicp_t* h, int which, double** covs6_dev, size_t* n_points) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_covs_shard_begin");
     if ((which != 0 && which != 1) || !covs6_dev || !n_points) throw ArgError{NGICP_ERR_ARG, "bad argument"};
     Slot& slot = which ? h->tgt : h->src;
     ensure_slot_ready(h, slot, which ? "target" : "source");
@@ -2415,6 +2735,7 @@ int ngicp_covs_shard_begin(ngicp_t* h, int which, double** covs6_dev, size_t* n_
 }
 int ngicp_covs_shard_compute(ngicp_t* h, int which, size_t lo, size_t hi, void* stream_or_null) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_covs_shard_compute");
     if (which != 0 && which != 1) throw ArgError{NGICP_ERR_ARG, "bad argument"};
     CovSet& cs = h->shard_covs[which];
     Slot& slot = which ? h->tgt : h->src;
@@ -2426,6 +2747,7 @@ int ngicp_covs_shard_compute(ngicp_t* h, int which, size_t lo, size_t hi, void* 
 }
 int ngicp_covs_shard_commit(ngicp_t* h, int which) {
   return guarded(h, [&] {
+    refuse_if_voxelized(h, "ngicp_covs_shard_commit");
     if (which != 0 && which != 1) throw ArgError{NGICP_ERR_ARG, "bad argument"};
     CovSet& cs = h->shard_covs[which];
     Slot& slot = which ? h->tgt : h->src;
@@ -2617,6 +2939,7 @@ int ngicp_submap_set(ngicp_t* h, const int* ids, size_t n_ids, int* changed_out)
     h->tgt_covs.order = dc;
     h->submap_ids.assign(ids, ids + n_ids);
     h->submap_cloud = dc.get();
+    drop_voxel_map(h);
     h->hook_valid = 0;
     h->stats.submap_ms = now_ms() - t0;
     if (changed_out) *changed_out = 1;

@@ -217,7 +217,8 @@ __global__ void __launch_bounds__(256) k_voxel_keys(const float4* __restrict__ p
   vals[i] = i;
 }
 
-// ---- stable LSD radix sort of (voxel index, point index) pairs, 11 bits per pass, written out here (round 2 called hipCUB) ----
+// ---- stable LSD radix sort of (key, point index) pairs, 11 bits per pass, written out here (round 2 called hipCUB) ----
+// Key: the 32-bit voxel index of the filters, or the 63-bit (iz, iy, ix) voxel key of the voxelized-GICP map (ngk_sort_pairs_u64).
 // A WAVE owns a tile of kRadixTile consecutive elements and walks it in order, 64 at a time.  Pass structure: (1) per-wave digit
 // histogram -> hist[digit][wave]; (2) exclusive scan over hist in that (digit-major) order = where every wave's elements of every
 // digit go; (3) the same walk again: inside a step a lane's rank among the lanes with its digit comes from ballots (one per digit bit:
@@ -225,7 +226,8 @@ __global__ void __launch_bounds__(256) k_voxel_keys(const float4* __restrict__ p
 // order, then lane order = input order: stable.  A pass whose bits are all above the highest bit in use copies.
 constexpr int kRadixBits = 11, kRadixBins = 1 << kRadixBits, kRadixTile = 1024;
 
-__global__ void __launch_bounds__(256) k_radix_hist(const unsigned int* __restrict__ keys, const FilterState* __restrict__ st, int shift, int nwaves, int* __restrict__ hist) {
+template <class KeyT>
+__global__ void __launch_bounds__(256) k_radix_hist(const KeyT* __restrict__ keys, const FilterState* __restrict__ st, int shift, int nwaves, int* __restrict__ hist) {
   __shared__ int h[4][kRadixBins];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, gw = blockIdx.x * 4 + wave;
   if (shift >= st->bits || st->overflow) return;  // (block-uniform)
@@ -237,7 +239,7 @@ __global__ void __launch_bounds__(256) k_radix_hist(const unsigned int* __restri
   if (gw < nwaves)
     for (int o = lane; o < kRadixTile; o += 64) {
       const int i = base + o;
-      if (i < n) atomicAdd(&h[wave][(keys[i] >> shift) & (kRadixBins - 1)], 1);
+      if (i < n) atomicAdd(&h[wave][(int)((keys[i] >> shift) & (KeyT)(kRadixBins - 1))], 1);
     }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -246,8 +248,9 @@ __global__ void __launch_bounds__(256) k_radix_hist(const unsigned int* __restri
     for (int b = lane; b < kRadixBins; b += 64) hist[(size_t)b * nwaves + gw] = h[wave][b];
 }
 
-__global__ void __launch_bounds__(256) k_radix_scatter(const unsigned int* __restrict__ keys, const int* __restrict__ vals, const FilterState* __restrict__ st, int shift, int nwaves,
-                                                        const int* __restrict__ offs, unsigned int* __restrict__ keys_out, int* __restrict__ vals_out) {
+template <class KeyT>
+__global__ void __launch_bounds__(256) k_radix_scatter(const KeyT* __restrict__ keys, const int* __restrict__ vals, const FilterState* __restrict__ st, int shift, int nwaves,
+                                                        const int* __restrict__ offs, KeyT* __restrict__ keys_out, int* __restrict__ vals_out) {
   __shared__ int run[4][kRadixBins];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, gw = blockIdx.x * 4 + wave;
   if (gw >= nwaves || st->overflow) return;  // (wave-uniform; no block-level synchronisation below)
@@ -270,9 +273,9 @@ __global__ void __launch_bounds__(256) k_radix_scatter(const unsigned int* __res
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const int i = base + o + lane;
     const bool valid = i < n;
-    const unsigned int key = valid ? keys[i] : 0u;
+    const KeyT key = valid ? keys[i] : (KeyT)0;
     const int val = valid ? vals[i] : 0;
-    const int d = (int)((key >> shift) & (kRadixBins - 1));
+    const int d = (int)((key >> shift) & (KeyT)(kRadixBins - 1));
     unsigned long long m = __ballot(valid);  // the lanes that share this lane's digit
 #pragma unroll
     for (int bit = 0; bit < kRadixBits; ++bit) {
@@ -386,9 +389,9 @@ static int filter_cloud_impl(hipStream_t s, FilterWorkspace* ws, const float4* i
     const int passes = (ws->last_bits > 0 && !force_all_passes) ? std::min(3, (ws->last_bits + kRadixBits - 1) / kRadixBits) : 3;
     passes_run = passes;
     for (int pass = 0; pass < passes; ++pass) {
-      hipLaunchKernelGGL(k_radix_hist, dim3(rblocks), dim3(256), 0, s, (const unsigned int*)keys_a, (const FilterState*)st, pass * kRadixBits, nwaves, hist);
+      hipLaunchKernelGGL(k_radix_hist<unsigned int>, dim3(rblocks), dim3(256), 0, s, (const unsigned int*)keys_a, (const FilterState*)st, pass * kRadixBits, nwaves, hist);
       if (exclusive_scan(s, ws, hist, (int)hist_entries, hoffs, err, errlen)) return -1;
-      hipLaunchKernelGGL(k_radix_scatter, dim3(rblocks), dim3(256), 0, s, (const unsigned int*)keys_a, (const int*)vals_a, (const FilterState*)st, pass * kRadixBits, nwaves,
+      hipLaunchKernelGGL(k_radix_scatter<unsigned int>, dim3(rblocks), dim3(256), 0, s, (const unsigned int*)keys_a, (const int*)vals_a, (const FilterState*)st, pass * kRadixBits, nwaves,
                          (const int*)hoffs, keys_b, vals_b);
       std::swap(keys_a, keys_b);
       std::swap(vals_a, vals_b);
@@ -426,6 +429,43 @@ static int filter_cloud_impl(hipStream_t s, FilterWorkspace* ws, const float4* i
 extern "C" int ngk_filter_cloud(hipStream_t s, FilterWorkspace* ws, const float4* in_dev, int n, int remove_nan, float crop_half, float leaf, const float4** out_dev,
                                 int* n_out, char* err, size_t errlen) {
   return filter_cloud_impl(s, ws, in_dev, n, remove_nan, crop_half, leaf, out_dev, n_out, err, errlen, false);
+}
+
+// the sort's own record for a caller that brings its keys: n pairs, `bits` significant key bits
+__global__ void k_sort_state(FilterState* __restrict__ st, int n, int bits) {
+  FilterState r{};
+  r.n_surv = n;
+  r.bits = bits;
+  *st = r;
+}
+
+// The radix sort above on 64-bit keys (the voxelized-GICP map, ngicp_voxel.h): ceil(bits / 11) stable passes between the caller's two
+// (key, value) buffers.  *sorted_in_a = 1 when the result is back in the first pair.  Nothing is synchronised.
+extern "C" int ngk_sort_pairs_u64(hipStream_t s, FilterWorkspace* ws, unsigned long long* keys_a, unsigned long long* keys_b, int* vals_a, int* vals_b, int n, int bits,
+                                  int* sorted_in_a, char* err, size_t errlen) {
+  *sorted_in_a = 1;
+  if (n <= 0) return 0;
+  const int nwaves = (n + kRadixTile - 1) / kRadixTile, rblocks = (nwaves + 3) / 4;
+  const size_t hist_entries = (size_t)kRadixBins * nwaves;
+  if (ensure(ws, 7, (hist_entries / kScanTile + 2) * sizeof(int), err, errlen) || ensure(ws, 3, sizeof(FilterState) + 64, err, errlen) ||
+      ensure(ws, 5, (hist_entries + 1 + kCellPad) * sizeof(int) * 2, err, errlen))
+    return -1;
+  FilterState* st = reinterpret_cast<FilterState*>(ws->buf[3]);
+  int* hist = reinterpret_cast<int*>(ws->buf[5]);
+  int* hoffs = hist + hist_entries;
+  hipLaunchKernelGGL(k_sort_state, dim3(1), dim3(1), 0, s, st, n, bits);
+  const int passes = (bits + kRadixBits - 1) / kRadixBits;
+  for (int pass = 0; pass < passes; ++pass) {
+    hipLaunchKernelGGL(k_radix_hist<unsigned long long>, dim3(rblocks), dim3(256), 0, s, (const unsigned long long*)keys_a, (const FilterState*)st, pass * kRadixBits, nwaves, hist);
+    if (exclusive_scan(s, ws, hist, (int)hist_entries, hoffs, err, errlen)) return -1;
+    hipLaunchKernelGGL(k_radix_scatter<unsigned long long>, dim3(rblocks), dim3(256), 0, s, (const unsigned long long*)keys_a, (const int*)vals_a, (const FilterState*)st,
+                       pass * kRadixBits, nwaves, (const int*)hoffs, keys_b, vals_b);
+    std::swap(keys_a, keys_b);
+    std::swap(vals_a, vals_b);
+    *sorted_in_a ^= 1;
+  }
+  FLT_TRY(hipGetLastError());
+  return 0;
 }
 
 extern "C" void ngk_filter_free(FilterWorkspace* ws) {

@@ -1,0 +1,307 @@
+// Voxelized GICP: the target reduced once to one Gaussian per occupied voxel, and a pass that finds a source point's
+// correspondence with one table lookup instead of an exact 1-NN search.  The project's own definition (include/ngicp.h, "voxelized
+// GICP"); no bit-fidelity to any outside library is claimed.
+//
+//   voxel of a float point p      ijk = floorf(p * inv_res) per axis, inv_res = 1.0f / (float)resolution: one float multiply, nothing
+//                                 fused (the library is built with -ffp-contract=off), then floorf.  |i| >= 2^20 on any axis: no voxel
+//                                 (a target with such a point is refused, a source point there has no correspondence), so that the
+//                                 63-bit key (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20) orders the voxels by (iz, iy, ix).
+//   voxel map of the target       per occupied voxel v, all sums in ascending ORIGINAL target index: n_v, mean_v = (sum (double)p_j) / n_v,
+//                                 cov_v = (sum C_j) / n_v.  Voxels are numbered in ascending key.  Build: keys in original order ->
+//                                 the filters' stable LSD radix sort (ngk_sort_pairs_u64) -> segment heads -> exclusive scan -> one
+//                                 thread per voxel adds its segment in order.  Nothing depends on the order in which threads arrive.
+//   lookup                        an open-addressing hash table (linear probing, load <= 1/2) from key to voxel number.  Every key is
+//                                 inserted once, so WHERE a key lands depends on the order of arrival but WHAT a lookup returns does
+//                                 not.  One 16-byte load per probe (about 1.5 probes per hit at this load in theory; not yet
+//                                 measured), against the log2(100k) ~ 17 dependent loads of a binary search over 100k sorted keys.
+//   k_vgicp_pass                  k_gicp_pass's role in the two-launch loop with the same mode bits (bit 0: error of the trial pose under
+//                                 the previous pass's correspondences, bit 1: lookup + linearisation at the trial pose, bit 2: ignore
+//                                 `done`), DIRECT1 rule: the source point at the float pose, q = ((c0 x + c1 y) + c2 z) + c3, corresponds
+//                                 to the voxel of q if that voxel is occupied.  max_correspondence_distance is not consulted.
+//                                 Terms (FP64): e = mean_v - T a, M = (cov_v + R C_a R^T)^-1; the matrix stored and used is n_v M, so the
+//                                 tail and k_lm_solve are the exact path's.  A block takes 256 consecutive source points in the index's
+//                                 sorted order and writes one row of 32 sums, reduced in a fixed order.
+#pragma once
+#include "ngicp_pass.h"
+
+namespace ngk {
+
+constexpr int kVoxBias = 1 << 20;       // |i| < 2^20 per axis
+constexpr int kVoxKeyBits = 63;
+constexpr unsigned long long kVoxEmpty = ~0ull;  // (no key has bit 63)
+constexpr int kVoxBlock = 256;          // source points per block of k_vgicp_pass
+constexpr int kVoxRec = 10;             // doubles per voxel record: mean 3, covariance {xx, xy, xz, yy, yz, zz}, count
+
+__device__ __forceinline__ bool voxel_key(float x, float y, float z, float inv_res, unsigned long long& key) {
+  const float fx = floorf(x * inv_res), fy = floorf(y * inv_res), fz = floorf(z * inv_res);
+  const float lim = 1048576.f;
+  if (!(fx > -lim && fx < lim && fy > -lim && fy < lim && fz > -lim && fz < lim)) return false;  // (a NaN coordinate ends here too)
+  key = ((unsigned long long)((int)fz + kVoxBias) << 42) | ((unsigned long long)((int)fy + kVoxBias) << 21) | (unsigned long long)((int)fx + kVoxBias);
+  return true;
+}
+
+__device__ __forceinline__ unsigned int voxel_hash(unsigned long long k, unsigned int mask) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return (unsigned int)k & mask;
+}
+
+// voxel number of `key`, or -1.  The table always has empty slots (load <= 1/2): the probe sequence ends.
+__device__ __forceinline__ int voxel_lookup(const ulonglong2* __restrict__ table, unsigned int mask, unsigned long long key, unsigned int& probes) {
+  unsigned int slot = voxel_hash(key, mask);
+  for (unsigned int t = 0; t <= mask; ++t) {
+    const ulonglong2 e = table[slot];
+    ++probes;
+    if (e.x == key) return (int)e.y;
+    if (e.x == kVoxEmpty) return -1;
+    slot = (slot + 1) & mask;
+  }
+  return -1;
+}
+
+// keys[o] / vals[o] for ORIGINAL target index o (the sort is stable: a voxel's points stay in ascending original index); vals = the
+// point's position in the cell-sorted cloud, where its coordinates and covariance are.  *bad != 0: a point without a voxel.
+__global__ void __launch_bounds__(256) k_voxel_map_keys(const float4* __restrict__ pts, int n, float inv_res, unsigned long long* __restrict__ keys, int* __restrict__ vals,
+                                                         int* __restrict__ bad) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const float4 p = pts[s];
+  const int o = __float_as_int(p.w);
+  unsigned long long key = 0;
+  if (!voxel_key(p.x, p.y, p.z, inv_res, key)) atomicOr(bad, 1);
+  keys[o] = key;
+  vals[o] = s;
+}
+
+__global__ void __launch_bounds__(256) k_voxel_map_heads(const unsigned long long* __restrict__ keys, int n, int* __restrict__ head) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  head[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1 : 0;
+}
+
+// seg_start[v] = first sorted position of voxel v (vox_of: the exclusive prefix of head, n + 1 entries); seg_start[n_vox] = n
+__global__ void __launch_bounds__(256) k_voxel_map_starts(const int* __restrict__ head, const int* __restrict__ vox_of, int n, int* __restrict__ seg_start) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  if (head[j]) seg_start[vox_of[j]] = j;
+  if (j == n - 1) seg_start[vox_of[n]] = n;
+}
+
+// one thread per voxel: its record (sums in segment order = ascending original index), its key, its entry in the hash table
+__global__ void __launch_bounds__(256) k_voxel_map_fill(const unsigned long long* __restrict__ keys, const int* __restrict__ order, const int* __restrict__ seg_start, int n_vox,
+                                                         const float4* __restrict__ pts, const double* __restrict__ covs, double* __restrict__ rec,
+                                                         unsigned long long* __restrict__ vkeys, ulonglong2* __restrict__ table, unsigned int mask) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_vox) return;
+  const int s = seg_start[v], e = seg_start[v + 1];
+  double m[3] = {0.0, 0.0, 0.0}, c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = s; j < e; ++j) {
+    const int p = order[j];
+    const float4 q = pts[p];
+    m[0] += (double)q.x;
+    m[1] += (double)q.y;
+    m[2] += (double)q.z;
+    const double* C = covs + (size_t)p * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] += C[k];
+  }
+  const double cnt = (double)(e - s);
+  double* r = rec + (size_t)v * kVoxRec;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) r[k] = m[k] / cnt;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) r[3 + k] = c[k] / cnt;
+  r[9] = cnt;
+  const unsigned long long key = keys[s];
+  vkeys[v] = key;
+  unsigned int slot = voxel_hash(key, mask);
+  for (unsigned int t = 0; t <= mask; ++t) {  // (keys are distinct and the table is at most half full: a free slot comes)
+    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(&table[slot]), kVoxEmpty, key);
+    if (prev == kVoxEmpty) {
+      table[slot].y = (unsigned long long)v;
+      break;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+struct VoxelPassArgs {
+  const float4* src;        // source points in the index's sorted order, w = original index
+  const double* cov_src;    // [n_src][6], the same order
+  int n_src;
+  const ulonglong2* table;  // {key, voxel number}; kVoxEmpty in free slots
+  unsigned int mask;
+  const double* rec;        // [n_vox][kVoxRec]
+  int n_vox;
+  float inv_res;
+  int* corr[2];             // [n_src] voxel number or -1 (ping-pong halves, as PassArgs::tpt)
+  double* mahal[2];         // [n_src][6] n_v (cov_v + R C_a R^T)^-1
+  LmState* st;
+  double* partials;         // [blocks][kNumSlots]
+  int mode;                 // bit0: error part, bit1: linearise part, bit2: ignore st->done (test hooks)
+  unsigned long long* t_first;  // device word: stamped by the first pass of an alignment (block 0), or null
+};
+
+__global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
+  __shared__ double red[4][16 * 30];
+  __shared__ double lds[4][kNumSlots];
+  __shared__ unsigned int cnt[4][2][64];
+  const LmState* __restrict__ st = a.st;
+  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
+  const int cur = st->hot.cur, nxt = cur ^ 1;
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
+  float Tf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
+  if (!(a.mode & 4) && done_now) return;
+  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+
+  const bool do_err = (a.mode & 1) && have_lin_now;
+  const bool do_lin = (a.mode & 2);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * kVoxBlock + threadIdx.x;
+  const bool mine = i < a.n_src;
+
+  double acc[kNumSums];
+#pragma unroll
+  for (int v = 0; v < kNumSums; ++v) acc[v] = 0.0;
+  unsigned int nprobes = 0, nvalid = 0;
+  if (mine) {
+    const float4 sp = a.src[i];
+    const double ax = (double)sp.x, ay = (double)sp.y, az = (double)sp.z;
+    const double tax = R[0] * ax + R[1] * ay + R[2] * az + t[0];  // T * a in FP64, as the exact pass
+    const double tay = R[3] * ax + R[4] * ay + R[5] * az + t[1];
+    const double taz = R[6] * ax + R[7] * ay + R[8] * az + t[2];
+    if (do_err) {  // error of the trial pose under the previous pass's correspondences
+      const int v_old = a.corr[cur][i];
+      if ((unsigned int)v_old < (unsigned int)a.n_vox) {  // (-1: none)
+        const double* mv = a.rec + (size_t)v_old * kVoxRec;
+        const double* M = a.mahal[cur] + (size_t)i * 6;
+        const double ex = mv[0] - tax, ey = mv[1] - tay, ez = mv[2] - taz;
+        const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+        const double mex = m00 * ex + m01 * ey + m02 * ez;
+        const double mey = m01 * ex + m11 * ey + m12 * ez;
+        const double mez = m02 * ex + m12 * ey + m22 * ez;
+        acc[28] += ex * mex + ey * mey + ez * mez;
+      }
+    }
+    if (do_lin) {
+      // the float pose times the point, in the exact pass's order: ((c0*x + c1*y) + c2*z) + c3
+      const float qx = ((Tf[0] * sp.x + Tf[1] * sp.y) + Tf[2] * sp.z) + Tf[3];
+      const float qy = ((Tf[4] * sp.x + Tf[5] * sp.y) + Tf[6] * sp.z) + Tf[7];
+      const float qz = ((Tf[8] * sp.x + Tf[9] * sp.y) + Tf[10] * sp.z) + Tf[11];
+      unsigned long long key = 0;
+      int v = -1;
+      if (voxel_key(qx, qy, qz, a.inv_res, key)) v = voxel_lookup(a.table, a.mask, key, nprobes);
+      a.corr[nxt][i] = v;
+      if (v >= 0) {
+        ++nvalid;
+        const double* rv = a.rec + (size_t)v * kVoxRec;
+        const double* CA = a.cov_src + (size_t)i * 6;
+        double ca[6], rcr[6], M[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) ca[e] = CA[e];
+        const double bx = rv[0], by = rv[1], bz = rv[2], nv = rv[9];
+        rotate_sym(R, ca, rcr);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) rcr[e] = rv[3 + e] + rcr[e];
+        inv3_sym(rcr, M);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) M[e] = nv * M[e];
+        double* Mo = a.mahal[nxt] + (size_t)i * 6;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) Mo[e] = M[e];
+        // residual, Jacobian, normal equations: the exact pass's tail with mean_v for the target point and n_v M for M
+        const double ex = bx - tax, ey = by - tay, ez = bz - taz;
+        const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+        const double mex = m00 * ex + m01 * ey + m02 * ez;
+        const double mey = m01 * ex + m11 * ey + m12 * ez;
+        const double mez = m02 * ex + m12 * ey + m22 * ez;
+        acc[27] += ex * mex + ey * mey + ez * mez;
+        const double A00 = tay * m02 - taz * m01, A10 = taz * m00 - tax * m02, A20 = tax * m01 - tay * m00;
+        const double A01 = tay * m12 - taz * m11, A11 = taz * m01 - tax * m12, A21 = tax * m11 - tay * m01;
+        const double A02 = tay * m22 - taz * m12, A12 = taz * m02 - tax * m22, A22 = tax * m12 - tay * m02;
+        acc[0] += -(A01 * taz - A02 * tay);
+        acc[1] += -(-A00 * taz + A02 * tax);
+        acc[2] += -(A00 * tay - A01 * tax);
+        acc[6] += -(-A10 * taz + A12 * tax);
+        acc[7] += -(A10 * tay - A11 * tax);
+        acc[11] += -(A20 * tay - A21 * tax);
+        acc[3] += A00; acc[4] += A01; acc[5] += A02;
+        acc[8] += A10; acc[9] += A11; acc[10] += A12;
+        acc[12] += A20; acc[13] += A21; acc[14] += A22;
+        acc[15] += m00; acc[16] += m01; acc[17] += m02;
+        acc[18] += m11; acc[19] += m12;
+        acc[20] += m22;
+        acc[21] += mey * taz - mez * tay;
+        acc[22] += mez * tax - mex * taz;
+        acc[23] += mex * tay - mey * tax;
+        acc[24] += -mex;
+        acc[25] += -mey;
+        acc[26] += -mez;
+      }
+    }
+  }
+  // ---- the block's row, in a fixed order: sixteen lanes at a time write a [16][30] tile, lane v adds column v top to bottom (the exact
+  //      pass's R0); then the four waves in order ----
+  {
+    double* rw = red[wave];
+    double out = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      wave_lds_sync();
+      if ((lane >> 4) == q) {
+#pragma unroll
+        for (int v = 0; v < kNumSums; ++v) rw[(lane & 15) * 30 + v] = acc[v];
+      }
+      wave_lds_sync();
+      if (lane < kNumSums)
+        for (int l = 0; l < 16; ++l) out += rw[l * 30 + lane];
+    }
+    cnt[wave][0][lane] = nprobes;
+    cnt[wave][1][lane] = nvalid;
+    wave_lds_sync();
+    if (lane >= kNumSums && lane < kNumSums + 2) {
+      unsigned int sum = 0;
+      for (int l = 0; l < 64; ++l) sum += cnt[wave][lane - kNumSums][l];
+      out = (double)sum;
+    }
+    if (lane < kNumSlots) lds[wave][lane] = lane < kNumSums + 2 ? out : 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < kNumSlots) {
+    const int v = threadIdx.x;
+    a.partials[(size_t)blockIdx.x * kNumSlots + v] = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
+  }
+}
+
+// voxel numbers (and float squared distances to (float)mean_v at the pose of the linearisation) back in ORIGINAL source order
+__global__ void __launch_bounds__(256) k_voxel_corr_to_original(const int* __restrict__ corr, const float4* __restrict__ src, int n, const double* __restrict__ rec,
+                                                                 int* __restrict__ out_corr, float* __restrict__ out_sqd, const float* __restrict__ lin_f) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 sp = src[i];
+  const int o = __float_as_int(sp.w);
+  const int v = corr[i];
+  out_corr[o] = v;
+  if (out_sqd) {
+    float d = __builtin_inff();
+    if (v >= 0) {
+      const float qx = ((lin_f[0] * sp.x + lin_f[1] * sp.y) + lin_f[2] * sp.z) + lin_f[3];
+      const float qy = ((lin_f[4] * sp.x + lin_f[5] * sp.y) + lin_f[6] * sp.z) + lin_f[7];
+      const float qz = ((lin_f[8] * sp.x + lin_f[9] * sp.y) + lin_f[10] * sp.z) + lin_f[11];
+      const double* mv = rec + (size_t)v * kVoxRec;
+      d = sqdist(qx, qy, qz, Xyz{(float)mv[0], (float)mv[1], (float)mv[2]});
+    }
+    out_sqd[o] = d;
+  }
+}
+
+}  // namespace ngk

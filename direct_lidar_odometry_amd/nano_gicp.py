@@ -53,7 +53,8 @@ class Stats(C.Structure):
                 ("outer_iterations", C.c_int), ("lm_trials", C.c_int), ("mean_candidates", C.c_double), ("valid_fraction", C.c_double),
                 ("index_build_ms", C.c_double), ("covariance_ms", C.c_double), ("upload_ms", C.c_double), ("voxel_size", C.c_double),
                 ("grid_dims", C.c_int * 3), ("lanes_per_query", C.c_int), ("passes_timed", C.c_int), ("n_src", C.c_longlong), ("n_tgt", C.c_longlong), ("staged_fraction", C.c_double), ("submap_ms", C.c_double),
-                ("device_allocs", C.c_longlong), ("host_wait_spins", C.c_longlong), ("query_ms", C.c_double)]
+                ("device_allocs", C.c_longlong), ("host_wait_spins", C.c_longlong), ("query_ms", C.c_double),
+                ("voxelmap_ms", C.c_double)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -78,6 +79,7 @@ EXPORTS = [
     "ngicp_knn_search", "ngicp_radius_search", "ngicp_radius_fetch", "ngicp_fitness_score",
     "ngicp_align_batch", "ngicp_batch_get_lm_trace", "ngicp_fitness_score_batch",
     "ngicp_range_select", "ngicp_range_median",
+    "ngicp_set_voxel_resolution", "ngicp_voxelmap_size", "ngicp_voxelmap_get",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -162,6 +164,9 @@ def load_library() -> C.CDLL:
     L.ngicp_map_get.argtypes = [vp, c_f32p, C.c_size_t]
     L.ngicp_map_clear.argtypes = [vp]
     L.ngicp_math_selftest.argtypes = [vp, C.c_int, c_f64p, C.c_size_t, c_f64p]
+    L.ngicp_set_voxel_resolution.argtypes = [vp, C.c_double]
+    L.ngicp_voxelmap_size.argtypes = [vp, C.POINTER(C.c_size_t)]
+    L.ngicp_voxelmap_get.argtypes = [vp, c_i32p, c_f64p, c_f64p, c_i32p]
     _lib = L
     return L
 
@@ -248,6 +253,25 @@ class NanoGICP:
     def setHostWaitMode(self, mode: int):
         """0: the calling thread polls the device without giving its core up (default); 1: it yields between polls."""
         self._ck(self._L.ngicp_set_host_wait(self._h, int(mode)))
+
+    def setVoxelResolution(self, res: float):
+        """res > 0: voxelized GICP - align against one Gaussian per occupied target voxel of edge `res` (include/ngicp.h "voxelized GICP");
+        0 (the default): exact GICP.  In this mode setMaxCorrespondenceDistance is not consulted (voxel membership is the gate),
+        correspondences() returns voxel numbers, and alignBatch / the sharded entries raise."""
+        self._ck(self._L.ngicp_set_voxel_resolution(self._h, float(res)))
+        self._voxel_res = float(res)
+
+    def getVoxelResolution(self) -> float: return getattr(self, "_voxel_res", 0.0)
+
+    def getVoxelMapSize(self) -> int: return self._covs_size("ngicp_voxelmap_size")
+
+    def voxelMap(self):
+        """-> (ijk (V, 3) int32, mean (V, 3), cov (V, 3, 3), count (V,) int32) of the target's voxel map, voxels in ascending (iz, iy, ix)."""
+        n = self.getVoxelMapSize()
+        ijk = np.empty((n, 3), dtype=np.int32); mean = np.empty((n, 3)); c6 = np.empty((n, 6)); cnt = np.empty(n, dtype=np.int32)
+        self._ck(self._L.ngicp_voxelmap_get(self._h, _p(ijk, c_i32p), _p(mean, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p)))
+        cov = c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(n, 3, 3)
+        return ijk, mean, cov, cnt
 
     def setTuning(self, voxel_size: float = 0.0, lanes_per_query: int = 0):
         self._ck(self._L.ngicp_set_tuning(self._h, float(voxel_size), int(lanes_per_query)))

@@ -364,6 +364,21 @@ class NanoGICP {
   }
   ngicp_t* handle() { return h_; }
 
+  // ---- voxelized GICP (no counterpart in the reference; include/ngicp.h "voxelized GICP") ----
+  // setVoxelResolution(res > 0): align() matches every source point against the Gaussian of the target voxel (edge `res`) it falls into -
+  // one table lookup instead of an exact nearest-neighbour search; the voxel map is built on the device at the first align() after the
+  // target, its covariances or the resolution changed.  0 (the default) is exact GICP.  A different algorithm with different results:
+  // setMaxCorrespondenceDistance is not consulted, and alignBatch is not available while it is on.  getVoxelMapSize: occupied voxels.
+  void setVoxelResolution(double res) {
+    if (h_ && check(ngicp_set_voxel_resolution(h_, res), "setVoxelResolution")) voxel_resolution_ = res;
+  }
+  double getVoxelResolution() const { return voxel_resolution_; }
+  size_t getVoxelMapSize() {
+    size_t n = 0;
+    if (h_) check(ngicp_voxelmap_size(h_, &n), "getVoxelMapSize");
+    return n;
+  }
+
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
   // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN
   // after +inf); medianRange: rank n / 2, the reference's median_curr.  which: 0 = the input source, 1 = the target, 2 = the scan
@@ -549,6 +564,7 @@ class NanoGICP {
   types::Matrix6d final_hessian_;
   bool converged_ = false;
   int nr_iterations_ = 0;
+  double voxel_resolution_ = 0.0;
   mutable CovVector cache_src_, cache_tgt_;
 };
 

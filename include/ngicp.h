@@ -181,6 +181,32 @@ int ngicp_fitness_score(ngicp_t* h, const float T_colmajor_or_null[16], double m
  * ngicp_stats.query_ms is the device time of its kernels. */
 int ngicp_range_select(ngicp_t* h, int which, size_t rank, float* value, size_t* n_points_or_null);
 int ngicp_range_median(ngicp_t* h, int which, float* value, size_t* n_points_or_null);
+/* --- voxelized GICP: align against per-voxel target distributions (no counterpart in the reference; csrc/ngicp_voxel.h) ---
+ * A MODE of the handle, selected like the regularisation method: res > 0 selects it, 0 (the default) selects exact GICP; a negative or
+ * non-finite value is NGICP_ERR_ARG.  It is a different algorithm with different results, not a second route to the same answer.  The
+ * definition is this project's own; no bit-fidelity to any outside library is claimed.
+ *   voxel of a float point p   ijk = floorf(p * inv_res) per axis, inv_res = 1.0f / (float)res (one float multiply, nothing fused)
+ *   voxel map of the target    per occupied voxel v, summed in ascending original target index: n_v, mean_v = (sum (double)p_j) / n_v,
+ *                              cov_v = (sum C_j) / n_v over the target covariances (computed, or set through ngicp_set_target_covs / the
+ *                              submap store).  Voxels are numbered in ascending (iz, iy, ix).  Memory is O(occupied voxels).  A target
+ *                              with |i| >= 2^20 on any axis (or a non-finite point) is refused with NGICP_ERR_ARG when the map is built.
+ *                              Built lazily, at the first align / linearize / compute_error / voxelmap call after the target, its
+ *                              covariances or the resolution changed.
+ *   correspondence (DIRECT1)   source point i at pose T: q = float(T) * a_i in float, ((c0 x + c1 y) + c2 z) + c3; it corresponds to the
+ *                              voxel of q if that voxel is occupied, else to nothing.  max_corr_dist is NOT consulted in this mode:
+ *                              voxel membership is the gate.
+ *   terms (FP64)               e = mean_v - T a_i, M = (cov_v + R C_i R^T)^-1: err += n_v e^T M e, H += n_v J^T M J, b += n_v J^T M e.
+ * The loop (LM / GN, lambda schedule, trial passes, convergence test, trace), the final Hessian, the convergence flag and the iteration
+ * count are those of exact GICP.  While the mode is on, ngicp_get_correspondences returns the VOXEL NUMBER (or -1) per source point
+ * and the float squared distance to (float)mean_v (inf without a voxel), and ngicp_align_batch, ngicp_sharded_* and ngicp_covs_shard_*
+ * return NGICP_ERR_ARG ("not available with a voxelized target").  Queries, keyframes, the submap, filters and the range median are
+ * unaffected.  ngicp_stats: mean_candidates counts hash-table slots looked at per source point and pass; voxelmap_ms is the build. */
+int ngicp_set_voxel_resolution(ngicp_t* h, double res);
+/* the number of occupied voxels (builds the map if it is stale; NGICP_ERR_STATE while the mode is off) */
+int ngicp_voxelmap_size(ngicp_t* h, size_t* n_voxels);
+/* the map, voxels in the numbering above: ijk (n x 3 ints), mean (n x 3), cov (n x 6: xx, xy, xz, yy, yz, zz), count (n).  Every
+ * pointer may be NULL.  Builds the map if it is stale. */
+int ngicp_voxelmap_get(ngicp_t* h, int* ijk_n3, double* mean_n3, double* cov_n6, int* count_n);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
@@ -242,6 +268,7 @@ typedef struct ngicp_stats {
                                a frame shows up as a latency outlier: two readings around a call attribute it) */
   long long host_wait_spins; /* polls of the solver's progress word during the last ngicp_align() (busy or yielding, see below) */
   double query_ms;          /* device time (HIP events on the handle's stream) of the kernels of the last knn / radius / fitness / range query */
+  double voxelmap_ms;       /* device time of the last voxel-map build (voxelized GICP) */
 } ngicp_stats;
 int ngicp_get_stats(ngicp_t* h, ngicp_stats* out);
 /* HIP-event timing of the k_gicp_pass launches inside align (two event records per timed launch; off by default).
