@@ -376,6 +376,8 @@ struct ngicp {
 
   // voxelized GICP (ngicp_voxel.h)
   double voxel_res = 0.0;  // ngicp_set_voxel_resolution: > 0 selects the mode
+  int voxel_nbr = NGICP_VOX_DIRECT1;  // ngicp_set_voxel_neighbors: slots per source point (1, 7, 27); remembered while the mode is off
+  long long voxel_builds = 0;         // voxel maps built on this handle (ngicp_voxelmap_builds): only ensure_voxel_map adds to it
   struct VoxelMap {
     bool valid = false;
     double res = 0.0;                    // the resolution it was built with
@@ -393,6 +395,7 @@ struct ngicp {
   } vmap;
   FilterWorkspace vox_ws;                // the radix sort's scratch (its own: a preprocess result lives in fws)
   DevBuf vox_keys, vox_vals, vox_scan, vox_flag, vox_corr[2];
+  DevBuf vox_mahal[2], vox_corr_out;     // DIRECT7 / DIRECT27: [K][n_src][6] n_v M per slot (DIRECT1 uses the exact path's mahal); the n x K export
   hipEvent_t ev_vox_a = nullptr, ev_vox_b = nullptr;
 };
 
@@ -1491,6 +1494,7 @@ void ensure_voxel_map(ngicp* h) {
   m.cloud = h->tgt.dev;
   m.covs = h->tgt_covs.data;
   m.valid = true;
+  ++h->voxel_builds;
 }
 
 struct VoxelCtx {
@@ -1498,6 +1502,17 @@ struct VoxelCtx {
   SolveArgs sa;
   int nblocks;
 };
+
+// the pass of the neighbourhood in c.pa.nbr: k_vgicp_pass for DIRECT1, k_vgicp_pass_n<K> for DIRECT7 / DIRECT27; the same grid
+void launch_voxel_pass(ngicp* h, const VoxelCtx& c, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
+  const dim3 grid((unsigned)c.nblocks), block(kVoxBlock);
+  switch (c.pa.nbr) {
+    case NGICP_VOX_DIRECT1: hipExtLaunchKernelGGL(k_vgicp_pass, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+    case NGICP_VOX_DIRECT7: hipExtLaunchKernelGGL(k_vgicp_pass_n<7>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+    case NGICP_VOX_DIRECT27: hipExtLaunchKernelGGL(k_vgicp_pass_n<27>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+    default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
+  }
+}
 
 // prepare_loop readies the slots, the covariances, the state, the trace and the solver's arguments exactly as for the exact path; the
 // voxelized pass then brings its own grid (256 source points per block), its own rows and correspondence buffers.  The launch order of
@@ -1510,7 +1525,12 @@ void prepare_voxel_loop(ngicp* h, VoxelCtx& v) {
   const size_t n = S.n;
   const int nblocks = std::max(1, (int)((n + kVoxBlock - 1) / kVoxBlock));
   h->partials.ensure((size_t)kNumSlots * nblocks * sizeof(double));
-  for (int i = 0; i < 2; ++i) h->vox_corr[i].ensure(n * sizeof(int));
+  // slot-major state of the neighbourhood in use: corr[2][K][n] ints, and for K > 1 mahal[2][K][n][6] doubles (2 * K * 52 bytes a point)
+  const size_t K = (size_t)h->voxel_nbr;
+  for (int i = 0; i < 2; ++i) {
+    h->vox_corr[i].ensure(K * n * sizeof(int));
+    if (K > 1) h->vox_mahal[i].ensure(K * n * 6 * sizeof(double));
+  }
   VoxelPassArgs& a = v.pa;
   a.src = S.pts();
   a.cov_src = covs_for(h, h->src_covs, h->src.dev);
@@ -1522,8 +1542,10 @@ void prepare_voxel_loop(ngicp* h, VoxelCtx& v) {
   a.inv_res = 1.0f / (float)h->voxel_res;
   for (int i = 0; i < 2; ++i) {
     a.corr[i] = h->vox_corr[i].as<int>();
-    a.mahal[i] = h->mahal[i].as<double>();
+    a.mahal[i] = K > 1 ? h->vox_mahal[i].as<double>() : h->mahal[i].as<double>();
   }
+  a.nbr = (int)K;
+  a.slot_stride = (int)n;
   a.st = h->state.as<LmState>();
   a.partials = h->partials.as<double>();
   a.mode = 3;
@@ -1574,8 +1596,7 @@ void do_align_voxel(ngicp* h, const float guess[16], float* aligned, size_t out_
       continue;
     }
     const bool timed = h->profiling && launched % h->prof_stride == h->prof_stride / 2 && (size_t)(2 * launched + 1) < h->prof_events.size();
-    hipExtLaunchKernelGGL(k_vgicp_pass, dim3((unsigned)c.nblocks), dim3(kVoxBlock), 0, h->stream, timed ? h->prof_events[2 * launched] : nullptr,
-                          timed ? h->prof_events[2 * launched + 1] : nullptr, 0, c.pa);
+    launch_voxel_pass(h, c, timed ? h->prof_events[2 * launched] : nullptr, timed ? h->prof_events[2 * launched + 1] : nullptr);
     hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, c.sa);
     ++launched;
   }
@@ -2318,7 +2339,7 @@ int ngicp_linearize(ngicp_t* h, const double T[16], double H[36], double b[6], d
     HIP_TRY(hipMemcpyAsync(h->state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
     if (vox) {
       vc.pa.mode = 2 | 4;
-      hipLaunchKernelGGL(k_vgicp_pass, dim3((unsigned)vc.nblocks), dim3(kVoxBlock), 0, h->stream, vc.pa);
+      launch_voxel_pass(h, vc);
       c.sa = vc.sa;
     } else {
       c.pa.mode = 2 | 4;
@@ -2360,7 +2381,7 @@ int ngicp_compute_error(ngicp_t* h, const double T[16], double* err) {
     HIP_TRY(hipMemcpyAsync(h->state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
     if (vox) {
       vc.pa.mode = 1 | 4;
-      hipLaunchKernelGGL(k_vgicp_pass, dim3((unsigned)vc.nblocks), dim3(kVoxBlock), 0, h->stream, vc.pa);
+      launch_voxel_pass(h, vc);
       c.sa = vc.sa;
     } else {
       c.pa.mode = 1 | 4;
@@ -2390,7 +2411,8 @@ int ngicp_get_correspondences(ngicp_t* h, int* corr_out, float* sqd_out) {
     h->knn_d2.ensure(n * sizeof(float));
     LmState* dst = h->state.as<LmState>();
     if (h->voxel_res > 0.0)  // voxel numbers; distances to (float)mean_v
-      hipLaunchKernelGGL(k_voxel_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->vox_corr[st.hot.cur].as<int>(), h->src.dev->pts(), (int)n,
+      hipLaunchKernelGGL(k_voxel_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                         (const int*)h->vox_corr[st.hot.cur].as<int>() + (h->voxel_nbr == NGICP_VOX_DIRECT27 ? (size_t)vox_nbr_centre<27>() * n : 0), h->src.dev->pts(), (int)n,
                          (const double*)h->vmap.rec.as<double>(), h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
     else
     hipLaunchKernelGGL(k_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->tpt[st.hot.cur].as<float4>(), h->src.dev->qpts.as<float4>(),
@@ -2412,6 +2434,48 @@ int ngicp_set_voxel_resolution(ngicp_t* h, double res) {
     h->vmap.invalidate();  // (rebuilt at the next use; with res == 0 its memory stays with the handle, its holds on the target are dropped)
     h->hook_valid = 0;     // correspondences of the other mode, or voxel numbers of another lattice
   });
+}
+
+int ngicp_set_voxel_neighbors(ngicp_t* h, int mode) {
+  return guarded(h, [&] {
+    if (mode != NGICP_VOX_DIRECT1 && mode != NGICP_VOX_DIRECT7 && mode != NGICP_VOX_DIRECT27)
+      throw ArgError{NGICP_ERR_ARG, "voxel neighbourhood must be NGICP_VOX_DIRECT1 (1), NGICP_VOX_DIRECT7 (7) or NGICP_VOX_DIRECT27 (27)"};
+    if (mode == h->voxel_nbr) return;
+    h->voxel_nbr = mode;   // (the voxel map does not depend on it and stays)
+    h->hook_valid = 0;     // the per-slot state has another shape: compute_error and the correspondences wait for the next linearisation
+  });
+}
+
+int ngicp_get_voxel_neighbors(const ngicp_t* h, int* mode) {
+  if (!h || !mode) return NGICP_ERR_ARG;
+  *mode = h->voxel_nbr;
+  return NGICP_OK;
+}
+
+int ngicp_voxel_correspondences(ngicp_t* h, int* corr_n_by_K, size_t capacity_ints, int* K_out) {
+  return guarded(h, [&] {
+    if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "no voxel resolution set (ngicp_set_voxel_resolution)"};
+    if (!h->hook_valid) throw ArgError{NGICP_ERR_STATE, "no correspondences: call ngicp_linearize or ngicp_align first"};
+    const size_t n = h->src.dev->n, K = (size_t)h->voxel_nbr;
+    if (K_out) *K_out = (int)K;
+    if (!corr_n_by_K) throw ArgError{NGICP_ERR_ARG, "null output"};
+    if (capacity_ints < n * K) throw ArgError{NGICP_ERR_ARG, "voxel correspondences: the output holds fewer than n_src * K ints"};
+    LmState st;  // (in stream order, as ngicp_get_correspondences)
+    HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->vox_corr_out.ensure(n * K * sizeof(int));
+    hipLaunchKernelGGL(k_voxel_corr_n_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->vox_corr[st.hot.cur].as<int>(), h->src.dev->pts(), (int)n,
+                       (int)K, (int)n, h->vox_corr_out.as<int>());
+    HIP_TRY(hipMemcpyAsync(corr_n_by_K, h->vox_corr_out.p, n * K * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+  });
+}
+
+int ngicp_voxelmap_builds(const ngicp_t* h, long long* n_builds) {
+  if (!h || !n_builds) return NGICP_ERR_ARG;
+  *n_builds = h->voxel_builds;
+  return NGICP_OK;
 }
 
 int ngicp_voxelmap_size(ngicp_t* h, size_t* n_voxels) {

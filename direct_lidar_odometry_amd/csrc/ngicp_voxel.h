@@ -21,6 +21,12 @@
 //                                 Terms (FP64): e = mean_v - T a, M = (cov_v + R C_a R^T)^-1; the matrix stored and used is n_v M, so the
 //                                 tail and k_lm_solve are the exact path's.  A block takes 256 consecutive source points in the index's
 //                                 sorted order and writes one row of 32 sums, reduced in a fixed order.
+//   k_vgicp_pass_n<K>             the same pass for the neighbourhoods DIRECT7 (K = 7) and DIRECT27 (K = 27): slot s of a point whose voxel is
+//                                 c corresponds to voxel c + off[s] if every component stays below 2^20 in magnitude (tested on the
+//                                 integers, before a key is formed) and the voxel is occupied.  A point's terms are added in ascending slot.
+//                                 K = 7: (0,0,0) (+1,0,0) (-1,0,0) (0,+1,0) (0,-1,0) (0,0,+1) (0,0,-1); K = 27: {-1,0,1}^3 in the key's order
+//                                 (dx fastest, dz slowest; the centre is slot 13).  State is slot-major: corr[K][n_src], mahal[K][n_src][6].
+//                                 k_vgicp_pass itself serves DIRECT1 and is not touched by any of this.
 #pragma once
 #include "ngicp_pass.h"
 
@@ -143,6 +149,8 @@ struct VoxelPassArgs {
   double* partials;         // [blocks][kNumSlots]
   int mode;                 // bit0: error part, bit1: linearise part, bit2: ignore st->done (test hooks)
   unsigned long long* t_first;  // device word: stamped by the first pass of an alignment (block 0), or null
+  int nbr;                  // slots per source point (1, 7 or 27); k_vgicp_pass reads neither this nor slot_stride
+  int slot_stride;          // k_vgicp_pass_n: corr / mahal are slot-major, slot s of point i at [s * slot_stride + i]
 };
 
 __global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
@@ -302,6 +310,215 @@ __global__ void __launch_bounds__(256) k_voxel_corr_to_original(const int* __res
     }
     out_sqd[o] = d;
   }
+}
+
+// ---- neighbourhoods (DIRECT7 / DIRECT27) ------------------------------------------------------------------------------------------
+// component `axis` (0: x, 1: y, 2: z) of the offset of slot s
+template <int K>
+__host__ __device__ constexpr int vox_nbr_off(int s, int axis) {
+  static_assert(K == 7 || K == 27, "DIRECT7 or DIRECT27");
+  if (K == 27) return axis == 0 ? s % 3 - 1 : axis == 1 ? (s / 3) % 3 - 1 : s / 9 - 1;
+  if (s == 0) return 0;
+  return (s - 1) / 2 == axis ? (((s - 1) & 1) ? -1 : 1) : 0;  // slots 1..6: +x -x +y -y +z -z
+}
+template <int K>
+__host__ __device__ constexpr int vox_nbr_centre() { return K == 27 ? 13 : 0; }
+
+template <int K>
+__global__ void __launch_bounds__(kVoxBlock, 2) k_vgicp_pass_n(VoxelPassArgs a) {
+  __shared__ double red[4][16 * 30];
+  __shared__ double lds[4][kNumSlots];
+  __shared__ unsigned int cnt[4][2][64];
+  __shared__ int vs[K][kVoxBlock];  // a thread's K voxel numbers between the lookups (unrolled) and the terms (a rolled loop): its own column
+  const LmState* __restrict__ st = a.st;
+  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
+  const int cur = st->hot.cur, nxt = cur ^ 1;
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
+  float Tf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
+  if (!(a.mode & 4) && done_now) return;
+  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+
+  const bool do_err = (a.mode & 1) && have_lin_now;
+  const bool do_lin = (a.mode & 2);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * kVoxBlock + threadIdx.x;
+  const bool mine = i < a.n_src;
+  const size_t stride = (size_t)a.slot_stride;
+
+  double acc[kNumSums];
+#pragma unroll
+  for (int v = 0; v < kNumSums; ++v) acc[v] = 0.0;
+  unsigned int nprobes = 0, nvalid = 0;
+  if (mine) {
+    const float4 sp = a.src[i];
+    const double ax = (double)sp.x, ay = (double)sp.y, az = (double)sp.z;
+    const double tax = R[0] * ax + R[1] * ay + R[2] * az + t[0];  // T * a in FP64, as the exact pass
+    const double tay = R[3] * ax + R[4] * ay + R[5] * az + t[1];
+    const double taz = R[6] * ax + R[7] * ay + R[8] * az + t[2];
+    if (do_err) {  // error of the trial pose under the previous linearisation's voxels and matrices, slot after slot
+      const int* __restrict__ co = a.corr[cur] + i;
+      int vo[K];
+#pragma unroll
+      for (int s = 0; s < K; ++s) vo[s] = co[(size_t)s * stride];
+#pragma unroll
+      for (int s = 0; s < K; ++s) {
+        if ((unsigned int)vo[s] < (unsigned int)a.n_vox) {  // (-1: none)
+          const double* mv = a.rec + (size_t)vo[s] * kVoxRec;
+          const double* M = a.mahal[cur] + ((size_t)s * stride + i) * 6;
+          const double ex = mv[0] - tax, ey = mv[1] - tay, ez = mv[2] - taz;
+          const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+          const double mex = m00 * ex + m01 * ey + m02 * ez;
+          const double mey = m01 * ex + m11 * ey + m12 * ez;
+          const double mez = m02 * ex + m12 * ey + m22 * ez;
+          acc[28] += ex * mex + ey * mey + ez * mez;
+        }
+      }
+    }
+    if (do_lin) {
+      const float qx = ((Tf[0] * sp.x + Tf[1] * sp.y) + Tf[2] * sp.z) + Tf[3];
+      const float qy = ((Tf[4] * sp.x + Tf[5] * sp.y) + Tf[6] * sp.z) + Tf[7];
+      const float qz = ((Tf[8] * sp.x + Tf[9] * sp.y) + Tf[10] * sp.z) + Tf[11];
+      const float fx = floorf(qx * a.inv_res), fy = floorf(qy * a.inv_res), fz = floorf(qz * a.inv_res);
+      const float lim = 1048576.f;
+      const bool centre_ok = fx > -lim && fx < lim && fy > -lim && fy < lim && fz > -lim && fz < lim;  // (false for a NaN coordinate too)
+      int* __restrict__ cn = a.corr[nxt] + i;
+      if (!centre_ok) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) cn[(size_t)s * stride] = -1;
+      } else {
+        const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
+        // ---- the K lookups: every key first, and the first probe of each in flight before any is looked at ----
+        unsigned long long key[K];
+        ulonglong2 first[K];
+        unsigned int in_range = 0;
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+          const int nx = cx + vox_nbr_off<K>(s, 0), ny = cy + vox_nbr_off<K>(s, 1), nz = cz + vox_nbr_off<K>(s, 2);
+          const bool ok = nx > -kVoxBias && nx < kVoxBias && ny > -kVoxBias && ny < kVoxBias && nz > -kVoxBias && nz < kVoxBias;
+          key[s] = ((unsigned long long)(nz + kVoxBias) << 42) | ((unsigned long long)(ny + kVoxBias) << 21) | (unsigned long long)(nx + kVoxBias);
+          in_range |= ok ? (1u << s) : 0u;
+          first[s] = a.table[ok ? voxel_hash(key[s], a.mask) : 0u];  // (a neighbour beyond the range: the load is neither used nor counted)
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+          int v = -1;
+          if (in_range & (1u << s)) {
+            ++nprobes;
+            if (first[s].x == key[s]) {
+              v = (int)first[s].y;
+            } else if (first[s].x != kVoxEmpty) {  // the probe sequence goes on (the table always has empty slots: it ends)
+              unsigned int sl = voxel_hash(key[s], a.mask);  // (rare: hashed again, not kept in a register for every slot)
+              for (unsigned int tt = 1; tt <= a.mask; ++tt) {
+                sl = (sl + 1) & a.mask;
+                const ulonglong2 e = a.table[sl];
+                ++nprobes;
+                if (e.x == key[s]) { v = (int)e.y; break; }
+                if (e.x == kVoxEmpty) break;
+              }
+            }
+          }
+          cn[(size_t)s * stride] = v;
+          vs[s][threadIdx.x] = v;
+        }
+        // ---- the terms, slot after slot; R C_a R^T once per point ----
+        const double* CA = a.cov_src + (size_t)i * 6;
+        double ca[6], rcr[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) ca[e] = CA[e];
+        rotate_sym(R, ca, rcr);
+#pragma unroll 1
+        for (int s = 0; s < K; ++s) {
+          const int v = vs[s][threadIdx.x];
+          if (v < 0) continue;
+          ++nvalid;
+          const double* rv = a.rec + (size_t)v * kVoxRec;
+          double S[6], M[6];
+          const double bx = rv[0], by = rv[1], bz = rv[2], nv = rv[9];
+#pragma unroll
+          for (int e = 0; e < 6; ++e) S[e] = rv[3 + e] + rcr[e];
+          inv3_sym(S, M);
+#pragma unroll
+          for (int e = 0; e < 6; ++e) M[e] = nv * M[e];
+          double* Mo = a.mahal[nxt] + ((size_t)s * stride + i) * 6;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) Mo[e] = M[e];
+          // residual, Jacobian, normal equations: k_vgicp_pass's tail
+          const double ex = bx - tax, ey = by - tay, ez = bz - taz;
+          const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+          const double mex = m00 * ex + m01 * ey + m02 * ez;
+          const double mey = m01 * ex + m11 * ey + m12 * ez;
+          const double mez = m02 * ex + m12 * ey + m22 * ez;
+          acc[27] += ex * mex + ey * mey + ez * mez;
+          const double A00 = tay * m02 - taz * m01, A10 = taz * m00 - tax * m02, A20 = tax * m01 - tay * m00;
+          const double A01 = tay * m12 - taz * m11, A11 = taz * m01 - tax * m12, A21 = tax * m11 - tay * m01;
+          const double A02 = tay * m22 - taz * m12, A12 = taz * m02 - tax * m22, A22 = tax * m12 - tay * m02;
+          acc[0] += -(A01 * taz - A02 * tay);
+          acc[1] += -(-A00 * taz + A02 * tax);
+          acc[2] += -(A00 * tay - A01 * tax);
+          acc[6] += -(-A10 * taz + A12 * tax);
+          acc[7] += -(A10 * tay - A11 * tax);
+          acc[11] += -(A20 * tay - A21 * tax);
+          acc[3] += A00; acc[4] += A01; acc[5] += A02;
+          acc[8] += A10; acc[9] += A11; acc[10] += A12;
+          acc[12] += A20; acc[13] += A21; acc[14] += A22;
+          acc[15] += m00; acc[16] += m01; acc[17] += m02;
+          acc[18] += m11; acc[19] += m12;
+          acc[20] += m22;
+          acc[21] += mey * taz - mez * tay;
+          acc[22] += mez * tax - mex * taz;
+          acc[23] += mex * tay - mey * tax;
+          acc[24] += -mex;
+          acc[25] += -mey;
+          acc[26] += -mez;
+        }
+      }
+    }
+  }
+  // ---- the block's row, in k_vgicp_pass's fixed order: sixteen lanes at a time through a [16][30] tile, then the four waves ----
+  {
+    double* rw = red[wave];
+    double out = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      wave_lds_sync();
+      if ((lane >> 4) == q) {
+#pragma unroll
+        for (int v = 0; v < kNumSums; ++v) rw[(lane & 15) * 30 + v] = acc[v];
+      }
+      wave_lds_sync();
+      if (lane < kNumSums)
+        for (int l = 0; l < 16; ++l) out += rw[l * 30 + lane];
+    }
+    cnt[wave][0][lane] = nprobes;
+    cnt[wave][1][lane] = nvalid;
+    wave_lds_sync();
+    if (lane >= kNumSums && lane < kNumSums + 2) {
+      unsigned int sum = 0;
+      for (int l = 0; l < 64; ++l) sum += cnt[wave][lane - kNumSums][l];
+      out = (double)sum;
+    }
+    if (lane < kNumSlots) lds[wave][lane] = lane < kNumSums + 2 ? out : 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < kNumSlots) {
+    const int v = threadIdx.x;
+    a.partials[(size_t)blockIdx.x * kNumSlots + v] = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
+  }
+}
+
+// the K voxel numbers of every source point, slot-major in sorted order -> row-major [n][K] in ORIGINAL source order
+__global__ void __launch_bounds__(256) k_voxel_corr_n_to_original(const int* __restrict__ corr, const float4* __restrict__ src, int n, int K, int slot_stride,
+                                                                   int* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int o = __float_as_int(src[i].w);
+  for (int s = 0; s < K; ++s) out[(size_t)o * K + s] = corr[(size_t)s * slot_stride + i];
 }
 
 }  // namespace ngk

@@ -42,6 +42,12 @@ class LSQ_OPTIMIZER_TYPE(enum.IntEnum):  # lsq_registration.hpp:54
     LevenbergMarquardt = 1
 
 
+class NeighborSearchMethod(enum.IntEnum):  # voxelized GICP: voxels a source point is matched against (include/ngicp.h NGICP_VOX_*)
+    DIRECT1 = 1
+    DIRECT7 = 7
+    DIRECT27 = 27
+
+
 class NgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ngicp error {code}: {msg}")
@@ -80,6 +86,7 @@ EXPORTS = [
     "ngicp_align_batch", "ngicp_batch_get_lm_trace", "ngicp_fitness_score_batch",
     "ngicp_range_select", "ngicp_range_median",
     "ngicp_set_voxel_resolution", "ngicp_voxelmap_size", "ngicp_voxelmap_get",
+    "ngicp_set_voxel_neighbors", "ngicp_get_voxel_neighbors", "ngicp_voxel_correspondences", "ngicp_voxelmap_builds",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -167,6 +174,10 @@ def load_library() -> C.CDLL:
     L.ngicp_set_voxel_resolution.argtypes = [vp, C.c_double]
     L.ngicp_voxelmap_size.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.ngicp_voxelmap_get.argtypes = [vp, c_i32p, c_f64p, c_f64p, c_i32p]
+    L.ngicp_set_voxel_neighbors.argtypes = [vp, C.c_int]
+    L.ngicp_get_voxel_neighbors.argtypes = [vp, c_i32p]
+    L.ngicp_voxel_correspondences.argtypes = [vp, c_i32p, C.c_size_t, c_i32p]
+    L.ngicp_voxelmap_builds.argtypes = [vp, C.POINTER(C.c_longlong)]
     _lib = L
     return L
 
@@ -264,6 +275,30 @@ class NanoGICP:
     def getVoxelResolution(self) -> float: return getattr(self, "_voxel_res", 0.0)
 
     def getVoxelMapSize(self) -> int: return self._covs_size("ngicp_voxelmap_size")
+
+    def setNeighborSearchMethod(self, method):
+        """DIRECT1 (default): a source point is matched against the voxel it falls into; DIRECT7: that voxel and its 6 face neighbours;
+        DIRECT27: all 27.  Remembered while the voxel mode is off; a change keeps the voxel map and drops the correspondences."""
+        self._ck(self._L.ngicp_set_voxel_neighbors(self._h, int(method)))
+
+    def getNeighborSearchMethod(self) -> NeighborSearchMethod:
+        m = C.c_int(0)
+        self._ck(self._L.ngicp_get_voxel_neighbors(self._h, C.byref(m)))
+        return NeighborSearchMethod(m.value)
+
+    def voxel_correspondences(self) -> np.ndarray:
+        """-> (n, K) int32: the voxel number of every slot of the last linearisation per source point (original order), -1 where empty."""
+        n, K = self._src.shape[0], int(self.getNeighborSearchMethod())
+        out = np.empty((n, K), dtype=np.int32); k = C.c_int(0)
+        self._ck(self._L.ngicp_voxel_correspondences(self._h, _p(out, c_i32p), out.size, C.byref(k)))
+        assert k.value == K
+        return out
+
+    def voxelMapBuilds(self) -> int:
+        """Voxel maps built on this handle so far (only a build counts)."""
+        b = C.c_longlong(0)
+        self._ck(self._L.ngicp_voxelmap_builds(self._h, C.byref(b)))
+        return b.value
 
     def voxelMap(self):
         """-> (ijk (V, 3) int32, mean (V, 3), cov (V, 3, 3), count (V,) int32) of the target's voxel map, voxels in ascending (iz, iy, ix)."""

@@ -94,6 +94,7 @@ struct SpaciousnessFilter {
 
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };  // gicp/gicp_settings.hpp:47
 enum class LSQ_OPTIMIZER_TYPE { GaussNewton, LevenbergMarquardt };                         // lsq_registration.hpp:54
+enum class NeighborSearchMethod { DIRECT1 = 1, DIRECT7 = 7, DIRECT27 = 27 };                // voxelized GICP (ngicp.h NGICP_VOX_*); no counterpart in the reference
 
 template <typename PointSource, typename PointTarget>
 class NanoGICP {
@@ -377,6 +378,26 @@ class NanoGICP {
     size_t n = 0;
     if (h_) check(ngicp_voxelmap_size(h_, &n), "getVoxelMapSize");
     return n;
+  }
+  // The voxels a source point is matched against: its own (DIRECT1, the default), its own and the 6 face neighbours (DIRECT7), or all 27
+  // (DIRECT27); the terms of the occupied ones are summed.  Remembered while the voxel mode is off.  A change keeps the voxel map.
+  void setNeighborSearchMethod(NeighborSearchMethod m) {
+    if (h_) check(ngicp_set_voxel_neighbors(h_, static_cast<int>(m)), "setNeighborSearchMethod");
+  }
+  NeighborSearchMethod getNeighborSearchMethod() const {
+    int m = NGICP_VOX_DIRECT1;
+    if (h_) check(ngicp_get_voxel_neighbors(h_, &m), "getNeighborSearchMethod");
+    return static_cast<NeighborSearchMethod>(m);
+  }
+  // the voxel numbers of every slot of the last linearisation, row-major n x K in the source's order, -1 where a slot is empty; K is
+  // getNeighborSearchMethod()'s value.  Empty on error (and while the voxel mode is off).
+  std::vector<int> voxelCorrespondences() {
+    std::vector<int> out;
+    if (!h_ || !input_) return out;
+    out.resize(input_->size() * static_cast<size_t>(getNeighborSearchMethod()));
+    int K = 0;
+    if (!check(ngicp_voxel_correspondences(h_, out.data(), out.size(), &K), "voxelCorrespondences")) out.clear();
+    return out;
   }
 
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----

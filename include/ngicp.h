@@ -202,6 +202,37 @@ int ngicp_range_median(ngicp_t* h, int which, float* value, size_t* n_points_or_
  * return NGICP_ERR_ARG ("not available with a voxelized target").  Queries, keyframes, the submap, filters and the range median are
  * unaffected.  ngicp_stats: mean_candidates counts hash-table slots looked at per source point and pass; voxelmap_ms is the build. */
 int ngicp_set_voxel_resolution(ngicp_t* h, double res);
+/* The neighbourhood of the correspondence rule: a fixed, ordered list of K integer voxel offsets (dx, dy, dz).
+ *   NGICP_VOX_DIRECT1  (K = 1, the default)  (0,0,0): the rule above, bit for bit
+ *   NGICP_VOX_DIRECT7  (K = 7)               slot 0 (0,0,0); slots 1-6 (+1,0,0) (-1,0,0) (0,+1,0) (0,-1,0) (0,0,+1) (0,0,-1)
+ *   NGICP_VOX_DIRECT27 (K = 27)              every (dx,dy,dz) in {-1,0,1}^3 in ascending (dz, dy, dx), dx fastest - the order of the voxel
+ *                                            key; the centre is slot 13
+ * Source point i at pose T: c = floorf(q * inv_res) as above.  If c is out of range on any axis (|c| >= 2^20, or q is not finite) the
+ * point has no correspondence in any slot.  Otherwise slot s corresponds to voxel c + off[s] if every component of c + off[s] is below
+ * 2^20 in magnitude (tested on the integers, before any key is formed: nothing carries into the neighbouring key field) and that voxel is
+ * occupied; else slot s is -1.  Every occupied slot contributes the terms above (e = mean_v - T a_i, M = (cov_v + R C_i R^T)^-1, weight
+ * n_v); a point's terms are added in ascending slot, R C_i R^T is formed once per point.  The trial error uses the frozen n_v M and the
+ * voxel of every slot of the previous linearisation.  max_corr_dist remains unconsulted.
+ * ngicp_set_voxel_neighbors: any other value is NGICP_ERR_ARG.  It may be called whether or not the mode is on, and is remembered.
+ * Setting the value already set does nothing.  A change keeps the voxel map (which does not depend on the neighbourhood) and drops the
+ * correspondences and the hooks' state, as a change of resolution does: ngicp_compute_error, ngicp_get_correspondences and
+ * ngicp_voxel_correspondences return NGICP_ERR_STATE until the next linearisation.  Per-slot state on the device: 2 * K * 52 bytes per
+ * source point.  In DIRECT7 / DIRECT27 ngicp_get_correspondences keeps its shape and reports the CENTRE slot's voxel and the float
+ * squared distance to its (float)mean_v.  ngicp_stats keeps its layout; two fields change meaning: mean_candidates counts hash-table
+ * slots looked at per source point and pass over all K lookups, and valid_fraction counts PAIRS (occupied slots) per source point and
+ * pass, so it can exceed 1.  ngicp_align_batch, ngicp_sharded_* and ngicp_covs_shard_* stay refused while the mode is on. */
+#define NGICP_VOX_DIRECT1 1
+#define NGICP_VOX_DIRECT7 7
+#define NGICP_VOX_DIRECT27 27
+int ngicp_set_voxel_neighbors(ngicp_t* h, int mode);
+int ngicp_get_voxel_neighbors(const ngicp_t* h, int* mode);
+/* the voxel numbers of every slot of the last linearisation, row-major n_src x K in original source order, -1 where a slot is empty.
+ * *K_out (may be NULL) is the neighbourhood's K; capacity_ints < n_src * K is NGICP_ERR_ARG (K_out is set first).  Valid when
+ * ngicp_get_correspondences is; NGICP_ERR_STATE while the voxel mode is off. */
+int ngicp_voxel_correspondences(ngicp_t* h, int* corr_n_by_K, size_t capacity_ints, int* K_out);
+/* how many voxel maps this handle has built since it was created: only a build adds to it (a stale map is rebuilt at its next use;
+ * a change of neighbourhood does not make it stale) */
+int ngicp_voxelmap_builds(const ngicp_t* h, long long* n_builds);
 /* the number of occupied voxels (builds the map if it is stale; NGICP_ERR_STATE while the mode is off) */
 int ngicp_voxelmap_size(ngicp_t* h, size_t* n_voxels);
 /* the map, voxels in the numbering above: ijk (n x 3 ints), mean (n x 3), cov (n x 6: xx, xy, xz, yy, yz, zz), count (n).  Every

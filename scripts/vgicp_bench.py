@@ -1,6 +1,6 @@
 """Voxelized GICP (setVoxelResolution) next to exact GICP in the same run, on the same handle, clouds, covariances and settings.
 
-  python scripts/vgicp_bench.py [--workloads c3,c5] [--resolutions 0.5,1.0,2.0] [--reps 30] [--out profiles/vgicp_bench.json]
+  python scripts/vgicp_bench.py [--workloads c3,c5] [--resolutions 0.5,1.0,2.0] [--neighbors 1,7,27] [--reps 30] [--out profiles/vgicp_bench.json]
 one JSON line on stdout (and in --out).  Its us_per_pass are HIP-event times.  Kernel times from the profiler: a run of its own under
   rocprofv3 --kernel-trace --stats --output-format csv -- python scripts/vgicp_bench.py --reps 5
 (k_vgicp_pass against k_gicp_pass in its kernel table, which belongs next to the JSON as profiles/vgicp_kernel_stats.csv; its averages
@@ -14,6 +14,10 @@ transformation epsilon 0.01, the workload's correspondence gate - which the voxe
   align_ms           host-to-host, median and p10..p90 of --reps alignments after 3 warm-ups; the two modes alternate inside one loop
   map_build_ms       device time of the voxel-map build (ngicp_stats.voxelmap_ms), median of --reps rebuilds
   iterations, trials, the final pose's distance from the ground truth (m, rad), the share of source points with a correspondence.
+--neighbors: the neighbourhoods (setNeighborSearchMethod) to run at every resolution, DIRECT1 always among them.  DIRECT1's figures
+stay where they were (resolutions[r]); the others are under resolutions[r]["neighbors"][K] with the same device figures plus
+us_per_pass_vs_direct1, the per-pass time relative to DIRECT1 of the same run, resolution and handle - the figure of interest - and
+valid_fraction there counts pairs per point.  Changing the neighbourhood keeps the voxel map, so no build is timed for them.
 """
 import argparse
 import json
@@ -62,6 +66,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="c3,c5")
     ap.add_argument("--resolutions", default="0.5,1.0,2.0")
+    ap.add_argument("--neighbors", default="1,7,27")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -111,6 +116,22 @@ def main():
                 tv.append((t1 - t0) * 1e3)
                 te.append((t3 - t2) * 1e3)
             v.update(voxels=int(n_vox), map_build_ms=float(np.median(builds)), align=_summ(tv), exact_align_same_loop=_summ(te))
+            v["neighbors"] = {}
+            g.setVoxelResolution(r)
+            for K in [int(k) for k in a.neighbors.split(",") if int(k) != 1]:
+                g.setNeighborSearchMethod(K)
+                for _ in range(3):
+                    g.align(w.guess)
+                vk = _device_figures(g, clouds, w)
+                tk = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    g.align(w.guess)
+                    tk.append((time.perf_counter() - t0) * 1e3)
+                vk.update(align=_summ(tk), us_per_pass_vs_direct1=vk["us_per_pass"] / v["us_per_pass"] if v["us_per_pass"] else None)
+                v["neighbors"][str(K)] = vk
+            g.setNeighborSearchMethod(1)
+            g.setVoxelResolution(0)
             res["resolutions"][str(r)] = v
             print(name, r, json.dumps(v), file=sys.stderr, flush=True)
         print(name, "exact", json.dumps(res["exact"]), file=sys.stderr, flush=True)
