@@ -27,6 +27,7 @@
 #include "ngicp_range.h"
 #include "ngicp_batch.h"
 #include "ngicp_voxel.h"
+#include "ngicp_voxel_batch.h"
 
 using namespace ngk;
 
@@ -260,20 +261,22 @@ struct Params {
   int num_threads = 0;
 };
 
-// Working set of ngicp_align_batch: everything an alignment writes, once per lane, in buffers of its own - the
-// handle's single-alignment state is not touched.  Grow-only, reused from call to call.
+// Working set of ngicp_align_batch and ngicp_voxel_align_batch (4.9): everything an alignment writes, once per lane, in
+// buffers of its own - the handle's single-alignment state is not touched.  Grow-only, reused from call to call.  The two entries share
+// the records, the rows, the traces and the pinned words (one call runs at a time on a handle); each has its own correspondence state.
 struct BatchWs {
-  DevBuf recs;      // the lane records, one upload per call: [cap] LmState images, then [cap] PassArgs, then [cap] SolveArgs
+  DevBuf recs;      // the lane records, one upload per call: [cap] LmState images, then [cap] PassArgs or VoxelPassArgs, then [cap] SolveArgs
   DevBuf tpt, mahal;  // [lanes][2][n_src] float4 / [lanes][2][n_src][6] double
   DevBuf partials, order, cost, far, trace;  // [lanes][groups][32]; [lanes][groups] launch order / cost; [lanes][batches]; [lanes][rows][8]
   DevBuf flags;     // [lanes] x {order flag, ticket, -, -}
+  DevBuf vox_corr, vox_mahal;  // ngicp_voxel_align_batch: [lanes][2][K][n_src] voxel numbers / [lanes][2][K][n_src][6] n_v M (2 * K * 52 bytes a point and lane)
   DevBuf fit_T, fit_part, fit_out;  // ngicp_fitness_score_batch
   unsigned char* pin_recs = nullptr;  // pinned image of `recs` (kBatchMaxLanes lanes)
   int* pin_progress = nullptr;        // pinned [kBatchMaxLanes] x kProgressStride: a lane's {passes done | kProgressDone}
   LmHot* pin_final = nullptr;         // pinned [kBatchMaxLanes]: a lane's state image when it is done
   const void* order_src = nullptr;    // source index / group count / lanes the launch orders on the device were built for
   int order_groups = -1, order_lanes = 0;
-  int lanes = 0;                      // lanes of the last call (ngicp_batch_get_lm_trace)
+  int lanes = 0;                      // lanes of the last call of either entry (ngicp_batch_get_lm_trace)
   size_t trace_stride = 0;            // doubles between two lanes' traces
   std::vector<size_t> trace_rows;     // rows of each lane's trace on the device
   static constexpr int kProgressStride = 16;  // a 64-byte line per lane's word
@@ -1636,6 +1639,88 @@ void ensure_batch_pinned(ngicp* h) {
   if (!w.pin_final) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w.pin_final), (size_t)kBatchMaxLanes * sizeof(LmHot), hipHostMallocDefault));
 }
 
+// The feeding loop of a batch, shared by ngicp_align_batch and ngicp_voxel_align_batch: the lane records are on the device, every
+// lane's progress word in pinned memory is 0; launch_pass_batch(bl, n_live) enqueues one pass launch that serves the n_live lanes listed
+// in bl.lane, and one k_lm_solve_batch launch behind it steps their optimisers.  result[g]: lane g's final state image.
+template <class LaunchPass>
+void feed_batch(ngicp* h, int B, BatchLaunch& bl, long max_passes, std::vector<LmHot>& result, LaunchPass&& launch_pass_batch) {
+  BatchWs& w = h->batch;
+  // The feeding discipline of do_align: (pass, solve) pairs kept `depth` ahead of the slowest live lane's progress word.  A lane that
+  // reports done leaves the list; its blocks in the launches already enqueued return at their head.
+  const int depth = h->chunk_pairs;
+  const double t_loop = now_ms();
+  unsigned long spins = 0;
+  bool idle_seen = false;
+  // Every so many polls the stream is asked for its status: an asynchronous error comes out as its HIP error, not as the timeout.
+  // true: the stream has nothing left to run.
+  auto look_at_stream = [&]() -> bool {
+    const hipError_t q = hipStreamQuery(h->stream);
+    if (q == hipErrorNotReady) {
+      (void)hipGetLastError();
+    } else if (q != hipSuccess) {
+      throw HipError{q, "hipStreamQuery(h->stream)", __FILE__, __LINE__};
+    }
+    if (now_ms() - t_loop > 30000.0) throw ArgError{NGICP_ERR_HIP, "the batched registration loop did not finish within 30 s"};
+    return q == hipSuccess;
+  };
+  auto relax = [&]() {
+    // (idle at the last look: every launch enqueued had run, so the words the caller has just read again were final)
+    if (idle_seen) throw ArgError{NGICP_ERR_HIP, "the batched registration loop: the stream is idle but a lane has not reported"};
+    if ((++spins & (h->host_wait ? 0xff : 0xfff)) == 0 && look_at_stream()) {
+      idle_seen = true;
+      return;
+    }
+    if (h->host_wait) sched_yield(); else __builtin_ia32_pause();
+  };
+  long launched = 0;
+  int n_live = B;
+  std::vector<int> live((size_t)B);
+  for (int g = 0; g < B; ++g) live[(size_t)g] = g;
+  for (;;) {
+    long min_prog = std::numeric_limits<long>::max();
+    int keep_n = 0;
+    for (int i = 0; i < n_live; ++i) {
+      const int g = live[(size_t)i];
+      const int prog = __atomic_load_n(w.pin_progress + (size_t)g * BatchWs::kProgressStride, __ATOMIC_ACQUIRE);
+      if (prog & kProgressDone) {
+        result[(size_t)g] = w.pin_final[g];  // (stored before the flag: lm_solve_body)
+        continue;
+      }
+      live[(size_t)keep_n++] = g;
+      min_prog = std::min(min_prog, (long)(prog & kProgressMask));
+    }
+    n_live = keep_n;
+    if (n_live == 0) break;
+    if (launched >= max_passes || launched - min_prog >= depth) {  // enough in flight (or nothing left to launch: the last possible pass sets done)
+      relax();
+      continue;
+    }
+    idle_seen = false;
+    for (int i = 0; i < n_live; ++i) bl.lane[i] = live[(size_t)i];
+    launch_pass_batch(bl, n_live);
+    hipLaunchKernelGGL(k_lm_solve_batch, dim3((unsigned)n_live), dim3(kSolveThreads), 0, h->stream, bl);
+    ++launched;
+  }
+}
+
+// every lane's final state into the caller's arrays, and the description of the traces ngicp_batch_get_lm_trace serves
+void return_batch_results(ngicp* h, const std::vector<LmHot>& result, size_t trace_stride, float* T_out, int* converged, int* nr_iterations, double* hessians) {
+  BatchWs& w = h->batch;
+  for (size_t g = 0; g < result.size(); ++g) {
+    const LmHot& r = result[g];
+    pose_to_colmajor_f(r.x0, T_out + g * 16);
+    if (converged) converged[g] = r.converged;
+    if (nr_iterations) nr_iterations[g] = r.nr_iterations;
+    if (hessians)
+      for (int rr = 0; rr < 6; ++rr)
+        for (int cc = 0; cc < 6; ++cc) hessians[g * 36 + cc * 6 + rr] = r.final_H[rr * 6 + cc];
+    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");  // impl/lsq_registration_impl.hpp:106
+    w.trace_rows.push_back((size_t)r.n_trace);
+  }
+  w.lanes = (int)result.size();
+  w.trace_stride = trace_stride;
+}
+
 // The batch always takes the default route: walks in global memory (k_gicp_pass_batch), a solver launch of its own (k_lm_solve_batch).
 // NGICP_PERSIST, NGICP_HEAD, NGICP_FUSED, NGICP_QUEUE, NGICP_PASS_IMPL and NGICP_ORDER do not apply to it.
 void do_align_batch(ngicp* h, int B, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* hessians) {
@@ -1720,87 +1805,117 @@ void do_align_batch(ngicp* h, int B, const float* guesses, float* T_out, int* co
   } else {
     HIP_TRY(hipMemcpyAsync(recs_dev, w.pin_recs, recs_bytes, hipMemcpyHostToDevice, h->stream));  // ONE upload
     BatchLaunch bl;
-    bl.pass = reinterpret_cast<const PassArgs*>(recs_dev + off_pass);
+    bl.pass = recs_dev + off_pass;
     bl.solve = reinterpret_cast<const SolveArgs*>(recs_dev + off_solve);
     for (int i = 0; i < kBatchMaxLanes; ++i) bl.lane[i] = 0;
-    // The feeding discipline of do_align: (pass, solve) pairs kept `depth` ahead of the slowest live lane's progress word.  A lane that
-    // reports done leaves the list; its blocks in the launches already enqueued return at their head.
-    const int depth = h->chunk_pairs;
-    const double t_loop = now_ms();
-    unsigned long spins = 0;
-    bool idle_seen = false;
-    // Every so many polls the stream is asked for its status: an asynchronous error comes out as its HIP error, not as the timeout.
-    // true: the stream has nothing left to run.
-    auto look_at_stream = [&]() -> bool {
-      const hipError_t q = hipStreamQuery(h->stream);
-      if (q == hipErrorNotReady) {
-        (void)hipGetLastError();
-      } else if (q != hipSuccess) {
-        throw HipError{q, "hipStreamQuery(h->stream)", __FILE__, __LINE__};
-      }
-      if (now_ms() - t_loop > 30000.0) throw ArgError{NGICP_ERR_HIP, "the batched registration loop did not finish within 30 s"};
-      return q == hipSuccess;
-    };
-    auto relax = [&]() {
-      // (idle at the last look: every launch enqueued had run, so the words the caller has just read again were final)
-      if (idle_seen) throw ArgError{NGICP_ERR_HIP, "the batched registration loop: the stream is idle but a lane has not reported"};
-      if ((++spins & (h->host_wait ? 0xff : 0xfff)) == 0 && look_at_stream()) {
-        idle_seen = true;
-        return;
-      }
-      if (h->host_wait) sched_yield(); else __builtin_ia32_pause();
-    };
-    long launched = 0;
-    int n_live = B;
-    std::vector<int> live((size_t)B);
-    for (int g = 0; g < B; ++g) live[(size_t)g] = g;
-    for (;;) {
-      long min_prog = std::numeric_limits<long>::max();
-      int keep_n = 0;
-      for (int i = 0; i < n_live; ++i) {
-        const int g = live[(size_t)i];
-        const int prog = __atomic_load_n(w.pin_progress + (size_t)g * BatchWs::kProgressStride, __ATOMIC_ACQUIRE);
-        if (prog & kProgressDone) {
-          result[(size_t)g] = w.pin_final[g];  // (stored before the flag: lm_solve_body)
-          continue;
-        }
-        live[(size_t)keep_n++] = g;
-        min_prog = std::min(min_prog, (long)(prog & kProgressMask));
-      }
-      n_live = keep_n;
-      if (n_live == 0) break;
-      if (launched >= max_passes || launched - min_prog >= depth) {  // enough in flight (or nothing left to launch: the last possible pass sets done)
-        relax();
-        continue;
-      }
-      idle_seen = false;
-      for (int i = 0; i < n_live; ++i) bl.lane[i] = live[(size_t)i];
+    feed_batch(h, B, bl, max_passes, result, [&](const BatchLaunch& l, int n_live) {
       const bool four = (long)nblocks * n_live > 2L * h->pass_slots;  // launch_pass's rule on the whole grid
       if (four)
-        hipLaunchKernelGGL((k_gicp_pass_batch<2, 4>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, bl);
+        hipLaunchKernelGGL((k_gicp_pass_batch<2, 4>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, l);
       else
-        hipLaunchKernelGGL((k_gicp_pass_batch<2, 3>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, bl);
-      hipLaunchKernelGGL(k_lm_solve_batch, dim3((unsigned)n_live), dim3(kSolveThreads), 0, h->stream, bl);
-      ++launched;
-    }
+        hipLaunchKernelGGL((k_gicp_pass_batch<2, 3>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, l);
+    });
     HIP_TRY(hipGetLastError());
   }
-  for (int g = 0; g < B; ++g) {
-    const LmHot& r = result[(size_t)g];
-    pose_to_colmajor_f(r.x0, T_out + (size_t)g * 16);
-    if (converged) converged[g] = r.converged;
-    if (nr_iterations) nr_iterations[g] = r.nr_iterations;
-    if (hessians)
-      for (int rr = 0; rr < 6; ++rr)
-        for (int cc = 0; cc < 6; ++cc) hessians[(size_t)g * 36 + cc * 6 + rr] = r.final_H[rr * 6 + cc];
-    if (r.lm_failed) std::fprintf(stderr, "lm not converged!!\n");  // impl/lsq_registration_impl.hpp:106
-    w.trace_rows.push_back((size_t)r.n_trace);
-  }
-  w.lanes = B;
-  w.trace_stride = trace_stride;
+  return_batch_results(h, result, trace_stride, T_out, converged, nr_iterations, hessians);
   w.order_src = h->src.dev.get();
   w.order_groups = nblocks;
   w.order_lanes = std::max(order_kept ? lanes_before : 0, B);
+}
+
+// ngicp_voxel_align_batch: do_align_batch's protocol - the lane records in one pinned block and one upload, a progress
+// word and a final image per lane in pinned memory, the live lanes in the kernel arguments, feed_batch - with k_vgicp_pass_batch<K> in
+// k_gicp_pass_batch's place and the solver's records as prepare_voxel_loop sets them (no launch order).  Every per-lane buffer is the
+// batch's own: vox_corr / vox_mahal / mahal / state / partials / trace of the handle, which the getters of the last ngicp_align read,
+// are neither resized nor written.  None of the exact path's kernel-variant switches applies.
+void do_align_voxel_batch(ngicp* h, int B, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* hessians) {
+  static_assert(sizeof(VoxelPassArgs) <= sizeof(PassArgs), "the pinned record block is sized for PassArgs records");
+  BatchWs& w = h->batch;
+  const int max_rows = std::max(1, h->p.max_iter) * std::max(1, h->p.lm_max_iter) + 1;
+  LoopCtx c;
+  prepare_loop(h, c, false);  // (slots, lazy covariances, the solver's configuration)
+  ensure_voxel_map(h);        // (at most one build, whatever the number of lanes)
+  const size_t n = h->src.dev->n, K = (size_t)h->voxel_nbr;
+  const int nblocks = std::max(1, (int)((n + kVoxBlock - 1) / kVoxBlock));
+  const size_t corr_stride = round_up(K * n * sizeof(int), 256), mahal_stride = round_up(K * n * 6 * sizeof(double), 256);
+  const size_t part_stride = (size_t)nblocks * kNumSlots * sizeof(double);
+  const size_t trace_stride = (size_t)max_rows * kTraceCols;
+  const size_t off_pass = (size_t)B * sizeof(LmState), off_solve = off_pass + round_up((size_t)B * sizeof(VoxelPassArgs), 16);
+  const size_t recs_bytes = off_solve + (size_t)B * sizeof(SolveArgs);
+  w.lanes = 0;  // (the traces of the previous call go with the buffers)
+  w.trace_rows.clear();
+  // (every buffer is sized before the first launch: growing one frees it, and freeing waits for the device)
+  ensure_batch_pinned(h);
+  w.recs.ensure(recs_bytes);
+  w.vox_corr.ensure((size_t)B * 2 * corr_stride);
+  w.vox_mahal.ensure((size_t)B * 2 * mahal_stride);
+  w.partials.ensure((size_t)B * part_stride);
+  w.trace.ensure((size_t)B * trace_stride * sizeof(double));
+
+  LmState* const st_host = reinterpret_cast<LmState*>(w.pin_recs);
+  VoxelPassArgs* const pa_host = reinterpret_cast<VoxelPassArgs*>(w.pin_recs + off_pass);
+  SolveArgs* const sa_host = reinterpret_cast<SolveArgs*>(w.pin_recs + off_solve);
+  unsigned char* const recs_dev = w.recs.as<unsigned char>();
+  VoxelPassArgs shared;
+  shared.src = h->src.dev->pts();
+  shared.cov_src = c.pa.cov_src;
+  shared.n_src = (int)n;
+  shared.table = h->vmap.table.as<ulonglong2>();
+  shared.mask = h->vmap.mask;
+  shared.rec = h->vmap.rec.as<double>();
+  shared.n_vox = (int)h->vmap.n_vox;
+  shared.inv_res = 1.0f / (float)h->voxel_res;
+  shared.mode = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? 2 : 3;
+  shared.t_first = nullptr;
+  shared.nbr = (int)K;
+  shared.slot_stride = (int)n;
+  for (int g = 0; g < B; ++g) {
+    init_state_from_pose(st_host[g], pose_from_colmajor_f(guesses + (size_t)g * 16));
+    if (h->p.max_iter <= 0) st_host[g].hot.done = 1;
+    VoxelPassArgs pa = shared;
+    pa.st = reinterpret_cast<LmState*>(recs_dev) + g;
+    for (int i = 0; i < 2; ++i) {
+      pa.corr[i] = reinterpret_cast<int*>(w.vox_corr.as<unsigned char>() + ((size_t)g * 2 + i) * corr_stride);
+      pa.mahal[i] = reinterpret_cast<double*>(w.vox_mahal.as<unsigned char>() + ((size_t)g * 2 + i) * mahal_stride);
+    }
+    pa.partials = reinterpret_cast<double*>(w.partials.as<unsigned char>() + (size_t)g * part_stride);
+    SolveArgs sa = c.sa;
+    sa.st = pa.st;
+    sa.partials = pa.partials;
+    sa.nblocks = nblocks;
+    sa.grp_order = nullptr;  // (the solver sorts nothing: prepare_voxel_loop)
+    sa.grp_cost = nullptr;
+    sa.order_valid = nullptr;
+    sa.trace = w.trace.as<double>() + (size_t)g * trace_stride;
+    sa.progress_host = w.pin_progress + (size_t)g * BatchWs::kProgressStride;
+    sa.final_host = w.pin_final + g;
+    sa.t_first = nullptr;
+    pa_host[g] = pa;
+    sa_host[g] = sa;
+    *sa.progress_host = 0;
+  }
+  const long max_passes = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? (long)h->p.max_iter : (long)h->p.max_iter * std::max(1, h->p.lm_max_iter) + 1;
+  std::vector<LmHot> result((size_t)B);
+  if (h->p.max_iter <= 0) {
+    for (int g = 0; g < B; ++g) result[(size_t)g] = st_host[g].hot;  // every lane returns its guess, as ngicp_align does; nothing is launched
+  } else {
+    HIP_TRY(hipMemcpyAsync(recs_dev, w.pin_recs, recs_bytes, hipMemcpyHostToDevice, h->stream));  // ONE upload
+    BatchLaunch bl;
+    bl.pass = recs_dev + off_pass;
+    bl.solve = reinterpret_cast<const SolveArgs*>(recs_dev + off_solve);
+    for (int i = 0; i < kBatchMaxLanes; ++i) bl.lane[i] = 0;
+    feed_batch(h, B, bl, max_passes, result, [&](const BatchLaunch& l, int n_live) {
+      const dim3 grid((unsigned)nblocks, (unsigned)n_live), block(kVoxBlock);
+      switch ((int)K) {
+        case NGICP_VOX_DIRECT1: hipLaunchKernelGGL(k_vgicp_pass_batch<1>, grid, block, 0, h->stream, l); break;
+        case NGICP_VOX_DIRECT7: hipLaunchKernelGGL(k_vgicp_pass_batch<7>, grid, block, 0, h->stream, l); break;
+        case NGICP_VOX_DIRECT27: hipLaunchKernelGGL(k_vgicp_pass_batch<27>, grid, block, 0, h->stream, l); break;
+        default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
+      }
+    });
+    HIP_TRY(hipGetLastError());
+  }
+  return_batch_results(h, result, trace_stride, T_out, converged, nr_iterations, hessians);
 }
 
 template <class F>
@@ -2277,10 +2392,21 @@ int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float*
   });
 }
 
+int ngicp_voxel_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
+  return guarded(h, [&] {
+    if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "ngicp_voxel_align_batch: the voxelized mode is off (ngicp_set_voxel_resolution)"};
+    if (n_guesses == 0) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_align_batch: n_guesses is 0"};
+    if (n_guesses > (size_t)NGICP_BATCH_MAX_LANES) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_align_batch: more than NGICP_BATCH_MAX_LANES (64) guesses in one call"};
+    if (!guesses) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_align_batch: null guesses"};
+    if (!T_out || !converged || !nr_iterations) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_align_batch: null output"};
+    do_align_voxel_batch(h, (int)n_guesses, guesses, T_out, converged, nr_iterations, final_hessians);
+  });
+}
+
 int ngicp_batch_get_lm_trace(ngicp_t* h, size_t lane, double* rows, size_t max_rows, size_t* n_rows) {
   return guarded(h, [&] {
     BatchWs& w = h->batch;
-    if (lane >= (size_t)w.lanes) throw ArgError{NGICP_ERR_ARG, "ngicp_batch_get_lm_trace: no such lane in the last ngicp_align_batch"};
+    if (lane >= (size_t)w.lanes) throw ArgError{NGICP_ERR_ARG, "ngicp_batch_get_lm_trace: no such lane in the last ngicp_align_batch / ngicp_voxel_align_batch"};
     const size_t n = w.trace_rows[lane];
     if (n_rows) *n_rows = n;
     const size_t take = std::min(n, max_rows);

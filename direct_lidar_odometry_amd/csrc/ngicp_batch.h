@@ -23,7 +23,8 @@ namespace ngk {
 constexpr int kBatchMaxLanes = 64;  // == NGICP_BATCH_MAX_LANES (include/ngicp.h)
 
 struct BatchLaunch {
-  const PassArgs* pass;    // [lanes of the batch] in device memory
+  const void* pass;        // [lanes of the batch] in device memory: PassArgs records (k_gicp_pass_batch) or VoxelPassArgs records
+                           // (k_vgicp_pass_batch, ngicp_voxel_batch.h)
   const SolveArgs* solve;  // likewise
   int lane[kBatchMaxLanes];  // blockIdx.y (pass) / blockIdx.x (solver) -> lane of the batch
 };
@@ -89,7 +90,7 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass_batch(BatchLaunch bl) {
   // scalar loads through the constant address space - neither the record nor the state changes while the launch runs.
   KernelBatchLaunch* kb = (KernelBatchLaunch*)__builtin_amdgcn_kernarg_segment_ptr();
   const int lane_id = kb->lane[blockIdx.y];
-  KernelPassArgs* ka = (KernelPassArgs*)(unsigned long long)(kb->pass + lane_id);
+  KernelPassArgs* ka = (KernelPassArgs*)(unsigned long long)(reinterpret_cast<const PassArgs*>(kb->pass) + lane_id);
   typedef const int __attribute__((address_space(4))) * ConstIntPtr;
   typedef const LmState __attribute__((address_space(4))) * StatePtr;
   const int done_now = ((StatePtr)(unsigned long long)ka->st)->hot.done;

@@ -27,6 +27,8 @@
 //                                 K = 7: (0,0,0) (+1,0,0) (-1,0,0) (0,+1,0) (0,-1,0) (0,0,+1) (0,0,-1); K = 27: {-1,0,1}^3 in the key's order
 //                                 (dx fastest, dz slowest; the centre is slot 13).  State is slot-major: corr[K][n_src], mahal[K][n_src][6].
 //                                 k_vgicp_pass itself serves DIRECT1 and is not touched by any of this.
+//   vgicp_pass_body / vgicp_pass_n_body<K>   what the two kernels do once they hold the state's pose and flags, as inlined functions:
+//                                 k_vgicp_pass_batch<K> (ngicp_voxel_batch.h) runs the same bodies on a lane's record.
 #pragma once
 #include "ngicp_pass.h"
 
@@ -153,24 +155,24 @@ struct VoxelPassArgs {
   int slot_stride;          // k_vgicp_pass_n: corr / mahal are slot-major, slot s of point i at [s * slot_stride + i]
 };
 
-__global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
-  __shared__ double red[4][16 * 30];
-  __shared__ double lds[4][kNumSlots];
-  __shared__ unsigned int cnt[4][2][64];
-  const LmState* __restrict__ st = a.st;
-  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
-  const int cur = st->hot.cur, nxt = cur ^ 1;
-  double R[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
-  float Tf[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
-  if (!(a.mode & 4) && done_now) return;
-  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+// The shared-memory arrays of a voxelized pass block (K = 1 has no `vs`).
+struct VoxelPassLds {
+  double red[4][16 * 30];
+  double lds[4][kNumSlots];
+  unsigned int cnt[4][2][64];
+};
 
+// One block of one DIRECT1 pass, from the pose on: everything k_vgicp_pass does once it holds the state's trial pose and flags.  The
+// single kernel and k_vgicp_pass_batch<1> (ngicp_voxel_batch.h) both inline it: the same per-point statements, the same reduction, the
+// same row - a lane of the batch comes out bit for bit as the single alignment.  A: VoxelPassArgs (the kernel's argument) or the same
+// record seen through the constant address space (KernelVoxelPassArgs: a lane's record in device memory, read with scalar loads).
+template <class A>
+__device__ __forceinline__ void vgicp_pass_body(A& a, const double (&R)[9], const double (&t)[3], const float (&Tf)[12], const int have_lin_now, const int cur,
+                                                VoxelPassLds& sh) {
+  double (&red)[4][16 * 30] = sh.red;
+  double (&lds)[4][kNumSlots] = sh.lds;
+  unsigned int (&cnt)[4][2][64] = sh.cnt;
+  const int nxt = cur ^ 1;
   const bool do_err = (a.mode & 1) && have_lin_now;
   const bool do_lin = (a.mode & 2);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -290,6 +292,26 @@ __global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
   }
 }
 
+typedef const VoxelPassArgs __attribute__((address_space(4))) KernelVoxelPassArgs;
+
+__global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
+  __shared__ VoxelPassLds sh;
+  const LmState* __restrict__ st = a.st;
+  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
+  const int cur = st->hot.cur;
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
+  float Tf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
+  if (!(a.mode & 4) && done_now) return;
+  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+  vgicp_pass_body(a, R, t, Tf, have_lin_now, cur, sh);
+}
+
 // voxel numbers (and float squared distances to (float)mean_v at the pose of the linearisation) back in ORIGINAL source order
 __global__ void __launch_bounds__(256) k_voxel_corr_to_original(const int* __restrict__ corr, const float4* __restrict__ src, int n, const double* __restrict__ rec,
                                                                  int* __restrict__ out_corr, float* __restrict__ out_sqd, const float* __restrict__ lin_f) {
@@ -325,25 +347,20 @@ template <int K>
 __host__ __device__ constexpr int vox_nbr_centre() { return K == 27 ? 13 : 0; }
 
 template <int K>
-__global__ void __launch_bounds__(kVoxBlock, 2) k_vgicp_pass_n(VoxelPassArgs a) {
-  __shared__ double red[4][16 * 30];
-  __shared__ double lds[4][kNumSlots];
-  __shared__ unsigned int cnt[4][2][64];
-  __shared__ int vs[K][kVoxBlock];  // a thread's K voxel numbers between the lookups (unrolled) and the terms (a rolled loop): its own column
-  const LmState* __restrict__ st = a.st;
-  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
-  const int cur = st->hot.cur, nxt = cur ^ 1;
-  double R[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
-  float Tf[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
-  if (!(a.mode & 4) && done_now) return;
-  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+struct VoxelPassLdsN : VoxelPassLds {
+  int vs[K][kVoxBlock];  // a thread's K voxel numbers between the lookups (unrolled) and the terms (a rolled loop): its own column
+};
 
+// vgicp_pass_body for the neighbourhoods: one block of one DIRECT7 / DIRECT27 pass from the pose on, inlined into k_vgicp_pass_n<K> and
+// k_vgicp_pass_batch<K>.
+template <int K, class A>
+__device__ __forceinline__ void vgicp_pass_n_body(A& a, const double (&R)[9], const double (&t)[3], const float (&Tf)[12], const int have_lin_now, const int cur,
+                                                  VoxelPassLdsN<K>& sh) {
+  double (&red)[4][16 * 30] = sh.red;
+  double (&lds)[4][kNumSlots] = sh.lds;
+  unsigned int (&cnt)[4][2][64] = sh.cnt;
+  int (&vs)[K][kVoxBlock] = sh.vs;
+  const int nxt = cur ^ 1;
   const bool do_err = (a.mode & 1) && have_lin_now;
   const bool do_lin = (a.mode & 2);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -510,6 +527,25 @@ __global__ void __launch_bounds__(kVoxBlock, 2) k_vgicp_pass_n(VoxelPassArgs a) 
     const int v = threadIdx.x;
     a.partials[(size_t)blockIdx.x * kNumSlots + v] = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
   }
+}
+
+template <int K>
+__global__ void __launch_bounds__(kVoxBlock, 2) k_vgicp_pass_n(VoxelPassArgs a) {
+  __shared__ VoxelPassLdsN<K> sh;
+  const LmState* __restrict__ st = a.st;
+  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
+  const int cur = st->hot.cur;
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
+  float Tf[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
+  if (!(a.mode & 4) && done_now) return;
+  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+  vgicp_pass_n_body<K>(a, R, t, Tf, have_lin_now, cur, sh);
 }
 
 // the K voxel numbers of every source point, slot-major in sorted order -> row-major [n][K] in ORIGINAL source order

@@ -87,6 +87,7 @@ EXPORTS = [
     "ngicp_range_select", "ngicp_range_median",
     "ngicp_set_voxel_resolution", "ngicp_voxelmap_size", "ngicp_voxelmap_get",
     "ngicp_set_voxel_neighbors", "ngicp_get_voxel_neighbors", "ngicp_voxel_correspondences", "ngicp_voxelmap_builds",
+    "ngicp_voxel_align_batch",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -144,6 +145,7 @@ def load_library() -> C.CDLL:
     L.ngicp_range_median.argtypes = [vp, C.c_int, c_f32p, C.POINTER(C.c_size_t)]
     L.ngicp_get_lm_trace.argtypes = [vp, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_align_batch.argtypes = [vp, C.c_size_t, c_f32p, c_f32p, c_i32p, c_i32p, c_f64p]
+    L.ngicp_voxel_align_batch.argtypes = [vp, C.c_size_t, c_f32p, c_f32p, c_i32p, c_i32p, c_f64p]
     L.ngicp_batch_get_lm_trace.argtypes = [vp, C.c_size_t, c_f64p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_fitness_score_batch.argtypes = [vp, C.c_size_t, c_f32p, C.c_double, c_f64p, C.POINTER(C.c_size_t)]
     L.ngicp_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -416,17 +418,26 @@ class NanoGICP:
         """Several initial guesses on the current source / target pair in the same launches (ngicp_align_batch; no counterpart in
         the reference).  guesses: (B, 4, 4).  -> (T (B, 4, 4) float32, converged (B,) bool, iterations (B,) int32, H (B, 6, 6) float64);
         lane g is bit for bit what align(guesses[g]) gives.  Leaves final_transformation_ and the other results of align() alone."""
+        return self._align_batch(self._L.ngicp_align_batch, "alignBatch", guesses)
+
+    def alignBatchVoxel(self, guesses):
+        """alignBatch against the voxelized target (ngicp_voxel_align_batch; setVoxelResolution > 0, any neighbourhood): the same
+        arguments and the same return tuple; lane g is bit for bit what align(guesses[g]) gives with the voxel mode on.  alignBatch
+        itself stays refused in that mode.  lm_trace(lane=g) serves its lanes afterwards."""
+        return self._align_batch(self._L.ngicp_voxel_align_batch, "alignBatchVoxel", guesses)
+
+    def _align_batch(self, entry, name, guesses):
         g = np.asarray(guesses)
         if g.ndim != 3 or g.shape[1:] != (4, 4):
-            raise NgicpError(-2, "alignBatch: guesses must be (B, 4, 4)")
+            raise NgicpError(-2, f"{name}: guesses must be (B, 4, 4)")
         B = g.shape[0]
         gc = np.ascontiguousarray(np.transpose(g, (0, 2, 1)), dtype=np.float32).reshape(B, 16)  # column-major per lane
         T = np.empty((B, 16), dtype=np.float32)
         H = np.empty((B, 36), dtype=np.float64)
         conv = np.zeros(B, dtype=np.int32)
         nit = np.zeros(B, dtype=np.int32)
-        self._ck(self._L.ngicp_align_batch(self._h, B, _p(gc, c_f32p) if B else None, _p(T, c_f32p) if B else None,
-                                           _p(conv, c_i32p) if B else None, _p(nit, c_i32p) if B else None, _p(H, c_f64p) if B else None))
+        self._ck(entry(self._h, B, _p(gc, c_f32p) if B else None, _p(T, c_f32p) if B else None,
+                       _p(conv, c_i32p) if B else None, _p(nit, c_i32p) if B else None, _p(H, c_f64p) if B else None))
         return (np.ascontiguousarray(np.transpose(T.reshape(B, 4, 4), (0, 2, 1))), conv.astype(bool), nit,
                 np.ascontiguousarray(np.transpose(H.reshape(B, 6, 6), (0, 2, 1))))
 
@@ -532,7 +543,7 @@ class NanoGICP:
         return np.float32(v.value)
 
     def lm_trace(self, lane=None) -> np.ndarray:
-        """LM trace of the last align() (lane None), or of lane `lane` of the last alignBatch()."""
+        """LM trace of the last align() (lane None), or of lane `lane` of the last alignBatch() / alignBatchVoxel()."""
         n = C.c_size_t(0)
         if lane is not None:
             self._ck(self._L.ngicp_batch_get_lm_trace(self._h, int(lane), None, 0, C.byref(n)))

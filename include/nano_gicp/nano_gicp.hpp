@@ -369,7 +369,8 @@ class NanoGICP {
   // setVoxelResolution(res > 0): align() matches every source point against the Gaussian of the target voxel (edge `res`) it falls into -
   // one table lookup instead of an exact nearest-neighbour search; the voxel map is built on the device at the first align() after the
   // target, its covariances or the resolution changed.  0 (the default) is exact GICP.  A different algorithm with different results:
-  // setMaxCorrespondenceDistance is not consulted, and alignBatch is not available while it is on.  getVoxelMapSize: occupied voxels.
+  // setMaxCorrespondenceDistance is not consulted, and alignBatch is not available while it is on (alignBatchVoxel is).  getVoxelMapSize:
+  // occupied voxels.
   void setVoxelResolution(double res) {
     if (h_ && check(ngicp_set_voxel_resolution(h_, res), "setVoxelResolution")) voxel_resolution_ = res;
   }
@@ -425,7 +426,12 @@ class NanoGICP {
     int nr_iterations = 0;
     types::Matrix6d hessian;
   };
-  std::vector<BatchResult> alignBatch(const std::vector<Matrix4>& guesses) {
+  std::vector<BatchResult> alignBatch(const std::vector<Matrix4>& guesses) { return alignBatchThrough(ngicp_align_batch, "alignBatch", guesses); }
+  // alignBatch against the voxelized target (setVoxelResolution > 0, any setNeighborSearchMethod): result g is bit for bit what
+  // alignPoseOnly(guesses[g]) leaves in the getters in that mode.  Empty (and a line on stderr) while the voxel mode is off.
+  std::vector<BatchResult> alignBatchVoxel(const std::vector<Matrix4>& guesses) { return alignBatchThrough(ngicp_voxel_align_batch, "alignBatchVoxel", guesses); }
+  template <class Entry>
+  std::vector<BatchResult> alignBatchThrough(Entry entry, const char* name, const std::vector<Matrix4>& guesses) {
     std::vector<BatchResult> out;
     if (!h_ || !input_ || !(target_ || device_target_) || guesses.empty()) return out;
     const size_t n = guesses.size();
@@ -433,8 +439,8 @@ class NanoGICP {
     std::vector<int> conv(n), nit(n);
     std::vector<double> H(n * 36);
     for (size_t i = 0; i < n; ++i) std::memcpy(&g[i * 16], guesses[i].data(), 16 * sizeof(float));
-    if (ngicp_align_batch(h_, n, g.data(), T.data(), conv.data(), nit.data(), H.data()) != NGICP_OK) {
-      std::fprintf(stderr, "[NanoGICP] alignBatch(): %s\n", ngicp_last_error(h_));
+    if (entry(h_, n, g.data(), T.data(), conv.data(), nit.data(), H.data()) != NGICP_OK) {
+      std::fprintf(stderr, "[NanoGICP] %s(): %s\n", name, ngicp_last_error(h_));
       return out;
     }
     out.resize(n);

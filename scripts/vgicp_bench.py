@@ -18,6 +18,11 @@ transformation epsilon 0.01, the workload's correspondence gate - which the voxe
 stay where they were (resolutions[r]); the others are under resolutions[r]["neighbors"][K] with the same device figures plus
 us_per_pass_vs_direct1, the per-pass time relative to DIRECT1 of the same run, resolution and handle - the figure of interest - and
 valid_fraction there counts pairs per point.  Changing the neighbourhood keeps the voxel map, so no build is timed for them.
+
+  python scripts/vgicp_bench.py --batch 2,8 [--workloads c1,s20k,c3,c5] [--resolutions 1.0] [--neighbors 1,7,27] [--reps 30]
+is a measurement of its own (nothing of the above runs): alignBatchVoxel(B guesses) against B sequential voxel-mode align() calls on
+the same handle in the same loop, host to host, per neighbourhood, at scripts/batch_bench.py's sizes, guesses and fixed 20 iterations;
+medians and p10..p90.  The yardstick is the loop of single aligns.  It writes profiles/vgicp_batch_bench.json unless --out says otherwise.
 """
 import argparse
 import json
@@ -34,6 +39,8 @@ DLO = dict(setMaximumIterations=32, setTransformationEpsilon=0.01)
 
 
 def _workload(clouds, name):
+    if name == "c1":
+        return clouds.scan_to_scan(10_000)
     if name == "c3":
         return clouds.scan_to_submap(100_000, 5)
     if name == "c5":
@@ -62,10 +69,80 @@ def _device_figures(g, clouds, w):
             "error_vs_ground_truth_m": dt, "error_vs_ground_truth_rad": dr}
 
 
+def _batch_guesses(clouds, w, B):
+    """scripts/batch_bench.py's: the workload's guess and B - 1 poses a few centimetres and a few tenths of a degree off it."""
+    rng = np.random.default_rng(11)
+    out = [np.asarray(w.guess, np.float32)]
+    for _ in range(B - 1):
+        t = rng.uniform(-0.03, 0.03, 3)
+        r = rng.uniform(-0.3, 0.3, 3)
+        out.append((np.asarray(w.guess, np.float64) @ clouds.make_pose(tuple(t), tuple(r))).astype(np.float32))
+    return np.stack(out)
+
+
+def batch_main(a, torch, clouds, ng):
+    """--batch: alignBatchVoxel(B) against a loop of B voxel-mode align() calls."""
+    fixed20 = dict(setMaximumIterations=20, setRotationEpsilon=1e-12, setTransformationEpsilon=1e-12)  # every lane runs all 20 iterations
+    lanes = [int(v) for v in a.batch.split(",")]
+    out = {"metric": "voxel_align_batch_vs_loop", "device": torch.cuda.get_device_name(0), "iterations": 20, "reps": a.reps, "workloads": {}}
+    for name in (a.workloads or "c1,s20k,c3,c5").split(","):
+        w = _workload(clouds, name)
+        g = ng.NanoGICP()
+        g.setCorrespondenceRandomness(20)
+        for k, v in fixed20.items():
+            getattr(g, k)(v)
+        g.setInputTarget(w.target)
+        g.setInputSource(w.source)
+        g.calculateSourceCovariances()
+        g.calculateTargetCovariances()
+        res = {"source_points": int(len(w.source)), "target_points": int(len(w.target)), "resolutions": {}}
+        for r in [float(v) for v in (a.resolutions or "1.0").split(",")]:
+            g.setVoxelResolution(r)
+            per_k = {}
+            for K in [int(k) for k in a.neighbors.split(",")]:
+                g.setNeighborSearchMethod(K)
+                per_b = {}
+                for B in lanes:
+                    G = _batch_guesses(clouds, w, B)
+
+                    def loop():
+                        for q in G:
+                            g.align(q)
+
+                    for _ in range(3):  # warm both (the map, the buffers of either path)
+                        g.alignBatchVoxel(G)
+                        loop()
+                    tb, tl = [], []
+                    for _ in range(a.reps):
+                        t0 = time.perf_counter()
+                        rr = g.alignBatchVoxel(G)
+                        t1 = time.perf_counter()
+                        loop()
+                        t2 = time.perf_counter()
+                        tb.append((t1 - t0) * 1e3)
+                        tl.append((t2 - t1) * 1e3)
+                    b, l = _summ(tb), _summ(tl)
+                    spread = max(b["p90_ms"] - b["p10_ms"], l["p90_ms"] - l["p10_ms"])
+                    per_b[str(B)] = {"batch": b, "loop": l, "loop_over_batch": l["median_ms"] / b["median_ms"],
+                                     "wins_beyond_spread": bool(l["median_ms"] - b["median_ms"] > spread), "iterations_per_lane": [int(v) for v in rr[2]]}
+                    print(name, r, K, B, json.dumps(per_b[str(B)]), file=sys.stderr, flush=True)
+                per_k[str(K)] = per_b
+            res["resolutions"][str(r)] = {"voxels": int(g.getVoxelMapSize()), "neighbors": per_k}
+        g.close()
+        out["workloads"][name] = res
+    line = json.dumps(out)
+    path = a.out or os.path.join(ROOT, "profiles", "vgicp_batch_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(line + "\n")
+    print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workloads", default="c3,c5")
-    ap.add_argument("--resolutions", default="0.5,1.0,2.0")
+    ap.add_argument("--workloads", default="")
+    ap.add_argument("--resolutions", default="")
+    ap.add_argument("--batch", default="", help="B[,B...]: time alignBatchVoxel(B guesses) against B sequential voxel-mode align() calls instead")
     ap.add_argument("--neighbors", default="1,7,27")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default="")
@@ -75,6 +152,10 @@ def main():
         raise SystemExit("vgicp_bench.py needs an MI355X: no HIP device visible (there is no CPU fallback)")
     from direct_lidar_odometry_amd import build, clouds, nano_gicp as ng
     build.build()
+    if a.batch:
+        return batch_main(a, torch, clouds, ng)
+    a.workloads = a.workloads or "c3,c5"
+    a.resolutions = a.resolutions or "0.5,1.0,2.0"
     out = {"metric": "vgicp_vs_exact_gicp", "device": torch.cuda.get_device_name(0), "settings": DLO, "reps": a.reps, "workloads": {}}
     for name in a.workloads.split(","):
         w = _workload(clouds, name)
