@@ -369,13 +369,22 @@ struct ngicp {
   int filt_n = 0;
 
   // device-resident keyframe store (src/dlo/odom.cc keyframes + keyframe_normals) and the submap assembled from it
+  // A keyframe's voxel part: its own per-voxel sums at one resolution, 88 bytes per occupied voxel.  Built lazily, by a
+  // merged voxel-map build or ngicp_keyframe_voxelmap_get; replaced when the resolution differs; gone with the keyframe.
+  struct VoxelPart {
+    double res = 0.0;
+    size_t n_vox = 0;
+    DevBuf keys, rec;                    // [n_vox] keys ascending, [n_vox][kVoxRec] {sum p 3, sum C 6, count}
+  };
   struct Keyframe {
     std::shared_ptr<DeviceCloud> cloud;  // indexed, cell-sorted
     std::shared_ptr<DevBuf> covs;        // [n][6] FP64 in the cloud's sorted order
+    std::shared_ptr<VoxelPart> part;     // null until asked for
   };
   std::vector<Keyframe> keyframes;
   std::vector<int> submap_ids;           // keyframes of the submap that is the current target (valid while submap_cloud is the target)
   const DeviceCloud* submap_cloud = nullptr;
+  std::weak_ptr<DevBuf> submap_covs;     // the covariance set ngicp_submap_set installed with it (weak: a recycled buffer is another object)
 
   // voxelized GICP (ngicp_voxel.h)
   double voxel_res = 0.0;  // ngicp_set_voxel_resolution: > 0 selects the mode
@@ -387,6 +396,7 @@ struct ngicp {
     std::shared_ptr<DeviceCloud> cloud;  // the target and the covariance set it was built from, HELD: a recycled object cannot take their addresses
     std::shared_ptr<DevBuf> covs;
     size_t n_vox = 0;
+    int merged = 0;                      // the route it was built by: 0 from the target's points, 1 from the submap's keyframe parts
     unsigned int mask = 0;               // hash table slots - 1
     DevBuf rec, vkeys, table;            // [n_vox][kVoxRec] doubles, [n_vox] keys, [mask + 1] {key, voxel number}
     void invalidate() {
@@ -400,6 +410,12 @@ struct ngicp {
   DevBuf vox_keys, vox_vals, vox_scan, vox_flag, vox_corr[2];
   DevBuf vox_mahal[2], vox_corr_out;     // DIRECT7 / DIRECT27: [K][n_src][6] n_v M per slot (DIRECT1 uses the exact path's mahal); the n x K export
   hipEvent_t ev_vox_a = nullptr, ev_vox_b = nullptr;
+  // the submap's map merged from keyframe parts (ngicp_set_voxel_submap_merge)
+  int voxel_merge = 0;                   // the setting; remembered while the voxel mode is off
+  long long merged_builds = 0, parts_built = 0;  // maps built by the merged route / keyframe parts built, since the handle was created
+  double last_parts_ms = 0.0, last_merge_ms = 0.0;  // event times of the last merged build: its part builds, the merge itself
+  DevBuf vox_part_tab;                   // a merged build's table: [m + 1] int offsets, then (8-byte aligned) [m] record pointers
+  hipEvent_t ev_vox_c = nullptr;         // between the parts and the merge
 };
 
 namespace {
@@ -1431,26 +1447,30 @@ void drop_voxel_map(ngicp* h) {
   if (h->voxel_res > 0.0) h->hook_valid = 0;
 }
 
-// The voxel map of the current target, its covariances (computed if missing, as for align) and the resolution: built at the first use
-// after any of the three changed.  Two host synchronisations (the voxel count sizes the map; the build time).
-void ensure_voxel_map(ngicp* h) {
-  ensure_slot_ready(h, h->tgt, "target");
-  if (h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
-  const double* covs = covs_for(h, h->tgt_covs, h->tgt.dev);
-  ngicp::VoxelMap& m = h->vmap;
-  if (m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data) return;
-  m.invalidate();
-  DeviceCloud& T = *h->tgt.dev;
-  const int n = (int)T.n;
-  const float inv_res = 1.0f / (float)h->voxel_res;
+// The working buffers of a voxel build over a list of up to n (key, value) pairs.  Every build sizes them for its longest list before
+// its first launch: growing a buffer frees it, and freeing waits for the device.
+void size_voxel_work(ngicp* h, size_t n) {
+  h->vox_keys.ensure(n * 2 * sizeof(unsigned long long));
+  h->vox_vals.ensure(n * 2 * sizeof(int));
+  h->vox_scan.ensure((n * 3 + 2 + kCellPad) * sizeof(int));
+  h->vox_flag.ensure(64);
+  h->tile_sums.ensure(((n + kScanTile - 1) / kScanTile) * sizeof(int));
+}
+
+// What a build's numbering step leaves on the device: the keys sorted (stable), the values beside them, where every run of equal keys
+// starts (n_seg + 1 entries) and the number of runs.
+struct VoxelSegments {
+  const unsigned long long* keys;
+  const int* order;
+  const int* seg_start;
+  const int* n_seg_dev;
+};
+
+// The n pairs at the front of vox_keys / vox_vals: stable radix sort, segment heads, exclusive scan, segment starts.  Shared by the map
+// of a target's points, a keyframe's part and the merge of parts.  Nothing is synchronised.
+VoxelSegments voxel_segments(ngicp* h, int n) {
   const unsigned blocks = (unsigned)((n + 255) / 256);
   const int ntiles = (n + kScanTile - 1) / kScanTile;
-  // (every buffer is sized before the first launch: growing one frees it, and freeing waits for the device)
-  h->vox_keys.ensure((size_t)n * 2 * sizeof(unsigned long long));
-  h->vox_vals.ensure((size_t)n * 2 * sizeof(int));
-  h->vox_scan.ensure(((size_t)n * 3 + 2 + kCellPad) * sizeof(int));
-  h->vox_flag.ensure(64);
-  h->tile_sums.ensure((size_t)ntiles * sizeof(int));
   unsigned long long* keys_a = h->vox_keys.as<unsigned long long>();
   unsigned long long* keys_b = keys_a + n;
   int* vals_a = h->vox_vals.as<int>();
@@ -1458,9 +1478,6 @@ void ensure_voxel_map(ngicp* h) {
   int* head = h->vox_scan.as<int>();
   int* vox_of = head + n;                    // n + 1 + kCellPad
   int* seg_start = vox_of + n + 1 + kCellPad;  // n + 1
-  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
-  HIP_TRY(hipMemsetAsync(h->vox_flag.p, 0, sizeof(int), h->stream));
-  hipLaunchKernelGGL(k_voxel_map_keys, dim3(blocks), dim3(256), 0, h->stream, T.pts(), n, inv_res, keys_a, vals_a, h->vox_flag.as<int>());
   char err[256] = {0};
   int in_a = 1;
   if (ngk_sort_pairs_u64(h->stream, &h->vox_ws, keys_a, keys_b, vals_a, vals_b, n, kVoxKeyBits, &in_a, err, sizeof(err))) throw ArgError{NGICP_ERR_HIP, err};
@@ -1471,20 +1488,49 @@ void ensure_voxel_map(ngicp* h) {
   hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
   hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)head, n, (const int*)h->tile_sums.as<int>(), vox_of);
   hipLaunchKernelGGL(k_voxel_map_starts, dim3(blocks), dim3(256), 0, h->stream, (const int*)head, (const int*)vox_of, n, seg_start);
-  int n_vox = 0, bad = 0;
-  HIP_TRY(hipMemcpyAsync(&n_vox, vox_of + n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
-  if (bad) throw ArgError{NGICP_ERR_ARG, "voxelized target: a point lies 2^20 voxels or more from the origin on some axis (or is not finite); use a coarser resolution"};
-  if (n_vox <= 0 || n_vox > n) throw ArgError{NGICP_ERR_HIP, "voxel map build: inconsistent voxel count"};
+  return VoxelSegments{keys, order, seg_start, vox_of + n};
+}
+
+// the points of an indexed cloud -> (voxel key, sorted position) pairs in ORIGINAL order at the front of vox_keys / vox_vals, numbered;
+// vox_flag is set when a point has no voxel
+VoxelSegments voxel_segments_of_cloud(ngicp* h, const DeviceCloud& dc) {
+  const int n = (int)dc.n;
+  const float inv_res = 1.0f / (float)h->voxel_res;
+  HIP_TRY(hipMemsetAsync(h->vox_flag.p, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_voxel_map_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, dc.pts(), n, inv_res, h->vox_keys.as<unsigned long long>(), h->vox_vals.as<int>(),
+                     h->vox_flag.as<int>());
+  return voxel_segments(h, n);
+}
+
+// sizes the map's own buffers for n_vox voxels, clears the table and returns its slot count (the stream is idle: the count was just read)
+size_t size_voxel_map(ngicp* h, ngicp::VoxelMap& m, int n_vox) {
   size_t slots = 64;
   while (slots < 2 * (size_t)n_vox) slots <<= 1;
   m.rec.ensure((size_t)n_vox * kVoxRec * sizeof(double));
   m.vkeys.ensure((size_t)n_vox * sizeof(unsigned long long));
   m.table.ensure(slots * sizeof(ulonglong2));
   HIP_TRY(hipMemsetAsync(m.table.p, 0xff, slots * sizeof(ulonglong2), h->stream));
-  hipLaunchKernelGGL(k_voxel_map_fill, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, h->stream, keys, order, (const int*)seg_start, n_vox, T.pts(), covs, m.rec.as<double>(),
+  return slots;
+}
+
+// The map from the target's points, "summed in ascending original target index".  Two host synchronisations (the voxel count sizes the
+// map; the build time).
+void build_voxel_map_from_points(ngicp* h, const double* covs) {
+  ngicp::VoxelMap& m = h->vmap;
+  DeviceCloud& T = *h->tgt.dev;
+  const int n = (int)T.n;
+  size_voxel_work(h, (size_t)n);
+  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+  const VoxelSegments sg = voxel_segments_of_cloud(h, T);
+  int n_vox = 0, bad = 0;
+  HIP_TRY(hipMemcpyAsync(&n_vox, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (bad) throw ArgError{NGICP_ERR_ARG, "voxelized target: a point lies 2^20 voxels or more from the origin on some axis (or is not finite); use a coarser resolution"};
+  if (n_vox <= 0 || n_vox > n) throw ArgError{NGICP_ERR_HIP, "voxel map build: inconsistent voxel count"};
+  const size_t slots = size_voxel_map(h, m, n_vox);
+  hipLaunchKernelGGL(k_voxel_map_fill, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_vox, T.pts(), covs, m.rec.as<double>(),
                      m.vkeys.as<unsigned long long>(), m.table.as<ulonglong2>(), (unsigned int)(slots - 1));
   HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
   HIP_TRY(hipEventSynchronize(h->ev_vox_b));
@@ -1493,6 +1539,127 @@ void ensure_voxel_map(ngicp* h) {
   if (hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess) h->stats.voxelmap_ms = ms;
   m.n_vox = (size_t)n_vox;
   m.mask = (unsigned int)(slots - 1);
+}
+
+// ---- the merged route (include/ngicp.h "merged voxel map") ----
+bool keyframe_part_current(const ngicp* h, const ngicp::Keyframe& kf) { return kf.part && kf.part->res == h->voxel_res; }
+
+// The voxel part of keyframe `id` at the handle's resolution.  The caller has sized the working buffers for the keyframe's points.
+// One host synchronisation (the voxel count sizes the part); the fill is left in the stream.
+void build_keyframe_part(ngicp* h, int id) {
+  ngicp::Keyframe& kf = h->keyframes[(size_t)id];
+  const int n = (int)kf.cloud->n;
+  const VoxelSegments sg = voxel_segments_of_cloud(h, *kf.cloud);
+  int n_vox = 0, bad = 0;
+  HIP_TRY(hipMemcpyAsync(&n_vox, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (bad)
+    throw ArgError{NGICP_ERR_ARG, "voxel part of keyframe " + std::to_string(id) +
+                                      ": a point lies 2^20 voxels or more from the origin on some axis (or is not finite); use a coarser resolution"};
+  if (n_vox <= 0 || n_vox > n) throw ArgError{NGICP_ERR_HIP, "voxel part build: inconsistent voxel count"};
+  auto part = std::make_shared<ngicp::VoxelPart>();
+  part->keys.ensure((size_t)n_vox * sizeof(unsigned long long));
+  part->rec.ensure((size_t)n_vox * kVoxRec * sizeof(double));
+  hipLaunchKernelGGL(k_voxel_part_fill, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_vox, kf.cloud->pts(),
+                     (const double*)kf.covs->as<double>(), part->rec.as<double>(), part->keys.as<unsigned long long>());
+  HIP_TRY(hipGetLastError());
+  part->res = h->voxel_res;
+  part->n_vox = (size_t)n_vox;
+  kf.part = part;  // (a part of another resolution goes here)
+  ++h->parts_built;
+}
+
+// Is the current target the device submap with the covariances ngicp_submap_set gave it?  Only then is the map a function of the
+// keyframes' parts; after ngicp_set_target_covs / ngicp_compute_target_covs it is built from the points.
+bool merged_route_applies(const ngicp* h) {
+  if (!h->voxel_merge || h->submap_ids.empty() || !h->tgt.dev || h->tgt.dev.get() != h->submap_cloud || !h->tgt_covs.data) return false;
+  return h->submap_covs.lock() == h->tgt_covs.data;
+}
+
+// The map of the submap `submap_ids` from its keyframes' parts: missing parts are built (one synchronisation each), the parts' keys are
+// gathered in list order with their global record position, sorted (stable: a voxel's parts stay in list order), numbered, and one
+// thread per merged voxel adds its parts and divides.  Two more synchronisations: the merged count, the time.
+void build_voxel_map_merged(ngicp* h) {
+  ngicp::VoxelMap& m = h->vmap;
+  const std::vector<int>& ids = h->submap_ids;
+  const size_t mk = ids.size();
+  size_t longest = 1, bound = 0;  // the longest list a part build sorts; an upper bound of the gathered list (a missing part: its points)
+  for (int id : ids) {
+    const ngicp::Keyframe& kf = h->keyframes[(size_t)id];
+    const bool have = keyframe_part_current(h, kf);
+    if (!have) longest = std::max(longest, kf.cloud->n);
+    bound += have ? kf.part->n_vox : kf.cloud->n;
+  }
+  if (bound > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "merged voxel map: too many keyframe voxels for int indices"};
+  size_voxel_work(h, std::max(longest, bound));
+  const size_t tab_off = ((mk + 1) * sizeof(int) + 7) / 8 * 8, tab_bytes = tab_off + mk * sizeof(const double*);
+  h->vox_part_tab.ensure(tab_bytes);
+  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+  for (int id : ids)
+    if (!keyframe_part_current(h, h->keyframes[(size_t)id])) build_keyframe_part(h, id);
+  HIP_TRY(hipEventRecord(h->ev_vox_c, h->stream));
+  std::vector<unsigned char> tab(tab_bytes, 0);  // (lives until the synchronisation below: the copy may read it late)
+  int* off = reinterpret_cast<int*>(tab.data());
+  const double** recs = reinterpret_cast<const double**>(tab.data() + tab_off);
+  size_t total = 0;
+  for (size_t i = 0; i < mk; ++i) {
+    const ngicp::VoxelPart& part = *h->keyframes[(size_t)ids[i]].part;
+    off[i] = (int)total;
+    recs[i] = part.rec.as<double>();
+    total += part.n_vox;
+  }
+  off[mk] = (int)total;
+  const int G = (int)total;
+  HIP_TRY(hipMemcpyAsync(h->vox_part_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
+  for (size_t i = 0; i < mk; ++i) {
+    const ngicp::VoxelPart& part = *h->keyframes[(size_t)ids[i]].part;
+    const int nk = (int)part.n_vox;
+    hipLaunchKernelGGL(k_voxel_part_gather, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream, (const unsigned long long*)part.keys.as<unsigned long long>(), nk, off[i],
+                       h->vox_keys.as<unsigned long long>(), h->vox_vals.as<int>());
+  }
+  VoxelSegments sg{};
+  try {
+    sg = voxel_segments(h, G);
+  } catch (...) {
+    (void)hipStreamSynchronize(h->stream);  // the upload of `tab` may still be pending: it must not outlive the vector
+    throw;
+  }
+  int n_vox = 0;
+  HIP_TRY(hipMemcpyAsync(&n_vox, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (n_vox <= 0 || n_vox > G) throw ArgError{NGICP_ERR_HIP, "merged voxel map build: inconsistent voxel count"};
+  const size_t slots = size_voxel_map(h, m, n_vox);
+  hipLaunchKernelGGL(k_voxel_merge_fill, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_vox,
+                     (const int*)h->vox_part_tab.as<int>(), reinterpret_cast<const double* const*>(h->vox_part_tab.as<unsigned char>() + tab_off), (int)mk, m.rec.as<double>(),
+                     m.vkeys.as<unsigned long long>(), m.table.as<ulonglong2>(), (unsigned int)(slots - 1));
+  HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
+  HIP_TRY(hipEventSynchronize(h->ev_vox_b));
+  HIP_TRY(hipGetLastError());
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess) h->stats.voxelmap_ms = ms;
+  if (hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_c) == hipSuccess) h->last_parts_ms = ms;
+  if (hipEventElapsedTime(&ms, h->ev_vox_c, h->ev_vox_b) == hipSuccess) h->last_merge_ms = ms;
+  m.n_vox = (size_t)n_vox;
+  m.mask = (unsigned int)(slots - 1);
+  ++h->merged_builds;
+}
+
+// The voxel map of the current target, its covariances (computed if missing, as for align) and the resolution: built at the first use
+// after any of the three changed, or after the route it would be built by did (ngicp_set_voxel_submap_merge).
+void ensure_voxel_map(ngicp* h) {
+  ensure_slot_ready(h, h->tgt, "target");
+  if (h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
+  const double* covs = covs_for(h, h->tgt_covs, h->tgt.dev);
+  ngicp::VoxelMap& m = h->vmap;
+  const int merged = merged_route_applies(h) ? 1 : 0;
+  if (m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && m.merged == merged) return;
+  m.invalidate();
+  if (merged) build_voxel_map_merged(h);
+  else build_voxel_map_from_points(h, covs);
+  m.merged = merged;
   m.res = h->voxel_res;
   m.cloud = h->tgt.dev;
   m.covs = h->tgt_covs.data;
@@ -2103,6 +2270,7 @@ int ngicp_create(int device, ngicp_t** out) {
     HIP_TRY(hipEventCreate(&h->ev_q_b));
     HIP_TRY(hipEventCreate(&h->ev_vox_a));
     HIP_TRY(hipEventCreate(&h->ev_vox_b));
+    HIP_TRY(hipEventCreate(&h->ev_vox_c));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_state), 2 * sizeof(LmState), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_final), sizeof(LmHot), hipHostMallocDefault));
     h->order_flag.ensure(64);
@@ -2192,6 +2360,7 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_q_b) (void)hipEventDestroy(h->ev_q_b);
   if (h->ev_vox_a) (void)hipEventDestroy(h->ev_vox_a);
   if (h->ev_vox_b) (void)hipEventDestroy(h->ev_vox_b);
+  if (h->ev_vox_c) (void)hipEventDestroy(h->ev_vox_c);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -2631,6 +2800,62 @@ int ngicp_voxelmap_get(ngicp_t* h, int* ijk_n3, double* mean_n3, double* cov_n6,
       }
       if (mean_n3) std::memcpy(mean_n3 + 3 * v, &rec[v * kVoxRec], 3 * sizeof(double));
       if (cov_n6) std::memcpy(cov_n6 + 6 * v, &rec[v * kVoxRec + 3], 6 * sizeof(double));
+      if (count_n) count_n[v] = (int)rec[v * kVoxRec + 9];
+    }
+  });
+}
+
+int ngicp_set_voxel_submap_merge(ngicp_t* h, int on) {
+  return guarded(h, [&] {
+    const int v = on ? 1 : 0;
+    if (v == h->voxel_merge) return;
+    h->voxel_merge = v;
+    h->vmap.invalidate();  // (rebuilt at the next use, by whichever route then applies)
+    h->hook_valid = 0;     // as a change of resolution: the hooks' state and the correspondences go with the map
+  });
+}
+
+int ngicp_get_voxel_submap_merge(const ngicp_t* h, int* on) {
+  if (!h || !on) return NGICP_ERR_ARG;
+  *on = h->voxel_merge;
+  return NGICP_OK;
+}
+
+int ngicp_voxelmap_merge_stats(const ngicp_t* h, long long* merged_builds, long long* parts_built, double* last_parts_ms, double* last_merge_ms) {
+  if (!h) return NGICP_ERR_ARG;
+  if (merged_builds) *merged_builds = h->merged_builds;
+  if (parts_built) *parts_built = h->parts_built;
+  if (last_parts_ms) *last_parts_ms = h->last_parts_ms;
+  if (last_merge_ms) *last_merge_ms = h->last_merge_ms;
+  return NGICP_OK;
+}
+
+int ngicp_keyframe_voxelmap_get(ngicp_t* h, int id, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n) {
+  return guarded(h, [&] {
+    if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "no voxel resolution set (ngicp_set_voxel_resolution)"};
+    if (id < 0 || (size_t)id >= h->keyframes.size()) throw ArgError{NGICP_ERR_ARG, "unknown keyframe id"};
+    ngicp::Keyframe& kf = h->keyframes[(size_t)id];
+    if (!keyframe_part_current(h, kf)) {
+      size_voxel_work(h, kf.cloud->n);
+      build_keyframe_part(h, id);
+    }
+    const size_t nv = kf.part->n_vox;
+    if (n_vox) *n_vox = nv;
+    if (!ijk_n3 && !sum_n3 && !covsum_n6 && !count_n) return;
+    std::vector<double> rec(nv * kVoxRec);
+    std::vector<unsigned long long> keys(nv);
+    HIP_TRY(hipMemcpyAsync(rec.data(), kf.part->rec.p, rec.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(keys.data(), kf.part->keys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    for (size_t v = 0; v < nv; ++v) {
+      if (ijk_n3) {
+        ijk_n3[3 * v + 0] = (int)(keys[v] & 0x1fffffull) - kVoxBias;
+        ijk_n3[3 * v + 1] = (int)((keys[v] >> 21) & 0x1fffffull) - kVoxBias;
+        ijk_n3[3 * v + 2] = (int)((keys[v] >> 42) & 0x1fffffull) - kVoxBias;
+      }
+      if (sum_n3) std::memcpy(sum_n3 + 3 * v, &rec[v * kVoxRec], 3 * sizeof(double));
+      if (covsum_n6) std::memcpy(covsum_n6 + 6 * v, &rec[v * kVoxRec + 3], 6 * sizeof(double));
       if (count_n) count_n[v] = (int)rec[v * kVoxRec + 9];
     }
   });
@@ -3129,6 +3354,7 @@ int ngicp_submap_set(ngicp_t* h, const int* ids, size_t n_ids, int* changed_out)
     h->tgt_covs.order = dc;
     h->submap_ids.assign(ids, ids + n_ids);
     h->submap_cloud = dc.get();
+    h->submap_covs = buf;
     drop_voxel_map(h);
     h->hook_valid = 0;
     h->stats.submap_ms = now_ms() - t0;

@@ -29,6 +29,11 @@
 //                                 k_vgicp_pass itself serves DIRECT1 and is not touched by any of this.
 //   vgicp_pass_body / vgicp_pass_n_body<K>   what the two kernels do once they hold the state's pose and flags, as inlined functions:
 //                                 k_vgicp_pass_batch<K> (ngicp_voxel_batch.h) runs the same bodies on a lane's record.
+//   merged voxel map              (a setting, off by default) the map of a submap from sums its keyframes carry:
+//                                 k_voxel_part_fill (one keyframe's per-voxel sums, no division), k_voxel_part_gather (the parts' keys in
+//                                 the order of the id list, value = global record position), the same stable sort and numbering, and
+//                                 k_voxel_merge_fill (one thread per voxel adds its parts in list order and divides once).  The record
+//                                 format, the numbering and the table are the map's above; the passes do not know the difference.
 #pragma once
 #include "ngicp_pass.h"
 
@@ -123,6 +128,92 @@ __global__ void __launch_bounds__(256) k_voxel_map_fill(const unsigned long long
 #pragma unroll
   for (int k = 0; k < 6; ++k) r[3 + k] = c[k] / cnt;
   r[9] = cnt;
+  const unsigned long long key = keys[s];
+  vkeys[v] = key;
+  unsigned int slot = voxel_hash(key, mask);
+  for (unsigned int t = 0; t <= mask; ++t) {  // (keys are distinct and the table is at most half full: a free slot comes)
+    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(&table[slot]), kVoxEmpty, key);
+    if (prev == kVoxEmpty) {
+      table[slot].y = (unsigned long long)v;
+      break;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+// ---- a submap's map merged from per-keyframe voxel sums (include/ngicp.h "merged voxel map") -------------------------
+// The voxel part of ONE keyframe: k_voxel_map_fill without the division and without the table.  A record holds the sums themselves,
+// {sum (double)p 3, sum C 6, count}, each started at 0.0 and added in segment order = ascending original index inside the keyframe;
+// the sorted key of voxel v goes to pkeys[v].
+__global__ void __launch_bounds__(256) k_voxel_part_fill(const unsigned long long* __restrict__ keys, const int* __restrict__ order, const int* __restrict__ seg_start, int n_vox,
+                                                          const float4* __restrict__ pts, const double* __restrict__ covs, double* __restrict__ rec,
+                                                          unsigned long long* __restrict__ pkeys) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_vox) return;
+  const int s = seg_start[v], e = seg_start[v + 1];
+  double m[3] = {0.0, 0.0, 0.0}, c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = s; j < e; ++j) {
+    const int p = order[j];
+    const float4 q = pts[p];
+    m[0] += (double)q.x;
+    m[1] += (double)q.y;
+    m[2] += (double)q.z;
+    const double* C = covs + (size_t)p * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] += C[k];
+  }
+  double* r = rec + (size_t)v * kVoxRec;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) r[k] = m[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) r[3 + k] = c[k];
+  r[9] = (double)(e - s);
+  pkeys[v] = keys[s];
+}
+
+// One listed keyframe's part keys into the gathered list at `offset`; the value is the GLOBAL part-record position offset + j (the
+// stable sort then keeps a voxel's parts in the order of the id list).
+__global__ void __launch_bounds__(256) k_voxel_part_gather(const unsigned long long* __restrict__ pkeys, int n, int offset, unsigned long long* __restrict__ keys,
+                                                            int* __restrict__ vals) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  keys[offset + j] = pkeys[j];
+  vals[offset + j] = offset + j;
+}
+
+// One thread per merged voxel: S = the first part record of its segment, then S + the next ones in segment order (ten doubles each,
+// the count among them: exact), one division, the record, the key and the table entry exactly as k_voxel_map_fill writes them.
+// part_off[0..m]: where each listed keyframe's records start in the gathered numbering (ascending, part_off[m] = the total);
+// part_rec[i]: that keyframe's records.  An id listed twice has two entries.
+__global__ void __launch_bounds__(256) k_voxel_merge_fill(const unsigned long long* __restrict__ keys, const int* __restrict__ order, const int* __restrict__ seg_start, int n_vox,
+                                                           const int* __restrict__ part_off, const double* const* __restrict__ part_rec, int m, double* __restrict__ rec,
+                                                           unsigned long long* __restrict__ vkeys, ulonglong2* __restrict__ table, unsigned int mask) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n_vox) return;
+  const int s = seg_start[v], e = seg_start[v + 1];
+  double S[kVoxRec];
+  for (int j = s; j < e; ++j) {
+    const int g = order[j];
+    int lo = 0, hi = m;  // the last i with part_off[i] <= g (parts are never empty: the offsets are strictly ascending)
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (part_off[mid] <= g) lo = mid;
+      else hi = mid;
+    }
+    const double* r = part_rec[lo] + (size_t)(g - part_off[lo]) * kVoxRec;
+    if (j == s) {
+#pragma unroll
+      for (int k = 0; k < kVoxRec; ++k) S[k] = r[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < kVoxRec; ++k) S[k] = S[k] + r[k];
+    }
+  }
+  const double cnt = S[9];
+  double* out = rec + (size_t)v * kVoxRec;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) out[k] = S[k] / cnt;
+  out[9] = cnt;
   const unsigned long long key = keys[s];
   vkeys[v] = key;
   unsigned int slot = voxel_hash(key, mask);

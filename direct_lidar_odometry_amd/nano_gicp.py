@@ -88,6 +88,7 @@ EXPORTS = [
     "ngicp_set_voxel_resolution", "ngicp_voxelmap_size", "ngicp_voxelmap_get",
     "ngicp_set_voxel_neighbors", "ngicp_get_voxel_neighbors", "ngicp_voxel_correspondences", "ngicp_voxelmap_builds",
     "ngicp_voxel_align_batch",
+    "ngicp_set_voxel_submap_merge", "ngicp_get_voxel_submap_merge", "ngicp_voxelmap_merge_stats", "ngicp_keyframe_voxelmap_get",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -180,6 +181,10 @@ def load_library() -> C.CDLL:
     L.ngicp_get_voxel_neighbors.argtypes = [vp, c_i32p]
     L.ngicp_voxel_correspondences.argtypes = [vp, c_i32p, C.c_size_t, c_i32p]
     L.ngicp_voxelmap_builds.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.ngicp_set_voxel_submap_merge.argtypes = [vp, C.c_int]
+    L.ngicp_get_voxel_submap_merge.argtypes = [vp, c_i32p]
+    L.ngicp_voxelmap_merge_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_f64p, c_f64p]
+    L.ngicp_keyframe_voxelmap_get.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t), c_i32p, c_f64p, c_f64p, c_i32p]
     _lib = L
     return L
 
@@ -309,6 +314,33 @@ class NanoGICP:
         self._ck(self._L.ngicp_voxelmap_get(self._h, _p(ijk, c_i32p), _p(mean, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p)))
         cov = c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(n, 3, 3)
         return ijk, mean, cov, cnt
+
+    def setVoxelSubmapMerge(self, on: bool):
+        """Off (the default): the voxel map of every target is summed over its points.  On: the map of a submap assembled by
+        setSubmapKeyframes is merged from per-keyframe voxel sums, built once per keyframe and resolution (include/ngicp.h "merged voxel
+        map": the same voxels and counts, means and covariances that differ in rounding only).  Remembered while the voxel mode is off."""
+        self._ck(self._L.ngicp_set_voxel_submap_merge(self._h, 1 if on else 0))
+
+    def getVoxelSubmapMerge(self) -> bool:
+        on = C.c_int(0)
+        self._ck(self._L.ngicp_get_voxel_submap_merge(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def voxelMapMergeStats(self) -> dict:
+        """{merged_builds, parts_built: since the handle was created; last_parts_ms, last_merge_ms: device time of the last merged build}."""
+        mb, pb, tp, tm = C.c_longlong(0), C.c_longlong(0), C.c_double(0), C.c_double(0)
+        self._ck(self._L.ngicp_voxelmap_merge_stats(self._h, C.byref(mb), C.byref(pb), C.byref(tp), C.byref(tm)))
+        return dict(merged_builds=mb.value, parts_built=pb.value, last_parts_ms=tp.value, last_merge_ms=tm.value)
+
+    def keyframeVoxelMap(self, kid: int):
+        """-> (ijk (V, 3) int32, sum (V, 3), covsum (V, 3, 3), count (V,) int32): the voxel part of keyframe `kid` at the current
+        resolution (sums, not means), voxels in ascending (iz, iy, ix); built if absent."""
+        nv = C.c_size_t(0)
+        self._ck(self._L.ngicp_keyframe_voxelmap_get(self._h, int(kid), C.byref(nv), None, None, None, None))
+        n = nv.value
+        ijk = np.empty((n, 3), dtype=np.int32); s = np.empty((n, 3)); c6 = np.empty((n, 6)); cnt = np.empty(n, dtype=np.int32)
+        self._ck(self._L.ngicp_keyframe_voxelmap_get(self._h, int(kid), C.byref(nv), _p(ijk, c_i32p), _p(s, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p)))
+        return ijk, s, c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(n, 3, 3), cnt
 
     def setTuning(self, voxel_size: float = 0.0, lanes_per_query: int = 0):
         self._ck(self._L.ngicp_set_tuning(self._h, float(voxel_size), int(lanes_per_query)))

@@ -400,6 +400,47 @@ class NanoGICP {
     if (!check(ngicp_voxel_correspondences(h_, out.data(), out.size(), &K), "voxelCorrespondences")) out.clear();
     return out;
   }
+  // setVoxelSubmapMerge(true): the voxel map of a submap assembled by setSubmapKeyframes is merged from per-keyframe voxel sums, which
+  // every keyframe carries and which are built once per keyframe and resolution, instead of being summed over all points of the submap
+  // at every change (include/ngicp.h "merged voxel map").  The voxels, their numbers and their counts are the same; means and covariances
+  // differ in rounding only (the sums are grouped by keyframe).  OFF by default; with it off nothing changes.  Every other target, and a
+  // submap whose covariances were replaced, is summed over its points as before.  Remembered while the voxel mode is off; a change
+  // drops the voxel map.
+  void setVoxelSubmapMerge(bool on) {
+    if (h_) check(ngicp_set_voxel_submap_merge(h_, on ? 1 : 0), "setVoxelSubmapMerge");
+  }
+  bool getVoxelSubmapMerge() const {
+    int on = 0;
+    if (h_) check(ngicp_get_voxel_submap_merge(h_, &on), "getVoxelSubmapMerge");
+    return on != 0;
+  }
+  // maps built by the merged route and keyframe parts built since this object was created; device time of the last merged build
+  struct VoxelMapMergeStats {
+    long long merged_builds = 0, parts_built = 0;
+    double last_parts_ms = 0.0, last_merge_ms = 0.0;
+  };
+  VoxelMapMergeStats voxelMapMergeStats() const {
+    VoxelMapMergeStats s;
+    if (h_) check(ngicp_voxelmap_merge_stats(h_, &s.merged_builds, &s.parts_built, &s.last_parts_ms, &s.last_merge_ms), "voxelMapMergeStats");
+    return s;
+  }
+  // the voxel part of keyframe `id` at the current resolution (built if absent): per voxel in ascending (iz, iy, ix) the index, the sum
+  // of the points, the sum of the covariances {xx, xy, xz, yy, yz, zz} and the count.  Empty on error (and while the voxel mode is off).
+  struct KeyframeVoxelMap {
+    std::vector<int> ijk;         // n x 3
+    std::vector<double> sum;      // n x 3
+    std::vector<double> covsum;   // n x 6
+    std::vector<int> count;       // n
+    size_t size() const { return count.size(); }
+  };
+  KeyframeVoxelMap keyframeVoxelMap(int id) {
+    KeyframeVoxelMap m;
+    size_t n = 0;
+    if (!h_ || !check(ngicp_keyframe_voxelmap_get(h_, id, &n, nullptr, nullptr, nullptr, nullptr), "keyframeVoxelMap")) return m;
+    m.ijk.resize(3 * n); m.sum.resize(3 * n); m.covsum.resize(6 * n); m.count.resize(n);
+    if (!check(ngicp_keyframe_voxelmap_get(h_, id, &n, m.ijk.data(), m.sum.data(), m.covsum.data(), m.count.data()), "keyframeVoxelMap")) m = KeyframeVoxelMap();
+    return m;
+  }
 
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
   // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN

@@ -238,6 +238,41 @@ int ngicp_voxelmap_size(ngicp_t* h, size_t* n_voxels);
 /* the map, voxels in the numbering above: ijk (n x 3 ints), mean (n x 3), cov (n x 6: xx, xy, xz, yy, yz, zz), count (n).  Every
  * pointer may be NULL.  Builds the map if it is stale. */
 int ngicp_voxelmap_get(ngicp_t* h, int* ijk_n3, double* mean_n3, double* cov_n6, int* count_n);
+/* --- merged voxel map: a submap's map from per-keyframe voxel sums (csrc/ngicp_voxel.h) ---------------------------
+ * A SETTING of the voxelized mode, OFF by default.  With it off nothing changes anywhere: the map of every target is the one defined
+ * above, summed over the concatenation.  With it on, the map of a target that ngicp_submap_set assembled is formed from sums each
+ * keyframe carries, built once per keyframe and resolution.  That adds per-keyframe partial sums and is therefore NOT the definition
+ * above; it has this one of its own.
+ *   voxel part of keyframe k   over the keyframe's points as the store holds them (world frame), with the voxel rule above
+ *   at resolution res          (floorf(p * inv_res), |i| < 2^20): for every voxel v that holds a point of k, n_kv, s_kv = sum (double)p_j
+ *                              (3 entries) and c_kv = sum C_j (6 entries).  Every sum starts at 0.0 and adds one term after the other in
+ *                              ascending original index inside the keyframe.  Voxels in ascending (iz, iy, ix).  No division.  A point
+ *                              2^20 voxels or more from the origin, or a non-finite one, refuses the build with NGICP_ERR_ARG; the
+ *                              message names the keyframe id.  88 bytes of device memory per keyframe voxel.
+ *   merged map of ids[0..m)    voxel v is occupied if any listed keyframe's part has it.  With i_1 < ... < i_r the positions in ids
+ *                              whose part has v: S = s_{ids[i_1], v}, then S = S + s_{ids[i_t], v} for t = 2..r; C likewise from the c
+ *                              sums; n_v = sum n.  mean_v = S / (double)n_v, cov_v = C / (double)n_v.  An id listed twice counts twice,
+ *                              as it does in the concatenation.
+ * The map keeps its format, its voxel numbering and its key table; the passes are the same kernels.  Consequences: ijk, counts and voxel
+ * numbers are exactly those of the map defined above for the same submap, so correspondences at a given pose are identical; means and
+ * covariances differ from it in rounding only; with a single id the two maps are bit-equal.
+ * The merged route is taken only when the setting is on, the current target is the submap ngicp_submap_set assembled, and its
+ * covariances are still the set ngicp_submap_set installed: after ngicp_set_target_covs or ngicp_compute_target_covs the map is built
+ * from the points, as for any other target.  A part is built lazily (only a merged build or ngicp_keyframe_voxelmap_get asks for one),
+ * replaced when the resolution differs, and freed by ngicp_keyframe_clear.
+ * ngicp_set_voxel_submap_merge: on != 0 switches the setting on.  It may be called whether or not the voxel mode is on, and is
+ * remembered.  Setting the value already set does nothing.  A change drops the voxel map, the hooks' state and the correspondences, as a
+ * change of resolution does.  ngicp_stats::voxelmap_ms and ngicp_voxelmap_builds keep their meaning: the last build and all builds, by
+ * either route. */
+int ngicp_set_voxel_submap_merge(ngicp_t* h, int on);
+int ngicp_get_voxel_submap_merge(const ngicp_t* h, int* on);
+/* maps built by the merged route and keyframe parts built, both since the handle was created; the device (event) times of the last
+ * merged build, split into its part builds (0 when every part was there) and the merge itself.  Every pointer may be NULL. */
+int ngicp_voxelmap_merge_stats(const ngicp_t* h, long long* merged_builds, long long* parts_built, double* last_parts_ms, double* last_merge_ms);
+/* the voxel part of keyframe `id` at the current resolution, built if absent: *n_vox voxels; ijk (n x 3 ints), sum (n x 3),
+ * covsum (n x 6: xx, xy, xz, yy, yz, zz), count (n).  The array pointers may be NULL to ask for the size only.  NGICP_ERR_STATE while
+ * the voxel mode is off, NGICP_ERR_ARG for an unknown id. */
+int ngicp_keyframe_voxelmap_get(ngicp_t* h, int id, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
