@@ -927,9 +927,9 @@ int ngicp_fitness_score_batch(ngicp_t* h, size_t n, const float* T_colmajor, dou
     for (size_t at = 0; at < n; at += chunk) {
       const size_t m = std::min(chunk, n - at);
       HIP_TRY(hipMemcpyAsync(w.fit_T.p, T_colmajor + at * 16, m * 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(k_fitness_batch, dim3((unsigned)nb, (unsigned)m), dim3(kKnnBlock), 0, h->stream, S.pts(), np, w.fit_T.as<float>(), T.pts(), T.cells(), T.grid, max_range,
+      hipLaunchKernelGGL(k_fitness, dim3((unsigned)nb, (unsigned)m), dim3(kKnnBlock), 0, h->stream, S.pts(), np, w.fit_T.as<float>(), T.pts(), T.cells(), T.grid, max_range,
                          w.fit_part.as<double2>());
-      hipLaunchKernelGGL(k_fitness_final_batch, dim3((unsigned)m), dim3(kFitnessFinalBlock), 0, h->stream, w.fit_part.as<double2>(), nb, w.fit_out.as<double2>());
+      hipLaunchKernelGGL(k_fitness_final, dim3((unsigned)m), dim3(kFitnessFinalBlock), 0, h->stream, w.fit_part.as<double2>(), nb, w.fit_out.as<double2>());
       HIP_TRY(hipMemcpyAsync(r.data() + at, w.fit_out.p, m * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(hipStreamSynchronize(h->stream));
     }
@@ -1267,7 +1267,7 @@ int ngicp_fitness_score(ngicp_t* h, const float T_colmajor[16], double max_range
     h->fit_out.ensure(sizeof(double2));
     HIP_TRY(hipMemcpyAsync(h->fit_T.p, T_colmajor ? T_colmajor : h->final_T, 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipEventRecord(h->ev_q_a, h->stream));
-    hipLaunchKernelGGL(k_fitness, dim3((unsigned)nb), dim3(kKnnBlock), 0, h->stream, S.pts(), n, h->fit_T.as<float>(), T.pts(), T.cells(), T.grid, max_range,
+    hipLaunchKernelGGL(k_fitness, dim3((unsigned)nb, 1u), dim3(kKnnBlock), 0, h->stream, S.pts(), n, h->fit_T.as<float>(), T.pts(), T.cells(), T.grid, max_range,
                        h->fit_part.as<double2>());
     hipLaunchKernelGGL(k_fitness_final, dim3(1), dim3(kFitnessFinalBlock), 0, h->stream, h->fit_part.as<double2>(), nb, h->fit_out.as<double2>());
     HIP_TRY(hipEventRecord(h->ev_q_b, h->stream));

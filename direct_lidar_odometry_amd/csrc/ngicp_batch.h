@@ -9,8 +9,8 @@
 //   k_lm_solve_batch            grid (live lanes): block l runs lm_solve_body<512, false> - k_lm_solve's body - on its lane's SolveArgs
 //                               record: own rows, state, trace, launch order, and own {progress word, final image} in pinned memory
 //                               (the image is stored before the word, and the device state before both: lm_solve_body).
-//   k_fitness_batch / k_fitness_final_batch   k_fitness with a lane dimension: B transforms, one launch, per lane the same per-point
-//                               work and the same fixed FP64 order of sums.
+//   k_fitness / k_fitness_final (ngicp_query.h)   the fitness kernels have a lane dimension of their own (grid row = transform): B
+//                               transforms are one launch of the kernels that ngicp_fitness_score launches with one row.
 // Which lanes a launch serves travels in its kernel arguments (BatchLaunch::lane): the host drops a lane from the list when it sees
 // that lane's done flag, without a copy; the launches already enqueued return at the head of the lane's blocks, as stale launches of
 // the single path do.
@@ -32,7 +32,9 @@ typedef const BatchLaunch __attribute__((address_space(4))) KernelBatchLaunch;
 
 // One group of one pass of one lane: the prologue of persist_group_body<.., RING = false> (arguments through the constant address space,
 // the pose from the state itself, rows stored plainly: the solver is a launch of its own) with k_gicp_pass's scalar wave number, then the
-// body every pass kernel includes.  Inlined into the kernel: no call, the search keeps its registers.
+// body every pass kernel includes.  Inlined into the kernel: no call, the search keeps its registers.  (The pose is read here and not
+// with load_pose, ngicp_pass.h: with it k_gicp_pass_batch's code came out different, six instructions shorter, and the exact route's
+// code objects are kept as they are.)
 #define NG_STAMP(k) \
   do {              \
   } while (0)  // (the batch path records no stamps)
@@ -51,8 +53,7 @@ __device__ __forceinline__ void batch_group_body(KernelPassArgs& a, const int gr
   g.slack = a.grid.slack;
   typedef const double __attribute__((address_space(4))) * ViewPtrD;
   typedef const float __attribute__((address_space(4))) * ViewPtrF;
-  typedef const LmState __attribute__((address_space(4))) * StatePtr;
-  StatePtr st4 = (StatePtr)(unsigned long long)a.st;
+  KernelStatePtr st4 = (KernelStatePtr)(unsigned long long)a.st;
   const int have_lin = st4->hot.have_lin;
   const int cur = st4->hot.cur & 1, nxt = cur ^ 1;
   ViewPtrD vx = (ViewPtrD)&st4->hot.xi;  // (Pose: R[9] then t[3])
@@ -92,8 +93,7 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass_batch(BatchLaunch bl) {
   const int lane_id = kb->lane[blockIdx.y];
   KernelPassArgs* ka = (KernelPassArgs*)(unsigned long long)(reinterpret_cast<const PassArgs*>(kb->pass) + lane_id);
   typedef const int __attribute__((address_space(4))) * ConstIntPtr;
-  typedef const LmState __attribute__((address_space(4))) * StatePtr;
-  const int done_now = ((StatePtr)(unsigned long long)ka->st)->hot.done;
+  const int done_now = ((KernelStatePtr)(unsigned long long)ka->st)->hot.done;
   const int order_is_valid = *(ConstIntPtr)(unsigned long long)ka->order_valid;
   const int order_entry = ((ConstIntPtr)(unsigned long long)ka->grp_order)[blockIdx.x];
   asm volatile("" ::"s"(done_now), "s"(order_is_valid), "s"(order_entry));  // (all three in flight before the first is looked at)
@@ -117,67 +117,6 @@ __global__ void __launch_bounds__(kSolveThreads) k_lm_solve_batch(BatchLaunch bl
   SolveArgs a;
   __builtin_memcpy(&a, w, sizeof(a));
   lm_solve_body<kSolveThreads, false>(a, sh);
-}
-
-// k_fitness for transform blockIdx.y of T_colmajor[B][16]: partials[blockIdx.y * gridDim.x + blockIdx.x] = {sum of the counted d2, count}.
-// (the same statements as k_fitness, ngicp_query.h: per lane of the batch the sums come out bit for bit as ngicp_fitness_score's)
-__global__ void __launch_bounds__(kKnnBlock) k_fitness_batch(const float4* __restrict__ src_sorted, int n, const float* __restrict__ T_colmajor,
-                                                             const float4* __restrict__ tgt_sorted, const int* __restrict__ tgt_cells, Grid g, double max_range,
-                                                             double2* __restrict__ partials) {
-  __shared__ int lds_bounds[36 * kKnnPairs];
-  __shared__ double2 wave_part[kKnnBlock / 64];
-  const float* __restrict__ Tm = T_colmajor + (size_t)blockIdx.y * 16;
-  const int lane = threadIdx.x & 63, sub = threadIdx.x & 1, pair = threadIdx.x >> 1;
-  const int i = blockIdx.x * kKnnPairs + pair;
-  double s = 0.0, c = 0.0;
-  if (i < n) {
-    const float4 p = src_sorted[i];
-    const float3 t = transform_point_f(Tm, p.x, p.y, p.z);
-    PairTopK<2> top;
-    knn_search<2, 4>(g, tgt_sorted, tgt_cells, t.x, t.y, t.z, -1, 1, top, lds_bounds + pair, sub, lane);
-    const float d2 = top.part.template d<0>();  // slot 0 lives in lane 0 of the pair
-    if (sub == 0 && (double)d2 <= max_range) {
-      s = (double)d2;
-      c = 1.0;
-    }
-  }
-  s = wave_sum(s);
-  c = wave_sum(c);
-  if (lane == 0) wave_part[threadIdx.x >> 6] = make_double2(s, c);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double2 r = wave_part[0];
-#pragma unroll
-    for (int w = 1; w < kKnnBlock / 64; ++w) {
-      r.x += wave_part[w].x;
-      r.y += wave_part[w].y;
-    }
-    partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = r;
-  }
-}
-
-// block l: out[l] = the sum of partials[l * nb .. l * nb + nb), in k_fitness_final's order
-__global__ void __launch_bounds__(kFitnessFinalBlock) k_fitness_final_batch(const double2* __restrict__ partials, int nb, double2* __restrict__ out) {
-  __shared__ double2 wave_part[kFitnessFinalBlock / 64];
-  const double2* __restrict__ mine = partials + (size_t)blockIdx.x * nb;
-  double s = 0.0, c = 0.0;
-  for (int b = threadIdx.x; b < nb; b += kFitnessFinalBlock) {
-    s += mine[b].x;
-    c += mine[b].y;
-  }
-  s = wave_sum(s);
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = make_double2(s, c);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double2 r = wave_part[0];
-#pragma unroll
-    for (int w = 1; w < kFitnessFinalBlock / 64; ++w) {
-      r.x += wave_part[w].x;
-      r.y += wave_part[w].y;
-    }
-    out[blockIdx.x] = r;
-  }
 }
 
 }  // namespace ngk

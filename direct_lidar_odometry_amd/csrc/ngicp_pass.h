@@ -32,6 +32,53 @@ constexpr int kNumSums = 29;
 constexpr int kNumSlots = 32;      // + candidates tested, valid correspondences, queries served through the LDS row list (exact integers carried as doubles)
 constexpr int kTraceCols = 8;
 
+// K3 of one correspondence, the only definition (every pass kernel, exact and voxelized, calls it): residual e = b - T a, Mahalanobis
+// matrix M = {m00, m01, m02, m11, m12, m22}, Ta = T a; adds y0 to acc[27], H's upper triangle to acc[0..20] and b to acc[21..26]
+// (impl/nano_gicp_impl.hpp:232-257).  Statement order and parentheses are the result's bits: nothing here may be reassociated or fused.
+__device__ __forceinline__ void lin_terms(double (&acc)[kNumSums], const double tax, const double tay, const double taz, const double ex, const double ey, const double ez,
+                                          const double (&M)[6]) {
+  const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+  const double mex = m00 * ex + m01 * ey + m02 * ez;
+  const double mey = m01 * ex + m11 * ey + m12 * ez;
+  const double mez = m02 * ex + m12 * ey + m22 * ez;
+  acc[27] += ex * mex + ey * mey + ez * mez;
+  // J = [S | -I], S = skew(Ta).   A = S*M  (column j of A = Ta x M[:,j]) = H_rot,trans block
+  const double A00 = tay * m02 - taz * m01, A10 = taz * m00 - tax * m02, A20 = tax * m01 - tay * m00;
+  const double A01 = tay * m12 - taz * m11, A11 = taz * m01 - tax * m12, A21 = tax * m11 - tay * m01;
+  const double A02 = tay * m22 - taz * m12, A12 = taz * m02 - tax * m22, A22 = tax * m12 - tay * m02;
+  // H_rr = S^T M S = -(A S);  S columns: (0,az,-ay) (-az,0,ax) (ay,-ax,0)
+  acc[0] += -(A01 * taz - A02 * tay);   // (0,0)
+  acc[1] += -(-A00 * taz + A02 * tax);  // (0,1)
+  acc[2] += -(A00 * tay - A01 * tax);   // (0,2)
+  acc[6] += -(-A10 * taz + A12 * tax);  // (1,1)
+  acc[7] += -(A10 * tay - A11 * tax);   // (1,2)
+  acc[11] += -(A20 * tay - A21 * tax);  // (2,2)
+  // H_rt = -S^T M = S M = A   rows 0..2, cols 3..5
+  acc[3] += A00; acc[4] += A01; acc[5] += A02;
+  acc[8] += A10; acc[9] += A11; acc[10] += A12;
+  acc[12] += A20; acc[13] += A21; acc[14] += A22;
+  // H_tt = M
+  acc[15] += m00; acc[16] += m01; acc[17] += m02;
+  acc[18] += m11; acc[19] += m12;
+  acc[20] += m22;
+  // b = J^T M e = [ S^T Me ; -Me ],  S^T v = v x Ta
+  acc[21] += mey * taz - mez * tay;
+  acc[22] += mez * tax - mex * taz;
+  acc[23] += mex * tay - mey * tax;
+  acc[24] += -mex;
+  acc[25] += -mey;
+  acc[26] += -mez;
+}
+
+// the error leg alone: e^T M e with M read from six doubles in memory, in lin_terms' order of operations
+__device__ __forceinline__ double err_term(const double ex, const double ey, const double ez, const double* M) {
+  const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
+  const double mex = m00 * ex + m01 * ey + m02 * ez;
+  const double mey = m01 * ex + m11 * ey + m12 * ez;
+  const double mez = m02 * ex + m12 * ey + m22 * ez;
+  return ex * mex + ey * mey + ez * mez;
+}
+
 struct LmConfig {
   int max_iterations;
   int lm_max_iterations;
@@ -93,6 +140,27 @@ constexpr int kViewWords = 128;
 constexpr int kGenLines = 256, kGenStride = 32;
 static_assert(sizeof(LmState) % 512 == 0 && offsetof(LmState, view) % 512 == 0, "ring entries are 512-byte aligned");
 
+// What a pass block takes from the state before it touches a point: the trial pose in FP64 and in float, and the flags.
+struct PassPose {
+  double R[9], t[3];
+  float Tf[12];
+  int have_lin, cur;
+};
+typedef const LmState __attribute__((address_space(4))) * KernelStatePtr;  // the state read with scalar loads: it does not change during a launch
+// S: a pointer to the state, generic (k_vgicp_pass, k_vgicp_pass_n) or KernelStatePtr (k_vgicp_pass_batch).  The `done` flag is the
+// caller's to test.
+template <class S>
+__device__ __forceinline__ void load_pose(S st, PassPose& p) {
+  p.have_lin = st->hot.have_lin;
+  p.cur = st->hot.cur;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) p.R[i] = st->hot.xi.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) p.t[i] = st->hot.xi.t[i];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) p.Tf[i] = st->xi_f[i];
+}
+
 struct alignas(4) Xyz { float x, y, z; };
 __device__ __forceinline__ float sqdist(float qx, float qy, float qz, const Xyz& p) {
   const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
@@ -100,6 +168,16 @@ __device__ __forceinline__ float sqdist(float qx, float qy, float qz, const Xyz&
   r = r + dy * dy;
   r = r + dz * dz;
   return r;
+}
+
+// the float pose (xi_f / lin_f: rows of [R|t], row-major 3x4) times a point, in the NN query's order: ((c0*x + c1*y) + c2*z) + c3.
+// (not transform_point_f, ngicp_cloudops.h: that one takes a column-major 4x4 and adds in another order)
+__device__ __forceinline__ float3 transform_point_rowmajor_f(const float* Tf, float x, float y, float z) {
+  float3 q;
+  q.x = ((Tf[0] * x + Tf[1] * y) + Tf[2] * z) + Tf[3];
+  q.y = ((Tf[4] * x + Tf[5] * y) + Tf[6] * z) + Tf[7];
+  q.z = ((Tf[8] * x + Tf[9] * y) + Tf[10] * z) + Tf[11];
+  return q;
 }
 
 // sorted float4 points (with their sentinel frame) -> the same points carrying their sorted position instead of their original index
@@ -1159,8 +1237,7 @@ __device__ __forceinline__ void persist_group_body(A& a, const int group, const 
   typedef const int __attribute__((address_space(4))) * ViewPtr;
   typedef const double __attribute__((address_space(4))) * ViewPtrD;
   typedef const float __attribute__((address_space(4))) * ViewPtrF;
-  typedef const LmState __attribute__((address_space(4))) * StatePtr;
-  StatePtr st4 = (StatePtr)(unsigned long long)a.st;
+  KernelStatePtr st4 = (KernelStatePtr)(unsigned long long)a.st;
   ViewPtr vw = (ViewPtr)(unsigned long long)(a.st->view + (size_t)(a.first_pass + pass_no) * kViewWords);
   const int have_lin = RING ? vw[kViewHaveLin] : st4->hot.have_lin;
   const int cur = (RING ? vw[kViewCur] : st4->hot.cur) & 1, nxt = cur ^ 1;  // (indices into two-element arrays of pointers, whatever the memory holds)
@@ -1514,10 +1591,8 @@ __global__ void __launch_bounds__(256) k_corr_to_original(const float4* __restri
   if (out_sqd) {
     float d = __builtin_inff();
     if (j >= 0) {
-      const float qx = ((lin_f[0] * sp.x + lin_f[1] * sp.y) + lin_f[2] * sp.z) + lin_f[3];
-      const float qy = ((lin_f[4] * sp.x + lin_f[5] * sp.y) + lin_f[6] * sp.z) + lin_f[7];
-      const float qz = ((lin_f[8] * sp.x + lin_f[9] * sp.y) + lin_f[10] * sp.z) + lin_f[11];
-      d = sqdist(qx, qy, qz, tgt_sorted[j]);
+      const float3 q = transform_point_rowmajor_f(lin_f, sp.x, sp.y, sp.z);
+      d = sqdist(q.x, q.y, q.z, tgt_sorted[j]);
     }
     out_sqd[o] = d;
   }

@@ -217,9 +217,8 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass_st(PassArgs a) {
       int cx = 0, cy = 0, cz = 0;
       if (qok) {
         // Eigen 4x4 * 4-vector in float: ((c0*x + c1*y) + c2*z) + c3*1
-        qx = ((Tf[0] * qpx + Tf[1] * qpy) + Tf[2] * qpz) + Tf[3];
-        qy = ((Tf[4] * qpx + Tf[5] * qpy) + Tf[6] * qpz) + Tf[7];
-        qz = ((Tf[8] * qpx + Tf[9] * qpy) + Tf[10] * qpz) + Tf[11];
+        const float3 q = transform_point_rowmajor_f(Tf, qpx, qpy, qpz);
+        qx = q.x, qy = q.y, qz = q.z;
         cell_coords(g, qx, qy, qz, cx, cy, cz);
       }
       float best = 3.4028234664e38f;
@@ -566,37 +565,7 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass_st(PassArgs a) {
 
           // K3: residual, Jacobian, normal equations (impl/nano_gicp_impl.hpp:232-257)
           const double ex = (double)bp.x - tax, ey = (double)bp.y - tay, ez = (double)bp.z - taz;
-          const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
-          const double mex = m00 * ex + m01 * ey + m02 * ez;
-          const double mey = m01 * ex + m11 * ey + m12 * ez;
-          const double mez = m02 * ex + m12 * ey + m22 * ez;
-          acc[27] += ex * mex + ey * mey + ez * mez;
-          // J = [S | -I], S = skew(Ta).   A = S*M  (column j of A = Ta x M[:,j]) = H_rot,trans block
-          const double A00 = tay * m02 - taz * m01, A10 = taz * m00 - tax * m02, A20 = tax * m01 - tay * m00;
-          const double A01 = tay * m12 - taz * m11, A11 = taz * m01 - tax * m12, A21 = tax * m11 - tay * m01;
-          const double A02 = tay * m22 - taz * m12, A12 = taz * m02 - tax * m22, A22 = tax * m12 - tay * m02;
-          // H_rr = S^T M S = -(A S);  S columns: (0,az,-ay) (-az,0,ax) (ay,-ax,0)
-          acc[0] += -(A01 * taz - A02 * tay);   // (0,0)
-          acc[1] += -(-A00 * taz + A02 * tax);  // (0,1)
-          acc[2] += -(A00 * tay - A01 * tax);   // (0,2)
-          acc[6] += -(-A10 * taz + A12 * tax);  // (1,1)
-          acc[7] += -(A10 * tay - A11 * tax);   // (1,2)
-          acc[11] += -(A20 * tay - A21 * tax);  // (2,2)
-          // H_rt = -S^T M = S M = A   rows 0..2, cols 3..5
-          acc[3] += A00; acc[4] += A01; acc[5] += A02;
-          acc[8] += A10; acc[9] += A11; acc[10] += A12;
-          acc[12] += A20; acc[13] += A21; acc[14] += A22;
-          // H_tt = M
-          acc[15] += m00; acc[16] += m01; acc[17] += m02;
-          acc[18] += m11; acc[19] += m12;
-          acc[20] += m22;
-          // b = J^T M e = [ S^T Me ; -Me ],  S^T v = v x Ta
-          acc[21] += mey * taz - mez * tay;
-          acc[22] += mez * tax - mex * taz;
-          acc[23] += mex * tay - mey * tax;
-          acc[24] += -mex;
-          acc[25] += -mey;
-          acc[26] += -mez;
+          lin_terms(acc, tax, tay, taz, ex, ey, ez, M);
         }
       }
     }

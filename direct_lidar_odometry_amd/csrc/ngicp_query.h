@@ -38,18 +38,21 @@ __device__ __forceinline__ double wave_sum(double v) {  // butterfly: every lane
 }
 
 // A pair of lanes per source point, in the source's cell-sorted order (neighbouring pairs walk neighbouring target cells); the
-// exact 1-NN is knn_search with k = 1.  partials[block] = {sum of the counted d2, count}.
+// exact 1-NN is knn_search with k = 1.  Grid (blocks, B): row blockIdx.y serves transform blockIdx.y of T_colmajor[B][16];
+// partials[blockIdx.y * gridDim.x + blockIdx.x] = {sum of the counted d2, count}.  ngicp_fitness_score launches B = 1,
+// ngicp_fitness_score_batch one row per lane: the same kernel, so a lane's sums are the single call's bit for bit.
 __global__ void __launch_bounds__(kKnnBlock) k_fitness(const float4* __restrict__ src_sorted, int n, const float* __restrict__ T_colmajor,
                                                        const float4* __restrict__ tgt_sorted, const int* __restrict__ tgt_cells, Grid g, double max_range,
                                                        double2* __restrict__ partials) {
   __shared__ int lds_bounds[36 * kKnnPairs];
   __shared__ double2 wave_part[kKnnBlock / 64];
+  const float* __restrict__ Tm = T_colmajor + (size_t)blockIdx.y * 16;
   const int lane = threadIdx.x & 63, sub = threadIdx.x & 1, pair = threadIdx.x >> 1;
   const int i = blockIdx.x * kKnnPairs + pair;
   double s = 0.0, c = 0.0;
   if (i < n) {
     const float4 p = src_sorted[i];
-    const float3 t = transform_point_f(T_colmajor, p.x, p.y, p.z);
+    const float3 t = transform_point_f(Tm, p.x, p.y, p.z);
     PairTopK<2> top;
     knn_search<2, 4>(g, tgt_sorted, tgt_cells, t.x, t.y, t.z, -1, 1, top, lds_bounds + pair, sub, lane);
     const float d2 = top.part.template d<0>();  // slot 0 lives in lane 0 of the pair
@@ -69,18 +72,20 @@ __global__ void __launch_bounds__(kKnnBlock) k_fitness(const float4* __restrict_
       r.x += wave_part[w].x;
       r.y += wave_part[w].y;
     }
-    partials[blockIdx.x] = r;
+    partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = r;
   }
 }
 
-// one block: out = the sum of partials[0..nb), in a fixed order (strided per thread, then wave butterflies, then the waves in order)
+// block l: out[l] = the sum of partials[l * nb .. l * nb + nb), in a fixed order (strided per thread, then wave butterflies, then the
+// waves in order)
 constexpr int kFitnessFinalBlock = 256;
 __global__ void __launch_bounds__(kFitnessFinalBlock) k_fitness_final(const double2* __restrict__ partials, int nb, double2* __restrict__ out) {
   __shared__ double2 wave_part[kFitnessFinalBlock / 64];
+  const double2* __restrict__ mine = partials + (size_t)blockIdx.x * nb;
   double s = 0.0, c = 0.0;
   for (int b = threadIdx.x; b < nb; b += kFitnessFinalBlock) {
-    s += partials[b].x;
-    c += partials[b].y;
+    s += mine[b].x;
+    c += mine[b].y;
   }
   s = wave_sum(s);
   c = wave_sum(c);
@@ -93,7 +98,7 @@ __global__ void __launch_bounds__(kFitnessFinalBlock) k_fitness_final(const doub
       r.x += wave_part[w].x;
       r.y += wave_part[w].y;
     }
-    *out = r;
+    out[blockIdx.x] = r;
   }
 }
 

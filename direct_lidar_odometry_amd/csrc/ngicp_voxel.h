@@ -29,6 +29,10 @@
 //                                 k_vgicp_pass itself serves DIRECT1 and is not touched by any of this.
 //   vgicp_pass_body / vgicp_pass_n_body<K>   what the two kernels do once they hold the state's pose and flags, as inlined functions:
 //                                 k_vgicp_pass_batch<K> (ngicp_voxel_batch.h) runs the same bodies on a lane's record.
+//   shared pieces, each defined once   voxel_cell / voxel_pack (-> voxel_key), voxel_probe_from (-> voxel_lookup, and the neighbourhoods'
+//                                 probe continuation), voxel_segment_sums and voxel_table_insert (the map's fill kernels), voxel_pass_begin
+//                                 (the single kernels' head), voxel_block_row (a pass block's row); from ngicp_pass.h: load_pose,
+//                                 transform_point_rowmajor_f, lin_terms / err_term (the exact pass's K3 and its error leg).
 //   merged voxel map              (a setting, off by default) the map of a submap from sums its keyframes carry:
 //                                 k_voxel_part_fill (one keyframe's per-voxel sums, no division), k_voxel_part_gather (the parts' keys in
 //                                 the order of the id list, value = global record position), the same stable sort and numbering, and
@@ -45,11 +49,24 @@ constexpr unsigned long long kVoxEmpty = ~0ull;  // (no key has bit 63)
 constexpr int kVoxBlock = 256;          // source points per block of k_vgicp_pass
 constexpr int kVoxRec = 10;             // doubles per voxel record: mean 3, covariance {xx, xy, xz, yy, yz, zz}, count
 
-__device__ __forceinline__ bool voxel_key(float x, float y, float z, float inv_res, unsigned long long& key) {
+// the cell of a float point; false when it has none (a component at or beyond 2^20 in magnitude, or a NaN coordinate)
+__device__ __forceinline__ bool voxel_cell(float x, float y, float z, float inv_res, int& ix, int& iy, int& iz) {
   const float fx = floorf(x * inv_res), fy = floorf(y * inv_res), fz = floorf(z * inv_res);
   const float lim = 1048576.f;
   if (!(fx > -lim && fx < lim && fy > -lim && fy < lim && fz > -lim && fz < lim)) return false;  // (a NaN coordinate ends here too)
-  key = ((unsigned long long)((int)fz + kVoxBias) << 42) | ((unsigned long long)((int)fy + kVoxBias) << 21) | (unsigned long long)((int)fx + kVoxBias);
+  ix = (int)fx, iy = (int)fy, iz = (int)fz;
+  return true;
+}
+
+// the key of a cell whose components are all below 2^20 in magnitude
+__device__ __forceinline__ unsigned long long voxel_pack(int ix, int iy, int iz) {
+  return ((unsigned long long)(iz + kVoxBias) << 42) | ((unsigned long long)(iy + kVoxBias) << 21) | (unsigned long long)(ix + kVoxBias);
+}
+
+__device__ __forceinline__ bool voxel_key(float x, float y, float z, float inv_res, unsigned long long& key) {
+  int ix, iy, iz;
+  if (!voxel_cell(x, y, z, inv_res, ix, iy, iz)) return false;
+  key = voxel_pack(ix, iy, iz);
   return true;
 }
 
@@ -62,17 +79,56 @@ __device__ __forceinline__ unsigned int voxel_hash(unsigned long long k, unsigne
   return (unsigned int)k & mask;
 }
 
-// voxel number of `key`, or -1.  The table always has empty slots (load <= 1/2): the probe sequence ends.
-__device__ __forceinline__ int voxel_lookup(const ulonglong2* __restrict__ table, unsigned int mask, unsigned long long key, unsigned int& probes) {
-  unsigned int slot = voxel_hash(key, mask);
+// voxel number of `key`, or -1, probing from `slot` on.  The table always has empty slots (load <= 1/2): the probe sequence ends at a
+// hit or at an empty slot, never at the loop's bound, which is there for form (mask + 1 slots from wherever the probe starts - the
+// neighbourhoods' continuation, which starts one slot on, used to stop one slot sooner).  `table` is not __restrict__ here: the
+// continuation never had it, and its caller stores to corr / LDS between probes.
+__device__ __forceinline__ int voxel_probe_from(const ulonglong2* table, unsigned int mask, unsigned int slot, unsigned long long key, unsigned int& probes) {
+  int v = -1;
   for (unsigned int t = 0; t <= mask; ++t) {
     const ulonglong2 e = table[slot];
     ++probes;
-    if (e.x == key) return (int)e.y;
-    if (e.x == kVoxEmpty) return -1;
+    if (e.x == key) { v = (int)e.y; break; }
+    if (e.x == kVoxEmpty) break;
     slot = (slot + 1) & mask;
   }
-  return -1;
+  return v;
+}
+
+__device__ __forceinline__ int voxel_lookup(const ulonglong2* __restrict__ table, unsigned int mask, unsigned long long key, unsigned int& probes) {
+  return voxel_probe_from(table, mask, voxel_hash(key, mask), key, probes);
+}
+
+// m, c = the sums of the points order[s .. e) and of their covariances, each started at 0.0 and added in segment order
+__device__ __forceinline__ void voxel_segment_sums(const int* __restrict__ order, int s, int e, const float4* __restrict__ pts, const double* __restrict__ covs, double (&m)[3],
+                                                   double (&c)[6]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) m[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c[k] = 0.0;
+  for (int j = s; j < e; ++j) {
+    const int p = order[j];
+    const float4 q = pts[p];
+    m[0] += (double)q.x;
+    m[1] += (double)q.y;
+    m[2] += (double)q.z;
+    const double* C = covs + (size_t)p * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] += C[k];
+  }
+}
+
+// {key, v} into the first free slot of key's probe sequence (keys are distinct and the table is at most half full: a free slot comes)
+__device__ __forceinline__ void voxel_table_insert(ulonglong2* __restrict__ table, unsigned int mask, unsigned long long key, int v) {
+  unsigned int slot = voxel_hash(key, mask);
+  for (unsigned int t = 0; t <= mask; ++t) {
+    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(&table[slot]), kVoxEmpty, key);
+    if (prev == kVoxEmpty) {
+      table[slot].y = (unsigned long long)v;
+      break;
+    }
+    slot = (slot + 1) & mask;
+  }
 }
 
 // keys[o] / vals[o] for ORIGINAL target index o (the sort is stable: a voxel's points stay in ascending original index); vals = the
@@ -110,17 +166,8 @@ __global__ void __launch_bounds__(256) k_voxel_map_fill(const unsigned long long
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n_vox) return;
   const int s = seg_start[v], e = seg_start[v + 1];
-  double m[3] = {0.0, 0.0, 0.0}, c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = s; j < e; ++j) {
-    const int p = order[j];
-    const float4 q = pts[p];
-    m[0] += (double)q.x;
-    m[1] += (double)q.y;
-    m[2] += (double)q.z;
-    const double* C = covs + (size_t)p * 6;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] += C[k];
-  }
+  double m[3], c[6];
+  voxel_segment_sums(order, s, e, pts, covs, m, c);
   const double cnt = (double)(e - s);
   double* r = rec + (size_t)v * kVoxRec;
 #pragma unroll
@@ -130,15 +177,7 @@ __global__ void __launch_bounds__(256) k_voxel_map_fill(const unsigned long long
   r[9] = cnt;
   const unsigned long long key = keys[s];
   vkeys[v] = key;
-  unsigned int slot = voxel_hash(key, mask);
-  for (unsigned int t = 0; t <= mask; ++t) {  // (keys are distinct and the table is at most half full: a free slot comes)
-    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(&table[slot]), kVoxEmpty, key);
-    if (prev == kVoxEmpty) {
-      table[slot].y = (unsigned long long)v;
-      break;
-    }
-    slot = (slot + 1) & mask;
-  }
+  voxel_table_insert(table, mask, key, v);
 }
 
 // ---- a submap's map merged from per-keyframe voxel sums (include/ngicp.h "merged voxel map") -------------------------
@@ -151,17 +190,8 @@ __global__ void __launch_bounds__(256) k_voxel_part_fill(const unsigned long lon
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n_vox) return;
   const int s = seg_start[v], e = seg_start[v + 1];
-  double m[3] = {0.0, 0.0, 0.0}, c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = s; j < e; ++j) {
-    const int p = order[j];
-    const float4 q = pts[p];
-    m[0] += (double)q.x;
-    m[1] += (double)q.y;
-    m[2] += (double)q.z;
-    const double* C = covs + (size_t)p * 6;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] += C[k];
-  }
+  double m[3], c[6];
+  voxel_segment_sums(order, s, e, pts, covs, m, c);
   double* r = rec + (size_t)v * kVoxRec;
 #pragma unroll
   for (int k = 0; k < 3; ++k) r[k] = m[k];
@@ -216,15 +246,7 @@ __global__ void __launch_bounds__(256) k_voxel_merge_fill(const unsigned long lo
   out[9] = cnt;
   const unsigned long long key = keys[s];
   vkeys[v] = key;
-  unsigned int slot = voxel_hash(key, mask);
-  for (unsigned int t = 0; t <= mask; ++t) {  // (keys are distinct and the table is at most half full: a free slot comes)
-    const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(&table[slot]), kVoxEmpty, key);
-    if (prev == kVoxEmpty) {
-      table[slot].y = (unsigned long long)v;
-      break;
-    }
-    slot = (slot + 1) & mask;
-  }
+  voxel_table_insert(table, mask, key, v);
 }
 
 struct VoxelPassArgs {
@@ -253,107 +275,15 @@ struct VoxelPassLds {
   unsigned int cnt[4][2][64];
 };
 
-// One block of one DIRECT1 pass, from the pose on: everything k_vgicp_pass does once it holds the state's trial pose and flags.  The
-// single kernel and k_vgicp_pass_batch<1> (ngicp_voxel_batch.h) both inline it: the same per-point statements, the same reduction, the
-// same row - a lane of the batch comes out bit for bit as the single alignment.  A: VoxelPassArgs (the kernel's argument) or the same
-// record seen through the constant address space (KernelVoxelPassArgs: a lane's record in device memory, read with scalar loads).
-template <class A>
-__device__ __forceinline__ void vgicp_pass_body(A& a, const double (&R)[9], const double (&t)[3], const float (&Tf)[12], const int have_lin_now, const int cur,
-                                                VoxelPassLds& sh) {
-  double (&red)[4][16 * 30] = sh.red;
+// A voxelized pass block's row of kNumSlots sums from its threads' sums and counters, in a fixed order: sixteen lanes at a time write a
+// [16][30] tile, lane v adds column v top to bottom (the exact pass's R0); lanes 29 and 30 add the two counter columns; then the four
+// waves in order.
+__device__ __forceinline__ void voxel_block_row(const double (&acc)[kNumSums], const unsigned int nprobes, const unsigned int nvalid, VoxelPassLds& sh, double* partials) {
   double (&lds)[4][kNumSlots] = sh.lds;
   unsigned int (&cnt)[4][2][64] = sh.cnt;
-  const int nxt = cur ^ 1;
-  const bool do_err = (a.mode & 1) && have_lin_now;
-  const bool do_lin = (a.mode & 2);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = blockIdx.x * kVoxBlock + threadIdx.x;
-  const bool mine = i < a.n_src;
-
-  double acc[kNumSums];
-#pragma unroll
-  for (int v = 0; v < kNumSums; ++v) acc[v] = 0.0;
-  unsigned int nprobes = 0, nvalid = 0;
-  if (mine) {
-    const float4 sp = a.src[i];
-    const double ax = (double)sp.x, ay = (double)sp.y, az = (double)sp.z;
-    const double tax = R[0] * ax + R[1] * ay + R[2] * az + t[0];  // T * a in FP64, as the exact pass
-    const double tay = R[3] * ax + R[4] * ay + R[5] * az + t[1];
-    const double taz = R[6] * ax + R[7] * ay + R[8] * az + t[2];
-    if (do_err) {  // error of the trial pose under the previous pass's correspondences
-      const int v_old = a.corr[cur][i];
-      if ((unsigned int)v_old < (unsigned int)a.n_vox) {  // (-1: none)
-        const double* mv = a.rec + (size_t)v_old * kVoxRec;
-        const double* M = a.mahal[cur] + (size_t)i * 6;
-        const double ex = mv[0] - tax, ey = mv[1] - tay, ez = mv[2] - taz;
-        const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
-        const double mex = m00 * ex + m01 * ey + m02 * ez;
-        const double mey = m01 * ex + m11 * ey + m12 * ez;
-        const double mez = m02 * ex + m12 * ey + m22 * ez;
-        acc[28] += ex * mex + ey * mey + ez * mez;
-      }
-    }
-    if (do_lin) {
-      // the float pose times the point, in the exact pass's order: ((c0*x + c1*y) + c2*z) + c3
-      const float qx = ((Tf[0] * sp.x + Tf[1] * sp.y) + Tf[2] * sp.z) + Tf[3];
-      const float qy = ((Tf[4] * sp.x + Tf[5] * sp.y) + Tf[6] * sp.z) + Tf[7];
-      const float qz = ((Tf[8] * sp.x + Tf[9] * sp.y) + Tf[10] * sp.z) + Tf[11];
-      unsigned long long key = 0;
-      int v = -1;
-      if (voxel_key(qx, qy, qz, a.inv_res, key)) v = voxel_lookup(a.table, a.mask, key, nprobes);
-      a.corr[nxt][i] = v;
-      if (v >= 0) {
-        ++nvalid;
-        const double* rv = a.rec + (size_t)v * kVoxRec;
-        const double* CA = a.cov_src + (size_t)i * 6;
-        double ca[6], rcr[6], M[6];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) ca[e] = CA[e];
-        const double bx = rv[0], by = rv[1], bz = rv[2], nv = rv[9];
-        rotate_sym(R, ca, rcr);
-#pragma unroll
-        for (int e = 0; e < 6; ++e) rcr[e] = rv[3 + e] + rcr[e];
-        inv3_sym(rcr, M);
-#pragma unroll
-        for (int e = 0; e < 6; ++e) M[e] = nv * M[e];
-        double* Mo = a.mahal[nxt] + (size_t)i * 6;
-#pragma unroll
-        for (int e = 0; e < 6; ++e) Mo[e] = M[e];
-        // residual, Jacobian, normal equations: the exact pass's tail with mean_v for the target point and n_v M for M
-        const double ex = bx - tax, ey = by - tay, ez = bz - taz;
-        const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
-        const double mex = m00 * ex + m01 * ey + m02 * ez;
-        const double mey = m01 * ex + m11 * ey + m12 * ez;
-        const double mez = m02 * ex + m12 * ey + m22 * ez;
-        acc[27] += ex * mex + ey * mey + ez * mez;
-        const double A00 = tay * m02 - taz * m01, A10 = taz * m00 - tax * m02, A20 = tax * m01 - tay * m00;
-        const double A01 = tay * m12 - taz * m11, A11 = taz * m01 - tax * m12, A21 = tax * m11 - tay * m01;
-        const double A02 = tay * m22 - taz * m12, A12 = taz * m02 - tax * m22, A22 = tax * m12 - tay * m02;
-        acc[0] += -(A01 * taz - A02 * tay);
-        acc[1] += -(-A00 * taz + A02 * tax);
-        acc[2] += -(A00 * tay - A01 * tax);
-        acc[6] += -(-A10 * taz + A12 * tax);
-        acc[7] += -(A10 * tay - A11 * tax);
-        acc[11] += -(A20 * tay - A21 * tax);
-        acc[3] += A00; acc[4] += A01; acc[5] += A02;
-        acc[8] += A10; acc[9] += A11; acc[10] += A12;
-        acc[12] += A20; acc[13] += A21; acc[14] += A22;
-        acc[15] += m00; acc[16] += m01; acc[17] += m02;
-        acc[18] += m11; acc[19] += m12;
-        acc[20] += m22;
-        acc[21] += mey * taz - mez * tay;
-        acc[22] += mez * tax - mex * taz;
-        acc[23] += mex * tay - mey * tax;
-        acc[24] += -mex;
-        acc[25] += -mey;
-        acc[26] += -mez;
-      }
-    }
-  }
-  // ---- the block's row, in a fixed order: sixteen lanes at a time write a [16][30] tile, lane v adds column v top to bottom (the exact
-  //      pass's R0); then the four waves in order ----
   {
-    double* rw = red[wave];
+    double* rw = sh.red[wave];
     double out = 0.0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -379,28 +309,92 @@ __device__ __forceinline__ void vgicp_pass_body(A& a, const double (&R)[9], cons
   __syncthreads();
   if (threadIdx.x < kNumSlots) {
     const int v = threadIdx.x;
-    a.partials[(size_t)blockIdx.x * kNumSlots + v] = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
+    partials[(size_t)blockIdx.x * kNumSlots + v] = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
   }
+}
+
+// One block of one DIRECT1 pass, from the pose on: everything k_vgicp_pass does once it holds the state's trial pose and flags.  The
+// single kernel and k_vgicp_pass_batch<1> (ngicp_voxel_batch.h) both inline it: the same per-point statements, the same reduction, the
+// same row - a lane of the batch comes out bit for bit as the single alignment.  A: VoxelPassArgs (the kernel's argument) or the same
+// record seen through the constant address space (KernelVoxelPassArgs: a lane's record in device memory, read with scalar loads).
+template <class A>
+__device__ __forceinline__ void vgicp_pass_body(A& a, const PassPose& p, VoxelPassLds& sh) {
+  const double (&R)[9] = p.R;
+  const double (&t)[3] = p.t;
+  const float (&Tf)[12] = p.Tf;
+  const int cur = p.cur;
+  const int nxt = cur ^ 1;
+  const bool do_err = (a.mode & 1) && p.have_lin;
+  const bool do_lin = (a.mode & 2);
+  const int i = blockIdx.x * kVoxBlock + threadIdx.x;
+  const bool mine = i < a.n_src;
+
+  double acc[kNumSums];
+#pragma unroll
+  for (int v = 0; v < kNumSums; ++v) acc[v] = 0.0;
+  unsigned int nprobes = 0, nvalid = 0;
+  if (mine) {
+    const float4 sp = a.src[i];
+    const double ax = (double)sp.x, ay = (double)sp.y, az = (double)sp.z;
+    const double tax = R[0] * ax + R[1] * ay + R[2] * az + t[0];  // T * a in FP64, as the exact pass
+    const double tay = R[3] * ax + R[4] * ay + R[5] * az + t[1];
+    const double taz = R[6] * ax + R[7] * ay + R[8] * az + t[2];
+    if (do_err) {  // error of the trial pose under the previous pass's correspondences
+      const int v_old = a.corr[cur][i];
+      if ((unsigned int)v_old < (unsigned int)a.n_vox) {  // (-1: none)
+        const double* mv = a.rec + (size_t)v_old * kVoxRec;
+        acc[28] += err_term(mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + (size_t)i * 6);
+      }
+    }
+    if (do_lin) {
+      const float3 q = transform_point_rowmajor_f(Tf, sp.x, sp.y, sp.z);  // the float pose times the point, as the exact pass
+      unsigned long long key = 0;
+      int v = -1;
+      if (voxel_key(q.x, q.y, q.z, a.inv_res, key)) v = voxel_lookup(a.table, a.mask, key, nprobes);
+      a.corr[nxt][i] = v;
+      if (v >= 0) {
+        ++nvalid;
+        const double* rv = a.rec + (size_t)v * kVoxRec;
+        const double* CA = a.cov_src + (size_t)i * 6;
+        double ca[6], rcr[6], M[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) ca[e] = CA[e];
+        const double bx = rv[0], by = rv[1], bz = rv[2], nv = rv[9];
+        rotate_sym(R, ca, rcr);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) rcr[e] = rv[3 + e] + rcr[e];
+        inv3_sym(rcr, M);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) M[e] = nv * M[e];
+        double* Mo = a.mahal[nxt] + (size_t)i * 6;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) Mo[e] = M[e];
+        // residual, Jacobian, normal equations: the exact pass's K3 with mean_v for the target point and n_v M for M
+        lin_terms(acc, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
+      }
+    }
+  }
+  voxel_block_row(acc, nprobes, nvalid, sh, a.partials);
 }
 
 typedef const VoxelPassArgs __attribute__((address_space(4))) KernelVoxelPassArgs;
 
+// The head of the two single kernels: the state's pose and flags; false when the block has nothing to do (the alignment is done and
+// mode bit 2 is not set); the first pass of an alignment stamps t_first.
+__device__ __forceinline__ bool voxel_pass_begin(const VoxelPassArgs& a, PassPose& p) {
+  const LmState* __restrict__ st = a.st;
+  const int done_now = st->hot.done;
+  load_pose(st, p);
+  if (!(a.mode & 4) && done_now) return false;
+  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !p.have_lin) *a.t_first = __builtin_amdgcn_s_memrealtime();
+  return true;
+}
+
 __global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
   __shared__ VoxelPassLds sh;
-  const LmState* __restrict__ st = a.st;
-  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
-  const int cur = st->hot.cur;
-  double R[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
-  float Tf[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
-  if (!(a.mode & 4) && done_now) return;
-  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
-  vgicp_pass_body(a, R, t, Tf, have_lin_now, cur, sh);
+  PassPose p;
+  if (!voxel_pass_begin(a, p)) return;
+  vgicp_pass_body(a, p, sh);
 }
 
 // voxel numbers (and float squared distances to (float)mean_v at the pose of the linearisation) back in ORIGINAL source order
@@ -415,11 +409,9 @@ __global__ void __launch_bounds__(256) k_voxel_corr_to_original(const int* __res
   if (out_sqd) {
     float d = __builtin_inff();
     if (v >= 0) {
-      const float qx = ((lin_f[0] * sp.x + lin_f[1] * sp.y) + lin_f[2] * sp.z) + lin_f[3];
-      const float qy = ((lin_f[4] * sp.x + lin_f[5] * sp.y) + lin_f[6] * sp.z) + lin_f[7];
-      const float qz = ((lin_f[8] * sp.x + lin_f[9] * sp.y) + lin_f[10] * sp.z) + lin_f[11];
+      const float3 q = transform_point_rowmajor_f(lin_f, sp.x, sp.y, sp.z);
       const double* mv = rec + (size_t)v * kVoxRec;
-      d = sqdist(qx, qy, qz, Xyz{(float)mv[0], (float)mv[1], (float)mv[2]});
+      d = sqdist(q.x, q.y, q.z, Xyz{(float)mv[0], (float)mv[1], (float)mv[2]});
     }
     out_sqd[o] = d;
   }
@@ -445,16 +437,15 @@ struct VoxelPassLdsN : VoxelPassLds {
 // vgicp_pass_body for the neighbourhoods: one block of one DIRECT7 / DIRECT27 pass from the pose on, inlined into k_vgicp_pass_n<K> and
 // k_vgicp_pass_batch<K>.
 template <int K, class A>
-__device__ __forceinline__ void vgicp_pass_n_body(A& a, const double (&R)[9], const double (&t)[3], const float (&Tf)[12], const int have_lin_now, const int cur,
-                                                  VoxelPassLdsN<K>& sh) {
-  double (&red)[4][16 * 30] = sh.red;
-  double (&lds)[4][kNumSlots] = sh.lds;
-  unsigned int (&cnt)[4][2][64] = sh.cnt;
+__device__ __forceinline__ void vgicp_pass_n_body(A& a, const PassPose& p, VoxelPassLdsN<K>& sh) {
+  const double (&R)[9] = p.R;
+  const double (&t)[3] = p.t;
+  const float (&Tf)[12] = p.Tf;
+  const int cur = p.cur;
   int (&vs)[K][kVoxBlock] = sh.vs;
   const int nxt = cur ^ 1;
-  const bool do_err = (a.mode & 1) && have_lin_now;
+  const bool do_err = (a.mode & 1) && p.have_lin;
   const bool do_lin = (a.mode & 2);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * kVoxBlock + threadIdx.x;
   const bool mine = i < a.n_src;
   const size_t stride = (size_t)a.slot_stride;
@@ -478,29 +469,18 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const double (&R)[9], co
       for (int s = 0; s < K; ++s) {
         if ((unsigned int)vo[s] < (unsigned int)a.n_vox) {  // (-1: none)
           const double* mv = a.rec + (size_t)vo[s] * kVoxRec;
-          const double* M = a.mahal[cur] + ((size_t)s * stride + i) * 6;
-          const double ex = mv[0] - tax, ey = mv[1] - tay, ez = mv[2] - taz;
-          const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
-          const double mex = m00 * ex + m01 * ey + m02 * ez;
-          const double mey = m01 * ex + m11 * ey + m12 * ez;
-          const double mez = m02 * ex + m12 * ey + m22 * ez;
-          acc[28] += ex * mex + ey * mey + ez * mez;
+          acc[28] += err_term(mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + ((size_t)s * stride + i) * 6);
         }
       }
     }
     if (do_lin) {
-      const float qx = ((Tf[0] * sp.x + Tf[1] * sp.y) + Tf[2] * sp.z) + Tf[3];
-      const float qy = ((Tf[4] * sp.x + Tf[5] * sp.y) + Tf[6] * sp.z) + Tf[7];
-      const float qz = ((Tf[8] * sp.x + Tf[9] * sp.y) + Tf[10] * sp.z) + Tf[11];
-      const float fx = floorf(qx * a.inv_res), fy = floorf(qy * a.inv_res), fz = floorf(qz * a.inv_res);
-      const float lim = 1048576.f;
-      const bool centre_ok = fx > -lim && fx < lim && fy > -lim && fy < lim && fz > -lim && fz < lim;  // (false for a NaN coordinate too)
+      const float3 q = transform_point_rowmajor_f(Tf, sp.x, sp.y, sp.z);
+      int cx, cy, cz;
       int* __restrict__ cn = a.corr[nxt] + i;
-      if (!centre_ok) {
+      if (!voxel_cell(q.x, q.y, q.z, a.inv_res, cx, cy, cz)) {  // (the centre has no cell: no slot has a voxel)
 #pragma unroll
         for (int s = 0; s < K; ++s) cn[(size_t)s * stride] = -1;
       } else {
-        const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
         // ---- the K lookups: every key first, and the first probe of each in flight before any is looked at ----
         unsigned long long key[K];
         ulonglong2 first[K];
@@ -509,7 +489,7 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const double (&R)[9], co
         for (int s = 0; s < K; ++s) {
           const int nx = cx + vox_nbr_off<K>(s, 0), ny = cy + vox_nbr_off<K>(s, 1), nz = cz + vox_nbr_off<K>(s, 2);
           const bool ok = nx > -kVoxBias && nx < kVoxBias && ny > -kVoxBias && ny < kVoxBias && nz > -kVoxBias && nz < kVoxBias;
-          key[s] = ((unsigned long long)(nz + kVoxBias) << 42) | ((unsigned long long)(ny + kVoxBias) << 21) | (unsigned long long)(nx + kVoxBias);
+          key[s] = voxel_pack(nx, ny, nz);
           in_range |= ok ? (1u << s) : 0u;
           first[s] = a.table[ok ? voxel_hash(key[s], a.mask) : 0u];  // (a neighbour beyond the range: the load is neither used nor counted)
         }
@@ -521,14 +501,7 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const double (&R)[9], co
             if (first[s].x == key[s]) {
               v = (int)first[s].y;
             } else if (first[s].x != kVoxEmpty) {  // the probe sequence goes on (the table always has empty slots: it ends)
-              unsigned int sl = voxel_hash(key[s], a.mask);  // (rare: hashed again, not kept in a register for every slot)
-              for (unsigned int tt = 1; tt <= a.mask; ++tt) {
-                sl = (sl + 1) & a.mask;
-                const ulonglong2 e = a.table[sl];
-                ++nprobes;
-                if (e.x == key[s]) { v = (int)e.y; break; }
-                if (e.x == kVoxEmpty) break;
-              }
+              v = voxel_probe_from(a.table, a.mask, (voxel_hash(key[s], a.mask) + 1) & a.mask, key[s], nprobes);  // (rare: hashed again, not kept in a register for every slot)
             }
           }
           cn[(size_t)s * stride] = v;
@@ -556,87 +529,20 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const double (&R)[9], co
           double* Mo = a.mahal[nxt] + ((size_t)s * stride + i) * 6;
 #pragma unroll
           for (int e = 0; e < 6; ++e) Mo[e] = M[e];
-          // residual, Jacobian, normal equations: k_vgicp_pass's tail
-          const double ex = bx - tax, ey = by - tay, ez = bz - taz;
-          const double m00 = M[0], m01 = M[1], m02 = M[2], m11 = M[3], m12 = M[4], m22 = M[5];
-          const double mex = m00 * ex + m01 * ey + m02 * ez;
-          const double mey = m01 * ex + m11 * ey + m12 * ez;
-          const double mez = m02 * ex + m12 * ey + m22 * ez;
-          acc[27] += ex * mex + ey * mey + ez * mez;
-          const double A00 = tay * m02 - taz * m01, A10 = taz * m00 - tax * m02, A20 = tax * m01 - tay * m00;
-          const double A01 = tay * m12 - taz * m11, A11 = taz * m01 - tax * m12, A21 = tax * m11 - tay * m01;
-          const double A02 = tay * m22 - taz * m12, A12 = taz * m02 - tax * m22, A22 = tax * m12 - tay * m02;
-          acc[0] += -(A01 * taz - A02 * tay);
-          acc[1] += -(-A00 * taz + A02 * tax);
-          acc[2] += -(A00 * tay - A01 * tax);
-          acc[6] += -(-A10 * taz + A12 * tax);
-          acc[7] += -(A10 * tay - A11 * tax);
-          acc[11] += -(A20 * tay - A21 * tax);
-          acc[3] += A00; acc[4] += A01; acc[5] += A02;
-          acc[8] += A10; acc[9] += A11; acc[10] += A12;
-          acc[12] += A20; acc[13] += A21; acc[14] += A22;
-          acc[15] += m00; acc[16] += m01; acc[17] += m02;
-          acc[18] += m11; acc[19] += m12;
-          acc[20] += m22;
-          acc[21] += mey * taz - mez * tay;
-          acc[22] += mez * tax - mex * taz;
-          acc[23] += mex * tay - mey * tax;
-          acc[24] += -mex;
-          acc[25] += -mey;
-          acc[26] += -mez;
+          lin_terms(acc, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
         }
       }
     }
   }
-  // ---- the block's row, in k_vgicp_pass's fixed order: sixteen lanes at a time through a [16][30] tile, then the four waves ----
-  {
-    double* rw = red[wave];
-    double out = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      wave_lds_sync();
-      if ((lane >> 4) == q) {
-#pragma unroll
-        for (int v = 0; v < kNumSums; ++v) rw[(lane & 15) * 30 + v] = acc[v];
-      }
-      wave_lds_sync();
-      if (lane < kNumSums)
-        for (int l = 0; l < 16; ++l) out += rw[l * 30 + lane];
-    }
-    cnt[wave][0][lane] = nprobes;
-    cnt[wave][1][lane] = nvalid;
-    wave_lds_sync();
-    if (lane >= kNumSums && lane < kNumSums + 2) {
-      unsigned int sum = 0;
-      for (int l = 0; l < 64; ++l) sum += cnt[wave][lane - kNumSums][l];
-      out = (double)sum;
-    }
-    if (lane < kNumSlots) lds[wave][lane] = lane < kNumSums + 2 ? out : 0.0;
-  }
-  __syncthreads();
-  if (threadIdx.x < kNumSlots) {
-    const int v = threadIdx.x;
-    a.partials[(size_t)blockIdx.x * kNumSlots + v] = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
-  }
+  voxel_block_row(acc, nprobes, nvalid, sh, a.partials);
 }
 
 template <int K>
 __global__ void __launch_bounds__(kVoxBlock, 2) k_vgicp_pass_n(VoxelPassArgs a) {
   __shared__ VoxelPassLdsN<K> sh;
-  const LmState* __restrict__ st = a.st;
-  const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
-  const int cur = st->hot.cur;
-  double R[9], t[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = st->hot.xi.R[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = st->hot.xi.t[i];
-  float Tf[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
-  if (!(a.mode & 4) && done_now) return;
-  if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
-  vgicp_pass_n_body<K>(a, R, t, Tf, have_lin_now, cur, sh);
+  PassPose p;
+  if (!voxel_pass_begin(a, p)) return;
+  vgicp_pass_n_body<K>(a, p, sh);
 }
 
 // the K voxel numbers of every source point, slot-major in sorted order -> row-major [n][K] in ORIGINAL source order

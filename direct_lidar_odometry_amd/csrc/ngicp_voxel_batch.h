@@ -5,7 +5,7 @@
 // shared.
 //   k_vgicp_pass_batch<K>   grid (ceil(n_src / kVoxBlock), live lanes), K = 1, 7, 27.  A block takes its lane from the launch's arguments
 //                           (BatchLaunch::lane[blockIdx.y]), returns at its head when that lane's state says `done`, reads the lane's
-//                           VoxelPassArgs record and the state's pose and flags, and runs the body the single kernel runs
+//                           VoxelPassArgs record and the state's pose and flags (load_pose, as the single kernels), and runs the body the single kernel runs
 //                           (vgicp_pass_body / vgicp_pass_n_body<K>, ngicp_voxel.h): the same per-point statements in the same slot
 //                           order, the same [16][30] tile reduction, the same four-wave sum, the same [block][kNumSlots] row - in the
 //                           lane's own buffers.  The rows k_lm_solve_batch then reads are bit for bit the single path's.
@@ -32,30 +32,17 @@ template <int K>
 __global__ void __launch_bounds__(kVoxBlock, K == 1 ? 1 : 2) k_vgicp_pass_batch(BatchLaunch bl) {
   static_assert(K == 1 || K == 7 || K == 27, "DIRECT1, DIRECT7 or DIRECT27");
   __shared__ typename VoxelBatchKernelTraits<K>::Lds sh;
-  typedef const double __attribute__((address_space(4))) * ConstDoublePtr;
-  typedef const float __attribute__((address_space(4))) * ConstFloatPtr;
-  typedef const LmState __attribute__((address_space(4))) * StatePtr;
   KernelBatchLaunch* kb = (KernelBatchLaunch*)__builtin_amdgcn_kernarg_segment_ptr();
   const int lane_id = kb->lane[blockIdx.y];
   KernelVoxelPassArgs* ka = (KernelVoxelPassArgs*)(unsigned long long)(reinterpret_cast<const VoxelPassArgs*>(kb->pass) + lane_id);
-  StatePtr st4 = (StatePtr)(unsigned long long)ka->st;
+  KernelStatePtr st4 = (KernelStatePtr)(unsigned long long)ka->st;
   if (st4->hot.done) return;
-  const int have_lin_now = st4->hot.have_lin;
-  const int cur = st4->hot.cur;
-  ConstDoublePtr vx = (ConstDoublePtr)&st4->hot.xi;  // (Pose: R[9] then t[3])
-  ConstFloatPtr vf = (ConstFloatPtr)st4->xi_f;
-  double R[9], t[3];
-  float Tf[12];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = vx[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[i] = vx[9 + i];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tf[i] = vf[i];
+  PassPose p;
+  load_pose(st4, p);
   if constexpr (K == 1)
-    vgicp_pass_body(*ka, R, t, Tf, have_lin_now, cur, sh);
+    vgicp_pass_body(*ka, p, sh);
   else
-    vgicp_pass_n_body<K>(*ka, R, t, Tf, have_lin_now, cur, sh);
+    vgicp_pass_n_body<K>(*ka, p, sh);
 }
 
 }  // namespace ngk
