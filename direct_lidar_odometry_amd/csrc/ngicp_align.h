@@ -70,14 +70,15 @@ struct LoopCtx {
 // own_buffers false (ngicp_align_batch): slots and covariances are readied and the fields every lane shares are filled in, but none of
 // the handle's single-alignment buffers is sized or referred to (the caller supplies every per-alignment pointer) and no stats field is
 // written: what the getters of the last ngicp_align read stays where it is.
-void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true) {
+// with_target false (the voxelized entries on a rolling map): the target slot is not read at all - it may be empty - and
+// the exact pass's target fields stay null; the voxelized loops overwrite or ignore everything else that depends on it.
+void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_target = true) {
   ensure_slot_ready(h, h->src, "source");
-  ensure_slot_ready(h, h->tgt, "target");
+  if (with_target) ensure_slot_ready(h, h->tgt, "target");
   // lazy covariances (impl/nano_gicp_impl.hpp:163-168)
   if (h->src_covs.n != h->src.dev->n) compute_covs(h, h->src, h->src_covs, "source");
-  if (h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
+  if (with_target && h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
   DeviceCloud& S = *h->src.dev;
-  DeviceCloud& T = *h->tgt.dev;
   const size_t n = S.n;
   const int nblocks = std::max(1, (S.n_batches + 3) / 4);  // one block per group of four batches
   const int max_rows = max_trace_rows(h->p);
@@ -113,13 +114,24 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true) {
   a.n_batches = S.n_batches;
   a.cov_src = covs_for(h, h->src_covs, h->src.dev);
   a.n_src = (int)n;
-  a.tgt = T.pts();
-  a.tgt3 = T.xyz3();
-  a.tgtp = T.xyzp();
-  a.tgt_cell_start = T.cells();
-  a.tgt_cell_box = (h->cell_boxes && T.has_boxes) ? T.cell_box.as<unsigned int>() + kCellPad : nullptr;
-  a.cov_tgt = covs_for(h, h->tgt_covs, h->tgt.dev);
-  a.grid = T.grid;
+  if (with_target) {
+    DeviceCloud& T = *h->tgt.dev;
+    a.tgt = T.pts();
+    a.tgt3 = T.xyz3();
+    a.tgtp = T.xyzp();
+    a.tgt_cell_start = T.cells();
+    a.tgt_cell_box = (h->cell_boxes && T.has_boxes) ? T.cell_box.as<unsigned int>() + kCellPad : nullptr;
+    a.cov_tgt = covs_for(h, h->tgt_covs, h->tgt.dev);
+    a.grid = T.grid;
+  } else {
+    a.tgt = nullptr;
+    a.tgt3 = nullptr;
+    a.tgtp = nullptr;
+    a.tgt_cell_start = nullptr;
+    a.tgt_cell_box = nullptr;
+    a.cov_tgt = nullptr;
+    a.grid = Grid{};
+  }
   for (int i = 0; i < 2; ++i) {
     a.tpt[i] = own_buffers ? h->tpt[i].as<float4>() : nullptr;
     a.mahal[i] = own_buffers ? h->mahal[i].as<double>() : nullptr;
@@ -148,7 +160,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true) {
   {
     // rings worth staging: enough to cover the distance gate (the search never looks farther), at most kStageMaxGrow
     int need = kStageMaxGrow;
-    if (h->p.max_corr_dist < 1e30) need = (int)std::ceil(h->p.max_corr_dist / (double)T.grid.h);
+    if (with_target && h->p.max_corr_dist < 1e30) need = (int)std::ceil(h->p.max_corr_dist / (double)a.grid.h);
     a.stage_grow = h->stage_grow <= 0 ? 0 : std::max(1, std::min(std::min(kStageMaxGrow, h->stage_grow), need));  // 0: search straight from global memory
   }
 
@@ -184,10 +196,10 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true) {
   c.nblocks = nblocks;
   if (!own_buffers) return;
   h->stats.lanes_per_query = 2;
-  h->stats.voxel_size = T.grid.h;
-  h->stats.grid_dims[0] = T.grid.nx;
-  h->stats.grid_dims[1] = T.grid.ny;
-  h->stats.grid_dims[2] = T.grid.nz;
+  h->stats.voxel_size = a.grid.h;
+  h->stats.grid_dims[0] = a.grid.nx;
+  h->stats.grid_dims[1] = a.grid.ny;
+  h->stats.grid_dims[2] = a.grid.nz;
 }
 
 void init_state_from_pose(LmState& st, const Pose& x0) {
@@ -357,7 +369,7 @@ void end_alignment(ngicp* h, Alignment& al, float* aligned, size_t out_stride, b
   if (event_times) sum_event_pass_times(h, al.st.hot.passes);
   ngicp_stats& s = h->stats;
   s.n_src = (long long)h->src.dev->n;
-  s.n_tgt = (long long)h->tgt.dev->n;
+  s.n_tgt = rolling_active(h) ? (long long)h->roll.n_vox : (long long)h->tgt.dev->n;  // (a rolling map has no target cloud: its voxels)
   s.host_wait_spins = (long long)al.spins;
   s.align_ms = now_ms() - al.t_begin;
 }
@@ -679,15 +691,15 @@ void launch_voxel_pass(ngicp* h, const VoxelCtx& c, hipEvent_t start = nullptr, 
 }
 
 // the fields of a voxelized pass that do not depend on the alignment (or the lane): the source, the map, the neighbourhood
-void fill_voxel_shared(ngicp* h, VoxelPassArgs& a) {
+void fill_voxel_shared(ngicp* h, VoxelPassArgs& a, const VoxelMapView& m) {
   DeviceCloud& S = *h->src.dev;
   a.src = S.pts();
   a.cov_src = covs_for(h, h->src_covs, h->src.dev);
   a.n_src = (int)S.n;
-  a.table = h->vmap.table.as<ulonglong2>();
-  a.mask = h->vmap.mask;
-  a.rec = h->vmap.rec.as<double>();
-  a.n_vox = (int)h->vmap.n_vox;
+  a.table = m.table;
+  a.mask = m.mask;
+  a.rec = m.rec;
+  a.n_vox = (int)m.n_vox;
   a.inv_res = 1.0f / (float)h->voxel_res;
   a.nbr = h->voxel_nbr;
   a.slot_stride = (int)S.n;
@@ -700,8 +712,8 @@ void fill_voxel_shared(ngicp* h, VoxelPassArgs& a) {
 // the exact pass's groups (grp_order, its flag) is neither read nor written.
 void prepare_voxel_loop(ngicp* h, VoxelCtx& v) {
   LoopCtx c;
-  prepare_loop(h, c);
-  ensure_voxel_map(h);
+  prepare_loop(h, c, true, !rolling_active(h));
+  const VoxelMapView vm = ensure_voxel_map(h);
   DeviceCloud& S = *h->src.dev;
   const size_t n = S.n;
   const int nblocks = std::max(1, (int)((n + kVoxBlock - 1) / kVoxBlock));
@@ -713,7 +725,7 @@ void prepare_voxel_loop(ngicp* h, VoxelCtx& v) {
     if (K > 1) h->vox_mahal[i].ensure(K * n * 6 * sizeof(double));
   }
   VoxelPassArgs& a = v.pa;
-  fill_voxel_shared(h, a);
+  fill_voxel_shared(h, a, vm);
   for (int i = 0; i < 2; ++i) {
     a.corr[i] = h->vox_corr[i].as<int>();
     a.mahal[i] = K > 1 ? h->vox_mahal[i].as<double>() : h->mahal[i].as<double>();
@@ -1005,8 +1017,8 @@ void do_align_voxel_batch(ngicp* h, int B, const float* guesses, float* T_out, i
   static_assert(sizeof(VoxelPassArgs) <= sizeof(PassArgs), "the pinned record block is sized for PassArgs records");
   BatchWs& w = h->batch;
   LoopCtx c;
-  prepare_loop(h, c, false);  // (slots, lazy covariances, the solver's configuration)
-  ensure_voxel_map(h);        // (at most one build, whatever the number of lanes)
+  prepare_loop(h, c, false, !rolling_active(h));   // (slots, lazy covariances, the solver's configuration)
+  const VoxelMapView vm = ensure_voxel_map(h);  // (at most one build, whatever the number of lanes)
   const size_t n = h->src.dev->n, K = (size_t)h->voxel_nbr;
   const int nblocks = std::max(1, (int)((n + kVoxBlock - 1) / kVoxBlock));
   const size_t corr_stride = round_up(K * n * sizeof(int), 256), mahal_stride = round_up(K * n * 6 * sizeof(double), 256);
@@ -1014,7 +1026,7 @@ void do_align_voxel_batch(ngicp* h, int B, const float* guesses, float* T_out, i
   w.vox_corr.ensure((size_t)B * 2 * corr_stride);
   w.vox_mahal.ensure((size_t)B * 2 * mahal_stride);
   VoxelPassArgs shared;
-  fill_voxel_shared(h, shared);
+  fill_voxel_shared(h, shared, vm);
   shared.mode = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? 2 : 3;
   SolveArgs solve = c.sa;
   solve.nblocks = nblocks;

@@ -1,6 +1,6 @@
 // C-ABI implementation (include/ngicp.h) — host driver for the HIP kernels.
 // One handle == one nano_gicp::NanoGICP instance (/root/reference/include/nano_gicp/nano_gicp.hpp:58-137).
-// One translation unit: the handle is in ngicp_handle.h, the voxel-map builds in ngicp_voxelmap.h, the registration loops in ngicp_align.h; here
+// One translation unit: the handle is in ngicp_handle.h, the voxel-map builds in ngicp_voxelmap.h, the rolling voxel map in ngicp_rollmap.h, the registration loops in ngicp_align.h; here
 // are the index build, the covariances, the queries' host helpers and the extern "C" surface.
 // Built for gfx950 only:  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC
 #include "../../include/ngicp.h"
@@ -30,6 +30,7 @@
 #include "ngicp_batch.h"
 #include "ngicp_voxel.h"
 #include "ngicp_voxel_batch.h"
+#include "ngicp_voxel_roll.h"
 
 using namespace ngk;
 
@@ -425,6 +426,7 @@ void drop_voxel_map(ngicp* h) {
 }  // namespace
 
 #include "ngicp_voxelmap.h"
+#include "ngicp_rollmap.h"
 #include "ngicp_align.h"
 
 namespace {
@@ -1005,7 +1007,7 @@ int ngicp_get_correspondences(ngicp_t* h, int* corr_out, float* sqd_out) {
     if (h->voxel_res > 0.0)  // voxel numbers; distances to (float)mean_v
       hipLaunchKernelGGL(k_voxel_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                          (const int*)h->vox_corr[st.hot.cur].as<int>() + (h->voxel_nbr == NGICP_VOX_DIRECT27 ? (size_t)vox_nbr_centre<27>() * n : 0), h->src.dev->pts(), (int)n,
-                         (const double*)h->vmap.rec.as<double>(), h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
+                         voxel_map_view(h).rec, h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
     else
     hipLaunchKernelGGL(k_corr_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->tpt[st.hot.cur].as<float4>(), h->src.dev->qpts.as<float4>(),
                        h->src.dev->pts(), h->tgt.dev->pts(), (int)n, h->knn_idx.as<int>(), sqd_out ? h->knn_d2.as<float>() : nullptr, dst->hot.lin_f);
@@ -1024,6 +1026,7 @@ int ngicp_set_voxel_resolution(ngicp_t* h, double res) {
     if (res == h->voxel_res) return;
     h->voxel_res = res;
     h->vmap.invalidate();  // (rebuilt at the next use; with res == 0 its memory stays with the handle, its holds on the target are dropped)
+    roll_clear(h);         // the rolling map's sums belong to one resolution (whether or not that setting is on)
     h->hook_valid = 0;     // correspondences of the other mode, or voxel numbers of another lattice
   });
 }
@@ -1074,20 +1077,19 @@ int ngicp_voxelmap_size(ngicp_t* h, size_t* n_voxels) {
   return guarded(h, [&] {
     if (!n_voxels) throw ArgError{NGICP_ERR_ARG, "null output"};
     if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "no voxel resolution set (ngicp_set_voxel_resolution)"};
-    ensure_voxel_map(h);
-    *n_voxels = h->vmap.n_vox;
+    *n_voxels = ensure_voxel_map(h).n_vox;
   });
 }
 
 int ngicp_voxelmap_get(ngicp_t* h, int* ijk_n3, double* mean_n3, double* cov_n6, int* count_n) {
   return guarded(h, [&] {
     if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "no voxel resolution set (ngicp_set_voxel_resolution)"};
-    ensure_voxel_map(h);
-    const size_t nv = h->vmap.n_vox;
+    const VoxelMapView vm = ensure_voxel_map(h);
+    const size_t nv = vm.n_vox;
     std::vector<double> rec(nv * kVoxRec);
     std::vector<unsigned long long> keys(nv);
-    HIP_TRY(hipMemcpyAsync(rec.data(), h->vmap.rec.p, rec.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(keys.data(), h->vmap.vkeys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(rec.data(), vm.rec, rec.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(keys.data(), vm.vkeys, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (size_t v = 0; v < nv; ++v) {
       if (ijk_n3) {
@@ -1156,6 +1158,77 @@ int ngicp_keyframe_voxelmap_get(ngicp_t* h, int id, size_t* n_vox, int* ijk_n3, 
       if (count_n) count_n[v] = (int)rec[v * kVoxRec + 9];
     }
   });
+}
+
+// ---- the rolling voxel map (include/ngicp.h "rolling voxel map"; ngicp_rollmap.h) ----
+int ngicp_set_voxel_rolling(ngicp_t* h, int on) {
+  return guarded(h, [&] {
+    const int v = on ? 1 : 0;
+    if (v == h->voxel_roll) return;
+    h->voxel_roll = v;  // (both maps stay as they are: the entries read the other one from now on)
+    h->hook_valid = 0;  // the correspondences number the other map's voxels
+  });
+}
+
+int ngicp_get_voxel_rolling(const ngicp_t* h, int* on) {
+  if (!h || !on) return NGICP_ERR_ARG;
+  *on = h->voxel_roll;
+  return NGICP_OK;
+}
+
+int ngicp_voxel_rolling_insert(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], size_t* n_new, size_t* n_touched) {
+  if (!from) return NGICP_ERR_ARG;
+  return guarded(h, [&] {
+    if (!T_colmajor) throw ArgError{NGICP_ERR_ARG, "null transform"};
+    roll_insert(h, from, T_colmajor, n_new, n_touched);
+  });
+}
+
+int ngicp_voxel_rolling_evict(ngicp_t* h, const float centre[3], double max_dist, long long min_stamp, size_t* n_removed) {
+  return guarded(h, [&] { roll_evict(h, centre, max_dist, min_stamp, n_removed); });
+}
+
+int ngicp_voxel_rolling_clear(ngicp_t* h) {
+  return guarded(h, [&] { roll_clear(h); });
+}
+
+int ngicp_voxel_rolling_get(ngicp_t* h, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n, long long* stamp_n) {
+  return guarded(h, [&] {
+    const ngicp::RollMap& r = h->roll;
+    const size_t nv = r.n_vox;
+    if (n_vox) *n_vox = nv;
+    if ((!ijk_n3 && !sum_n3 && !covsum_n6 && !count_n && !stamp_n) || nv == 0) return;
+    std::vector<double> sums(nv * kVoxRec);
+    std::vector<unsigned long long> keys(nv);
+    std::vector<long long> stamps(nv);
+    HIP_TRY(hipMemcpyAsync(sums.data(), r.sums.p, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(keys.data(), r.vkeys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(stamps.data(), r.stamps.p, stamps.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    for (size_t v = 0; v < nv; ++v) {
+      if (ijk_n3) {
+        ijk_n3[3 * v + 0] = (int)(keys[v] & 0x1fffffull) - kVoxBias;
+        ijk_n3[3 * v + 1] = (int)((keys[v] >> 21) & 0x1fffffull) - kVoxBias;
+        ijk_n3[3 * v + 2] = (int)((keys[v] >> 42) & 0x1fffffull) - kVoxBias;
+      }
+      if (sum_n3) std::memcpy(sum_n3 + 3 * v, &sums[v * kVoxRec], 3 * sizeof(double));
+      if (covsum_n6) std::memcpy(covsum_n6 + 6 * v, &sums[v * kVoxRec + 3], 6 * sizeof(double));
+      if (count_n) count_n[v] = (int)sums[v * kVoxRec + 9];
+      if (stamp_n) stamp_n[v] = stamps[v];
+    }
+  });
+}
+
+int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vox, size_t* capacity_vox, size_t* table_slots, double* last_insert_ms, double* last_evict_ms) {
+  if (!h) return NGICP_ERR_ARG;
+  if (inserts) *inserts = h->roll.inserts;
+  if (n_vox) *n_vox = h->roll.n_vox;
+  if (capacity_vox) *capacity_vox = h->roll.cap;
+  if (table_slots) *table_slots = h->roll.slots;
+  if (last_insert_ms) *last_insert_ms = h->roll.last_insert_ms;
+  if (last_evict_ms) *last_evict_ms = h->roll.last_evict_ms;
+  return NGICP_OK;
 }
 
 int ngicp_target_knn(ngicp_t* h, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {

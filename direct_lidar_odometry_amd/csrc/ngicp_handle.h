@@ -215,6 +215,15 @@ struct Slot {
   }
 };
 
+// What a voxelized pass reads of a voxel map, whoever filled it: the target's map (ngicp::VoxelMap) or the rolling map (ngicp::RollMap).
+struct VoxelMapView {
+  const ulonglong2* table;
+  unsigned int mask;
+  const double* rec;
+  const unsigned long long* vkeys;
+  size_t n_vox;
+};
+
 struct LoopCtx;  // the per-alignment launch arguments (defined with the registration loop)
 constexpr int kMaxPersistPasses = 2048;  // alignments with more possible passes than this take one launch per pass (the ring of views is 512 bytes per pass)
 constexpr int kMaxTickPasses = 1024;  // passes of an alignment whose timestamps the persistent kernel records when profiling is on
@@ -393,6 +402,15 @@ struct ngicp {
   double last_parts_ms = 0.0, last_merge_ms = 0.0;  // event times of the last merged build: its part builds, the merge itself
   DevBuf vox_part_tab;                   // a merged build's table: [m + 1] int offsets, then (8-byte aligned) [m] record pointers
   hipEvent_t ev_vox_c = nullptr;         // between the parts and the merge
+  // the rolling voxel map (ngicp_voxel_roll.h): a map that inserts and evictions maintain instead of a build from the target
+  int voxel_roll = 0;                    // ngicp_set_voxel_rolling; remembered while the voxel mode is off
+  struct RollMap {
+    size_t n_vox = 0, cap = 0, slots = 0;  // voxels, capacity of the per-voxel arrays (doubling), hash table slots (>= 2 * n_vox, a power of two)
+    long long inserts = 0;                 // accepted inserts since the last clear: the stamp of the last one
+    DevBuf sums, rec, vkeys, stamps, table;  // [cap][kVoxRec] {S 3, C 6, n}, [cap][kVoxRec] records, [cap] keys, [cap] stamps, [slots] {key, voxel number}
+    double last_insert_ms = 0.0, last_evict_ms = 0.0;  // device event times
+  } roll;
+  DevBuf roll_q, roll_sums, roll_hit, roll_tmp;  // an insert's transformed points, per-scan-voxel sums and lookup results; an eviction's compaction workspace
 };
 
 namespace {

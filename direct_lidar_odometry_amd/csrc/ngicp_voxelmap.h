@@ -204,15 +204,35 @@ void build_voxel_map_merged(ngicp* h) {
   ++h->merged_builds;
 }
 
+// Is the rolling map (ngicp_rollmap.h) the map of this handle's voxelized entries?  Then the target slot is not read at all.
+bool rolling_active(const ngicp* h) { return h->voxel_roll && h->voxel_res > 0.0; }
+
+// The map the voxelized entries use as it stands now, without building anything: the rolling map while that setting is on, else the
+// target's (what the correspondences of the last linearisation number).
+VoxelMapView voxel_map_view(const ngicp* h) {
+  if (rolling_active(h)) {
+    const ngicp::RollMap& r = h->roll;
+    return VoxelMapView{r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1), r.rec.as<double>(), r.vkeys.as<unsigned long long>(), r.n_vox};
+  }
+  const ngicp::VoxelMap& m = h->vmap;
+  return VoxelMapView{m.table.as<ulonglong2>(), m.mask, m.rec.as<double>(), m.vkeys.as<unsigned long long>(), m.n_vox};
+}
+
 // The voxel map of the current target, its covariances (computed if missing, as for align) and the resolution: built at the first use
-// after any of the three changed, or after the route it would be built by did (ngicp_set_voxel_submap_merge).
-void ensure_voxel_map(ngicp* h) {
+// after any of the three changed, or after the route it would be built by did (ngicp_set_voxel_submap_merge).  With the rolling setting
+// on: the rolling map as inserts and evictions left it (nothing is built, the target and the merged setting are not consulted); an
+// empty one is NGICP_ERR_STATE, where a missing target would be.
+VoxelMapView ensure_voxel_map(ngicp* h) {
+  if (rolling_active(h)) {
+    if (h->roll.n_vox == 0) throw ArgError{NGICP_ERR_STATE, "the rolling voxel map is empty (ngicp_voxel_rolling_insert)"};
+    return voxel_map_view(h);
+  }
   ensure_slot_ready(h, h->tgt, "target");
   if (h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
   const double* covs = covs_for(h, h->tgt_covs, h->tgt.dev);
   ngicp::VoxelMap& m = h->vmap;
   const int merged = merged_route_applies(h) ? 1 : 0;
-  if (m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && m.merged == merged) return;
+  if (m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && m.merged == merged) return voxel_map_view(h);
   m.invalidate();
   if (merged) build_voxel_map_merged(h);
   else build_voxel_map_from_points(h, covs);
@@ -222,6 +242,7 @@ void ensure_voxel_map(ngicp* h) {
   m.covs = h->tgt_covs.data;
   m.valid = true;
   ++h->voxel_builds;
+  return voxel_map_view(h);
 }
 
 }  // namespace

@@ -89,6 +89,8 @@ EXPORTS = [
     "ngicp_set_voxel_neighbors", "ngicp_get_voxel_neighbors", "ngicp_voxel_correspondences", "ngicp_voxelmap_builds",
     "ngicp_voxel_align_batch",
     "ngicp_set_voxel_submap_merge", "ngicp_get_voxel_submap_merge", "ngicp_voxelmap_merge_stats", "ngicp_keyframe_voxelmap_get",
+    "ngicp_set_voxel_rolling", "ngicp_get_voxel_rolling", "ngicp_voxel_rolling_insert", "ngicp_voxel_rolling_evict", "ngicp_voxel_rolling_clear",
+    "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -185,6 +187,14 @@ def load_library() -> C.CDLL:
     L.ngicp_get_voxel_submap_merge.argtypes = [vp, c_i32p]
     L.ngicp_voxelmap_merge_stats.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_f64p, c_f64p]
     L.ngicp_keyframe_voxelmap_get.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t), c_i32p, c_f64p, c_f64p, c_i32p]
+    c_i64p, c_szp = C.POINTER(C.c_longlong), C.POINTER(C.c_size_t)
+    L.ngicp_set_voxel_rolling.argtypes = [vp, C.c_int]
+    L.ngicp_get_voxel_rolling.argtypes = [vp, c_i32p]
+    L.ngicp_voxel_rolling_insert.argtypes = [vp, vp, c_f32p, c_szp, c_szp]
+    L.ngicp_voxel_rolling_evict.argtypes = [vp, c_f32p, C.c_double, C.c_longlong, c_szp]
+    L.ngicp_voxel_rolling_clear.argtypes = [vp]
+    L.ngicp_voxel_rolling_get.argtypes = [vp, c_szp, c_i32p, c_f64p, c_f64p, c_i32p, c_i64p]
+    L.ngicp_voxel_rolling_stats.argtypes = [vp, c_i64p, c_szp, c_szp, c_szp, c_f64p, c_f64p]
     _lib = L
     return L
 
@@ -341,6 +351,54 @@ class NanoGICP:
         ijk = np.empty((n, 3), dtype=np.int32); s = np.empty((n, 3)); c6 = np.empty((n, 6)); cnt = np.empty(n, dtype=np.int32)
         self._ck(self._L.ngicp_keyframe_voxelmap_get(self._h, int(kid), C.byref(nv), _p(ijk, c_i32p), _p(s, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p)))
         return ijk, s, c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(n, 3, 3), cnt
+
+    # ---- the rolling voxel map (include/ngicp.h "rolling voxel map") ----
+    def setVoxelRolling(self, on: bool):
+        """Off (the default): the voxel map is that of the target.  On (with setVoxelResolution > 0): align / linearize / compute_error /
+        alignBatchVoxel / voxelMap use a map that insertIntoVoxelMap and evictVoxelMap maintain across frames; the target is not read at
+        all.  Remembered while the voxel mode is off; switching off keeps the rolling map for the next time it is switched on."""
+        self._ck(self._L.ngicp_set_voxel_rolling(self._h, 1 if on else 0))
+
+    def getVoxelRolling(self) -> bool:
+        on = C.c_int(0)
+        self._ck(self._L.ngicp_get_voxel_rolling(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def insertIntoVoxelMap(self, producer: "NanoGICP", T) -> tuple:
+        """Add the producer's source cloud (the producer may be this object), transformed by the float pose T, to the rolling map with
+        its source covariances (computed if missing, as addKeyframe does).  -> (voxels created, voxels of the scan).  A scan with a
+        transformed point that has no voxel raises and changes nothing."""
+        t = _colmajor16(T, np.float32); n_new, n_touched = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_insert(self._h, producer._h, _p(t, c_f32p), C.byref(n_new), C.byref(n_touched)))
+        return n_new.value, n_touched.value
+
+    def evictVoxelMap(self, centre=(0.0, 0.0, 0.0), max_dist: float = 0.0, min_stamp: int = 0) -> int:
+        """Remove the voxels whose centre lies farther than max_dist from `centre` (max_dist > 0) or whose last insert is older than
+        min_stamp (min_stamp > 0; inserts count from 1).  Survivors keep their order.  -> voxels removed."""
+        c = np.ascontiguousarray(centre, dtype=np.float32).reshape(3); n = C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_evict(self._h, _p(c, c_f32p), float(max_dist), int(min_stamp), C.byref(n)))
+        return n.value
+
+    def clearVoxelMap(self): self._ck(self._L.ngicp_voxel_rolling_clear(self._h))
+
+    def rollingVoxelMap(self):
+        """-> (ijk (V, 3) int32, sum (V, 3), covsum (V, 3, 3), count (V,) int32, stamp (V,) int64): the rolling map's state, voxels in
+        order of first insertion (voxelMap() gives the means and covariances in the same numbering while the setting is on)."""
+        nv = C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_get(self._h, C.byref(nv), None, None, None, None, None))
+        n = nv.value
+        ijk = np.empty((n, 3), dtype=np.int32); s = np.empty((n, 3)); c6 = np.empty((n, 6)); cnt = np.empty(n, dtype=np.int32)
+        st = np.empty(n, dtype=np.int64)
+        self._ck(self._L.ngicp_voxel_rolling_get(self._h, C.byref(nv), _p(ijk, c_i32p), _p(s, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p),
+                                                 _p(st, C.POINTER(C.c_longlong))))
+        return ijk, s, c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(n, 3, 3), cnt, st
+
+    def voxelRollingStats(self) -> dict:
+        """{inserts: accepted since the last clear; n_vox, capacity_vox, table_slots; last_insert_ms, last_evict_ms: device event times}."""
+        ins, nv, cap, sl = C.c_longlong(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        ti, te = C.c_double(0), C.c_double(0)
+        self._ck(self._L.ngicp_voxel_rolling_stats(self._h, C.byref(ins), C.byref(nv), C.byref(cap), C.byref(sl), C.byref(ti), C.byref(te)))
+        return dict(inserts=ins.value, n_vox=nv.value, capacity_vox=cap.value, table_slots=sl.value, last_insert_ms=ti.value, last_evict_ms=te.value)
 
     def setTuning(self, voxel_size: float = 0.0, lanes_per_query: int = 0):
         self._ck(self._L.ngicp_set_tuning(self._h, float(voxel_size), int(lanes_per_query)))

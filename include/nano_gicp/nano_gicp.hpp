@@ -299,7 +299,7 @@ class NanoGICP {
   void align(PointCloudSource& output, const Matrix4& guess) {
     converged_ = false;
     set_identity(final_transformation_);
-    if (!h_ || !input_ || !(target_ || device_target_)) {  // PCL's initCompute() fails silently
+    if (!h_ || !input_ || !haveTarget()) {  // PCL's initCompute() fails silently
       std::fprintf(stderr, "[NanoGICP] align(): no input source/target\n");
       return;
     }
@@ -325,7 +325,7 @@ class NanoGICP {
   void alignPoseOnly(const Matrix4& guess) {
     converged_ = false;
     set_identity(final_transformation_);
-    if (!h_ || !input_ || !(target_ || device_target_)) return;
+    if (!h_ || !input_ || !haveTarget()) return;
     int conv = 0, nit = 0;
     int rc = ngicp_align(h_, guess.data(), final_transformation_.data(), &conv, &nit, final_hessian_.data(), nullptr, 0);
     converged_ = conv != 0;
@@ -442,6 +442,66 @@ class NanoGICP {
     return m;
   }
 
+  // ---- the rolling voxel map (no counterpart in the reference; include/ngicp.h "rolling voxel map") ----
+  // setVoxelRolling(true) with setVoxelResolution(res > 0): align() and alignBatchVoxel() use a voxel map that lives on the device across
+  // frames - insertIntoVoxelMap adds a scan at a pose, evictVoxelMap drops voxels by distance or age - instead of a map built from the
+  // target, which is then not read at all (it need not be set).  Remembered while the voxel mode is off; switching off keeps the map.
+  void setVoxelRolling(bool on) {
+    if (h_ && check(ngicp_set_voxel_rolling(h_, on ? 1 : 0), "setVoxelRolling")) voxel_rolling_ = on;
+  }
+  bool getVoxelRolling() const { return voxel_rolling_; }
+  // what an insert did: voxels it created, voxels of the scan (created or added to); ok false when it was refused (nothing changed)
+  struct VoxelMapInsert {
+    bool ok = false;
+    size_t n_new = 0, n_touched = 0;
+  };
+  // add `producer`'s current source cloud (the producer may be *this: align, then insert at the result), transformed by T on the device,
+  // with its source covariances (computed if missing, as addKeyframe does)
+  VoxelMapInsert insertIntoVoxelMap(NanoGICP& producer, const Matrix4& T) {
+    VoxelMapInsert r;
+    r.ok = h_ && check(ngicp_voxel_rolling_insert(h_, producer.h_, T.data(), &r.n_new, &r.n_touched), "insertIntoVoxelMap");
+    return r;
+  }
+  // remove the voxels whose centre is farther than max_dist from `centre` (max_dist > 0) or whose last insert is older than min_stamp
+  // (min_stamp > 0; inserts count from 1); returns how many went
+  size_t evictVoxelMap(const float centre[3], double max_dist, long long min_stamp = 0) {
+    size_t n = 0;
+    if (h_) check(ngicp_voxel_rolling_evict(h_, centre, max_dist, min_stamp, &n), "evictVoxelMap");
+    return n;
+  }
+  void clearVoxelMap() {
+    if (h_) check(ngicp_voxel_rolling_clear(h_), "clearVoxelMap");
+  }
+  // the map's state, voxels in order of first insertion: the index, the sums of the points and of the (rotated) covariances
+  // {xx, xy, xz, yy, yz, zz}, the count and the number of the last insert that added a point.  Empty on error.
+  struct RollingVoxelMap {
+    std::vector<int> ijk;          // n x 3
+    std::vector<double> sum;       // n x 3
+    std::vector<double> covsum;    // n x 6
+    std::vector<int> count;        // n
+    std::vector<long long> stamp;  // n
+    size_t size() const { return count.size(); }
+  };
+  RollingVoxelMap rollingVoxelMap() {
+    RollingVoxelMap m;
+    size_t n = 0;
+    if (!h_ || !check(ngicp_voxel_rolling_get(h_, &n, nullptr, nullptr, nullptr, nullptr, nullptr), "rollingVoxelMap")) return m;
+    m.ijk.resize(3 * n); m.sum.resize(3 * n); m.covsum.resize(6 * n); m.count.resize(n); m.stamp.resize(n);
+    if (!check(ngicp_voxel_rolling_get(h_, &n, m.ijk.data(), m.sum.data(), m.covsum.data(), m.count.data(), m.stamp.data()), "rollingVoxelMap")) m = RollingVoxelMap();
+    return m;
+  }
+  // accepted inserts since the last clear, voxels, capacity of the per-voxel arrays, table slots; device time of the last insert / eviction
+  struct VoxelRollingStats {
+    long long inserts = 0;
+    size_t n_vox = 0, capacity_vox = 0, table_slots = 0;
+    double last_insert_ms = 0.0, last_evict_ms = 0.0;
+  };
+  VoxelRollingStats voxelRollingStats() const {
+    VoxelRollingStats s;
+    if (h_) check(ngicp_voxel_rolling_stats(h_, &s.inserts, &s.n_vox, &s.capacity_vox, &s.table_slots, &s.last_insert_ms, &s.last_evict_ms), "voxelRollingStats");
+    return s;
+  }
+
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
   // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN
   // after +inf); medianRange: rank n / 2, the reference's median_curr.  which: 0 = the input source, 1 = the target, 2 = the scan
@@ -474,7 +534,7 @@ class NanoGICP {
   template <class Entry>
   std::vector<BatchResult> alignBatchThrough(Entry entry, const char* name, const std::vector<Matrix4>& guesses) {
     std::vector<BatchResult> out;
-    if (!h_ || !input_ || !(target_ || device_target_) || guesses.empty()) return out;
+    if (!h_ || !input_ || !haveTarget() || guesses.empty()) return out;
     const size_t n = guesses.size();
     std::vector<float> g(n * 16), T(n * 16);
     std::vector<int> conv(n), nit(n);
@@ -598,6 +658,8 @@ class NanoGICP {
     if (n) (source ? ngicp_get_source_covs : ngicp_get_target_covs)(h_, reinterpret_cast<double*>(v.data()));
     return v;
   }
+  // is there something to align against: a host target, a device submap, or (voxel mode with the rolling setting) the rolling map
+  bool haveTarget() const { return target_ || device_target_ || (voxel_rolling_ && voxel_resolution_ > 0.0); }
   bool check(int rc, const char* what) const {
     if (rc != NGICP_OK) std::fprintf(stderr, "[NanoGICP] %s: %s\n", what, h_ ? ngicp_last_error(h_) : "no engine");
     return rc == NGICP_OK;
@@ -633,6 +695,7 @@ class NanoGICP {
   bool converged_ = false;
   int nr_iterations_ = 0;
   double voxel_resolution_ = 0.0;
+  bool voxel_rolling_ = false;
   mutable CovVector cache_src_, cache_tgt_;
 };
 

@@ -273,6 +273,58 @@ int ngicp_voxelmap_merge_stats(const ngicp_t* h, long long* merged_builds, long 
  * covsum (n x 6: xx, xy, xz, yy, yz, zz), count (n).  The array pointers may be NULL to ask for the size only.  NGICP_ERR_STATE while
  * the voxel mode is off, NGICP_ERR_ARG for an unknown id. */
 int ngicp_keyframe_voxelmap_get(ngicp_t* h, int id, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n);
+/* --- rolling voxel map: insert scans, evict voxels, align (csrc/ngicp_voxel_roll.h) ---------------------------------
+ * A SETTING of the voxelized mode, OFF by default.  With it off nothing changes anywhere.  With it on (and res > 0) the voxelized
+ * entries align against a device-resident map that the caller maintains across frames, instead of a map built from the target.  It is
+ * this project's own definition; no fidelity to any outside library is claimed.
+ *   state                      per voxel v, in double: S_v (3 entries), C_v (6 entries: xx, xy, xz, yy, yz, zz), a count n_v and a stamp
+ *                              t_v, the number of the last insert that added a point to v; the handle counts its accepted inserts
+ *                              from 1.  Beside them the record the passes read, in the voxel map's format: mean_v = S_v / (double)n_v,
+ *                              cov_v = C_v / (double)n_v, n_v.
+ *   insert of cloud A at the   A is `from`'s current source cloud, as for ngicp_keyframe_add_transformed; its source covariances C_j are
+ *   float pose T               computed with `from`'s k and regularisation if missing, exactly as ngicp_keyframe_add does.
+ *                              q_j = T a_j in the order of ngicp_transform_source (pcl::transformPointCloud); the voxel of q_j by the
+ *                              mode's rule, floorf(q * inv_res), |i| < 2^20.  Per voxel of the scan, in ascending original index of A,
+ *                              every sum started at 0.0: s = sum (double)q_j, c = R (sum C_j) R^T with R the row-major double image of
+ *                              T's float 3x3 block - ONE rotation per voxel, applied to the sum, evaluated as the passes evaluate
+ *                              R C_a R^T - and n.  For a voxel the map has: S = S + s, C = C + c (one addition per entry), n += n,
+ *                              t = this insert.  A new voxel starts from the scan's sums themselves.  The records of the touched voxels
+ *                              are rewritten by one division per entry.
+ *   numbering                  voxels are numbered in order of first insertion; the new voxels of one insert in ascending (iz, iy, ix).
+ *                              An insert never changes the number of an existing voxel.
+ *   refusal                    an insert with a transformed point that has no voxel (2^20 or more voxels from the origin on an axis, or
+ *                              not finite) returns NGICP_ERR_ARG and changes nothing: map, counter and stamps stay as they were.
+ *   evict(c, max_dist,         voxel v is removed if max_dist > 0 and ((dx*dx + dy*dy) + dz*dz) > max_dist*max_dist with
+ *         min_stamp)           d = ((double)i + 0.5) * res - (double)c per axis (all in double, nothing fused), or if min_stamp > 0 and
+ *                              t_v < min_stamp.  Survivors keep their relative order and are renumbered densely.  The map may end empty.
+ *   clear                      empties the map and resets the insert counter.  ANY change of the resolution does the same (the sums belong
+ *                              to one resolution), whether or not the setting is on; a change of neighbourhood keeps the map.
+ * Insert, evict and clear drop the correspondences and the hooks' state, as a change of resolution does: ngicp_compute_error,
+ * ngicp_get_correspondences and ngicp_voxel_correspondences return NGICP_ERR_STATE until the next linearisation.
+ * While the setting is on and res > 0: ngicp_align, ngicp_linearize, ngicp_compute_error, ngicp_voxel_align_batch, ngicp_voxelmap_size
+ * and ngicp_voxelmap_get use the rolling map (ngicp_voxelmap_get then lists the voxels in the numbering above).  THE TARGET SLOT IS NOT
+ * READ AT ALL: it may be empty or hold anything; an empty rolling map is NGICP_ERR_STATE where a missing target would be.  The merged
+ * setting (ngicp_set_voxel_submap_merge) is ignored.  ngicp_voxelmap_builds and ngicp_stats::voxelmap_ms keep their meaning - inserts
+ * are not builds - and ngicp_stats::n_tgt reports the voxel count.  The exact path, the queries, keyframes, the submap, the filters and
+ * the range median are unaffected.
+ * Device memory: 208 bytes per voxel of capacity (80 sums, 80 record, 8 key, 8 stamp, 32 of the key table, which stays at most half
+ * full); the per-voxel arrays start at 1024 voxels and double, the table starts at 64 slots and doubles.  An eviction uses a grow-only
+ * workspace of 176 bytes per voxel; an insert 100 bytes per scan point on top of the voxel builds' sort buffers.
+ * ngicp_set_voxel_rolling: on != 0 switches the setting on.  Callable in any mode and remembered.  Setting the value already set does
+ * nothing.  Switching off keeps the rolling map and returns every entry to the target-based map; switching on again finds the map as it
+ * was left.  A change drops the correspondences and the hooks' state.
+ * ngicp_voxel_rolling_insert / _evict: NGICP_ERR_STATE unless the setting is on and res > 0.  `from` may be h itself (the usual loop:
+ * align, then insert at the result).  *n_new: voxels the insert created; *n_touched: voxels of the scan (created or added to).
+ * ngicp_voxel_rolling_get: the state in the numbering above - ijk (n x 3 ints), S (n x 3), C (n x 6), n (n), stamps (n); every array
+ * pointer may be NULL.  ngicp_voxel_rolling_stats: accepted inserts since the last clear, voxels, capacity of the per-voxel arrays,
+ * table slots, and the device event times of the last insert and the last eviction. */
+int ngicp_set_voxel_rolling(ngicp_t* h, int on);
+int ngicp_get_voxel_rolling(const ngicp_t* h, int* on);
+int ngicp_voxel_rolling_insert(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], size_t* n_new_or_null, size_t* n_touched_or_null);
+int ngicp_voxel_rolling_evict(ngicp_t* h, const float centre[3], double max_dist, long long min_stamp, size_t* n_removed_or_null);
+int ngicp_voxel_rolling_clear(ngicp_t* h);
+int ngicp_voxel_rolling_get(ngicp_t* h, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n, long long* stamp_n);
+int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vox, size_t* capacity_vox, size_t* table_slots, double* last_insert_ms, double* last_evict_ms);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
