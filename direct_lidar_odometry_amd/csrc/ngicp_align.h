@@ -19,6 +19,31 @@ int pass_impl() {
   return impl;
 }
 
+// The kernel variants that have no robust instantiation: with a robust kernel set, a route that would run one of them is refused
+// (a pass that silently ignored the kernel would be a wrong answer, not a slower one).
+const char* robust_unsupported_switch(const ngicp* h) {
+  if (pass_impl() == 1) return "NGICP_PASS_IMPL=1";
+  if (const char* s = std::getenv("NGICP_FUSED")) if (std::atoi(s) != 0) return "NGICP_FUSED";
+  if (const char* s = std::getenv("NGICP_QUEUE")) if (std::atoi(s) != 0) return "NGICP_QUEUE";
+  if (h->persist) return "NGICP_PERSIST";
+  if (h->head) return "NGICP_HEAD";
+  return nullptr;
+}
+void refuse_if_robust(const ngicp* h, const char* entry) {
+  if (h->robust_kind != NGICP_ROBUST_NONE)
+    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": not available with a robust kernel set (ngicp_set_robust_kernel(h, NGICP_ROBUST_NONE, 0) turns it off)"};
+}
+void refuse_robust_under_switch(const ngicp* h, const char* entry) {
+  if (h->robust_kind == NGICP_ROBUST_NONE) return;
+  if (const char* sw = robust_unsupported_switch(h))
+    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the robust kernel has no instantiation of the pass variant " + sw + " selects (unset it, or ngicp_set_robust_kernel(h, NGICP_ROBUST_NONE, 0))"};
+}
+void fill_robust(const ngicp* h, int& kind, double& c, double& c2) {
+  kind = h->robust_kind;
+  c = h->robust_width;
+  c2 = h->robust_width * h->robust_width;
+}
+
 void launch_pass(ngicp* h, const PassArgs& a, int nblocks, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
   // 32-query batches, 2 lanes per query.  Two builds of the kernel: 3 waves per SIMD (129 VGPRs), and 4 (128 VGPRs, two spilled
   // dwords, 4 blocks per CU) for grids of more than two rounds of blocks, where the launch is bound by how many blocks pass through
@@ -53,6 +78,13 @@ void launch_pass(ngicp* h, const PassArgs& a, int nblocks, hipStream_t s, hipEve
       hipExtLaunchKernelGGL((k_gicp_pass<2, 4, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
     else
       hipExtLaunchKernelGGL((k_gicp_pass<2, 3, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
+    return;
+  }
+  if (a.robust_kind != NGICP_ROBUST_NONE) {  // (the robust instantiations: the same kernel with the term weighted in its K4 leg and its K3 tail)
+    if (four)
+      hipExtLaunchKernelGGL((k_gicp_pass<2, 4, false, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
+    else
+      hipExtLaunchKernelGGL((k_gicp_pass<2, 3, false, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
     return;
   }
   if (four)
@@ -103,6 +135,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
   }
 
   PassArgs& a = c.pa;
+  fill_robust(h, a.robust_kind, a.robust_c, a.robust_c2);
   a.qpts = S.qpts.as<float4>();
   a.batches = S.batches.as<int2>();
   a.batch_boxes = S.batch_boxes.as<float>();
@@ -615,6 +648,7 @@ void launch_persist_one(ngicp* h, const LoopCtx& c, long launched, hipEvent_t st
 }
 
 void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride) {
+  refuse_robust_under_switch(h, "ngicp_align");
   Alignment al;
   reset_results(h);
   LoopCtx c;
@@ -682,8 +716,17 @@ struct VoxelCtx {
 // the pass of the neighbourhood in c.pa.nbr: k_vgicp_pass for DIRECT1, k_vgicp_pass_n<K> for DIRECT7 / DIRECT27; the same grid
 void launch_voxel_pass(ngicp* h, const VoxelCtx& c, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
   const dim3 grid((unsigned)c.nblocks), block(kVoxBlock);
+  if (c.pa.robust_kind != NGICP_ROBUST_NONE) {  // (the robust instantiations of the same three kernels)
+    switch (c.pa.nbr) {
+      case NGICP_VOX_DIRECT1: hipExtLaunchKernelGGL(k_vgicp_pass<true>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+      case NGICP_VOX_DIRECT7: hipExtLaunchKernelGGL((k_vgicp_pass_n<7, true>), grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+      case NGICP_VOX_DIRECT27: hipExtLaunchKernelGGL((k_vgicp_pass_n<27, true>), grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+      default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
+    }
+    return;
+  }
   switch (c.pa.nbr) {
-    case NGICP_VOX_DIRECT1: hipExtLaunchKernelGGL(k_vgicp_pass, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
+    case NGICP_VOX_DIRECT1: hipExtLaunchKernelGGL(k_vgicp_pass<>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
     case NGICP_VOX_DIRECT7: hipExtLaunchKernelGGL(k_vgicp_pass_n<7>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
     case NGICP_VOX_DIRECT27: hipExtLaunchKernelGGL(k_vgicp_pass_n<27>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
     default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
@@ -705,6 +748,7 @@ void fill_voxel_shared(ngicp* h, VoxelPassArgs& a, const VoxelMapView& m) {
   a.slot_stride = (int)S.n;
   a.mode = 3;
   a.t_first = nullptr;
+  fill_robust(h, a.robust_kind, a.robust_c, a.robust_c2);
 }
 
 // prepare_loop readies the slots, the covariances, the state, the trace and the solver's arguments exactly as for the exact path; the
@@ -769,6 +813,8 @@ struct HookCtx {
 };
 void prepare_hook(ngicp* h, HookCtx& k) {
   k.vox = h->voxel_res > 0.0;
+  if (!k.vox && h->robust_kind != NGICP_ROBUST_NONE && pass_impl() == 1)  // (the one switch the hooks' pass obeys)
+    throw ArgError{NGICP_ERR_ARG, "linearize / compute_error: the robust kernel has no instantiation of the pass variant NGICP_PASS_IMPL=1 selects"};
   if (k.vox) prepare_voxel_loop(h, k.vc);
   else prepare_loop(h, k.c);
 }

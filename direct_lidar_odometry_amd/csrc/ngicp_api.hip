@@ -31,6 +31,7 @@
 #include "ngicp_voxel.h"
 #include "ngicp_voxel_batch.h"
 #include "ngicp_voxel_roll.h"
+#include "ngicp_robust.h"
 
 using namespace ngk;
 
@@ -882,6 +883,7 @@ int ngicp_align(ngicp_t* h, const float guess[16], float T_out[16], int* converg
 int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_align_batch");
+    refuse_if_robust(h, "ngicp_align_batch");
     check_batch_args("ngicp_align_batch", n_guesses, guesses, T_out, converged, nr_iterations);
     do_align_batch(h, (int)n_guesses, guesses, T_out, converged, nr_iterations, final_hessians);
   });
@@ -890,6 +892,7 @@ int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float*
 int ngicp_voxel_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
   return guarded(h, [&] {
     if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "ngicp_voxel_align_batch: the voxelized mode is off (ngicp_set_voxel_resolution)"};
+    refuse_if_robust(h, "ngicp_voxel_align_batch");
     check_batch_args("ngicp_voxel_align_batch", n_guesses, guesses, T_out, converged, nr_iterations);
     do_align_voxel_batch(h, (int)n_guesses, guesses, T_out, converged, nr_iterations, final_hessians);
   });
@@ -1062,6 +1065,68 @@ int ngicp_voxel_correspondences(ngicp_t* h, int* corr_n_by_K, size_t capacity_in
     hipLaunchKernelGGL(k_voxel_corr_n_to_original, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int*)h->vox_corr[st.hot.cur].as<int>(), h->src.dev->pts(), (int)n,
                        (int)K, (int)n, h->vox_corr_out.as<int>());
     HIP_TRY(hipMemcpyAsync(corr_n_by_K, h->vox_corr_out.p, n * K * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+  });
+}
+
+int ngicp_set_robust_kernel(ngicp_t* h, int kind, double width) {
+  return guarded(h, [&] {
+    if (kind != NGICP_ROBUST_NONE && kind != NGICP_ROBUST_HUBER && kind != NGICP_ROBUST_CAUCHY && kind != NGICP_ROBUST_GEMAN_MCCLURE)
+      throw ArgError{NGICP_ERR_ARG, "robust kernel: kind must be NGICP_ROBUST_NONE (0), _HUBER (1), _CAUCHY (2) or _GEMAN_MCCLURE (3)"};
+    if (kind != NGICP_ROBUST_NONE && !(std::isfinite(width) && width > 0.0)) throw ArgError{NGICP_ERR_ARG, "robust kernel: the width must be finite and > 0"};
+    h->robust_kind = kind;
+    if (kind != NGICP_ROBUST_NONE) h->robust_width = width;  // (NONE has no width: the last one stays for ngicp_get_robust_kernel)
+    // (the stored correspondences and matrices do not depend on the kernel: the hooks' state stays valid)
+  });
+}
+
+int ngicp_get_robust_kernel(const ngicp_t* h, int* kind, double* width) {
+  if (!h) return NGICP_ERR_ARG;
+  if (kind) *kind = h->robust_kind;
+  if (width) *width = h->robust_width;
+  return NGICP_OK;
+}
+
+int ngicp_robust_terms(ngicp_t* h, const double T_colmajor[16], double* s_out, double* w_out, size_t capacity_doubles, int* K_out) {
+  return guarded(h, [&] {
+    if (!T_colmajor) throw ArgError{NGICP_ERR_ARG, "null pose"};
+    if (!h->hook_valid) throw ArgError{NGICP_ERR_STATE, "no correspondences: call ngicp_linearize or ngicp_align first"};
+    const bool vox = h->voxel_res > 0.0;
+    const size_t n = h->src.dev->n, K = vox ? (size_t)h->voxel_nbr : 1;
+    if (K_out) *K_out = (int)K;
+    if (!s_out || !w_out) throw ArgError{NGICP_ERR_ARG, "null output"};
+    if (capacity_doubles < n * K) throw ArgError{NGICP_ERR_ARG, "robust terms: an output holds fewer than n_src * K doubles"};
+    LmState st;  // (in stream order, as ngicp_get_correspondences)
+    HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int cur = st.hot.cur & 1;
+    h->robust_s.ensure(n * K * sizeof(double));
+    h->robust_w.ensure(n * K * sizeof(double));
+    RobustTermsArgs a{};
+    if (vox) {
+      const VoxelMapView vm = voxel_map_view(h);
+      a.pts = h->src.dev->pts();
+      a.corr = h->vox_corr[cur].as<int>();
+      a.rec = vm.rec;
+      a.n_vox = (int)vm.n_vox;
+      a.mahal = K > 1 ? h->vox_mahal[cur].as<double>() : h->mahal[cur].as<double>();
+    } else {
+      a.pts = h->src.dev->qpts.as<float4>();
+      a.src_sorted = h->src.dev->pts();
+      a.tpt = h->tpt[cur].as<float4>();
+      a.mahal = h->mahal[cur].as<double>();
+    }
+    a.n = (int)n;
+    a.K = (int)K;
+    a.slot_stride = (int)n;
+    a.T = pose_from_colmajor(T_colmajor);
+    fill_robust(h, a.kind, a.c, a.c2);
+    a.out_s = h->robust_s.as<double>();
+    a.out_w = h->robust_w.as<double>();
+    if (n) hipLaunchKernelGGL(k_robust_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a);
+    if (n) HIP_TRY(hipMemcpyAsync(s_out, h->robust_s.p, n * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(w_out, h->robust_w.p, n * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipGetLastError());
   });
@@ -1412,6 +1477,7 @@ int ngicp_set_profiling(ngicp_t* h, int on) {
 int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_begin");
+    refuse_if_robust(h, "ngicp_sharded_begin");
     h->shard_ctx.reset(new LoopCtx);
     LoopCtx& c = *h->shard_ctx;
     prepare_loop(h, c);
@@ -1428,6 +1494,7 @@ int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
 int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_pass");
+    refuse_if_robust(h, "ngicp_sharded_pass");
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -1445,6 +1512,7 @@ int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
 int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_null, int* done) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_step");
+    refuse_if_robust(h, "ngicp_sharded_step");
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -1475,6 +1543,7 @@ int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_nul
 int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_iterations, double final_hessian[36]) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_finish");
+    refuse_if_robust(h, "ngicp_sharded_finish");
     if (!h->sharded_active) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     hipStream_t s = h->shard_stream ? h->shard_stream : h->stream;  // the steps were enqueued there
     HIP_TRY(hipMemcpyAsync(&h->pin_state[1], h->state.p, sizeof(LmState), hipMemcpyDeviceToHost, s));

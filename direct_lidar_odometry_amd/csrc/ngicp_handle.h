@@ -372,6 +372,11 @@ struct ngicp {
   const DeviceCloud* submap_cloud = nullptr;
   std::weak_ptr<DevBuf> submap_covs;     // the covariance set ngicp_submap_set installed with it (weak: a recycled buffer is another object)
 
+  // robust kernel (include/ngicp.h "robust kernel"): remembered across mode switches, read when a pass's arguments are filled
+  int robust_kind = NGICP_ROBUST_NONE;
+  double robust_width = 1.0;
+  DevBuf robust_s, robust_w;             // ngicp_robust_terms: [n_src][K] doubles each
+
   // voxelized GICP (ngicp_voxel.h)
   double voxel_res = 0.0;  // ngicp_set_voxel_resolution: > 0 selects the mode
   int voxel_nbr = NGICP_VOX_DIRECT1;  // ngicp_set_voxel_neighbors: slots per source point (1, 7, 27); remembered while the mode is off

@@ -23,6 +23,7 @@
 #pragma once
 #include <type_traits>
 
+#include "../../include/ngicp.h"
 #include "ngicp_knn.h"
 
 namespace ngk {
@@ -77,6 +78,51 @@ __device__ __forceinline__ double err_term(const double ex, const double ey, con
   const double mey = m01 * ex + m11 * ey + m12 * ez;
   const double mez = m02 * ex + m12 * ey + m22 * ez;
   return ex * mex + ey * mey + ez * mez;
+}
+
+// The robust kernel of one term (include/ngicp.h, "robust kernel"), the only definition: s = e^T M e -> rho(s) and w(s) = d rho / d s.
+// kind is wave-uniform (an argument of the launch); c2 = c * c.  A term with !(s > 0) passes through as under NONE.  An inlier weight
+// is exactly 1.0 and its rho exactly s, so that scaling M by it changes no bit.
+__device__ __forceinline__ void robust_term(const int kind, const double c, const double c2, const double s, double& rho, double& w) {
+  rho = s;
+  w = 1.0;
+  if (!(s > 0.0)) return;
+  if (kind == NGICP_ROBUST_HUBER) {
+    if (!(s <= c2)) {
+      const double r = sqrt(s);
+      rho = 2.0 * c * r - c2;
+      w = c / r;
+    }
+  } else if (kind == NGICP_ROBUST_CAUCHY) {
+    const double u = s / c2;
+    rho = c2 * log1p(u);
+    w = 1.0 / (1.0 + u);
+  } else if (kind == NGICP_ROBUST_GEMAN_MCCLURE) {
+    const double q = c2 / (c2 + s);
+    rho = s * q;
+    w = q * q;
+  }
+}
+
+// K3 of one term under a robust kernel: s in err_term's order, M scaled by w, lin_terms, and the y0 slot takes rho instead of w s.
+// M itself (what the pass stores) stays unweighted.
+__device__ __forceinline__ void lin_terms_robust(double (&acc)[kNumSums], const int kind, const double c, const double c2, const double tax, const double tay, const double taz,
+                                                 const double ex, const double ey, const double ez, const double (&M)[6]) {
+  double rho, w;
+  robust_term(kind, c, c2, err_term(ex, ey, ez, M), rho, w);
+  double Mw[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) Mw[e] = w * M[e];
+  const double y0 = acc[27];
+  lin_terms(acc, tax, tay, taz, ex, ey, ez, Mw);
+  acc[27] = y0 + rho;
+}
+
+// the error leg of one term under a robust kernel: rho(e^T M e)
+__device__ __forceinline__ double err_term_robust(const int kind, const double c, const double c2, const double ex, const double ey, const double ez, const double* M) {
+  double rho, w;
+  robust_term(kind, c, c2, err_term(ex, ey, ez, M), rho, w);
+  return rho;
 }
 
 struct LmConfig {
@@ -271,6 +317,9 @@ struct PassArgs {
   int max_passes;
   int* gen;      // zero before the launch: passes released so far (agent scope), kGenLines copies in cache lines of their own
   SolveArgs sa;
+  // robust kernel (robust_term): read by the ROBUST instantiations of k_gicp_pass only, which the host launches exactly when kind != NONE
+  int robust_kind;
+  double robust_c, robust_c2;
 };
 
 // --- cooperative exact 1-NN ------------------------------------------------------------------
@@ -1118,7 +1167,7 @@ constexpr int kStampStride = 24;
     if (a.dbg_stamps && lane == 0) a.dbg_stamps[(size_t)(blockIdx.x * 4 + wave) * kStampStride + (k)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
 
-template <int G, int WPS = NGICP_PASS_WAVES, bool FUSED = false>
+template <int G, int WPS = NGICP_PASS_WAVES, bool FUSED = false, bool ROBUST = false>
 __global__ void __launch_bounds__(256, WPS) k_gicp_pass(PassArgs a) {
   constexpr int B = 64 / G;  // queries per wave batch
   // Walk windows (see scan_global_outward), measured with the packed points: the default build, whose launches are as long as their
@@ -1185,7 +1234,9 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass(PassArgs a) {
   if (a.dbg_span && threadIdx.x == 0) a.dbg_span[(size_t)blockIdx.x * 4] = __builtin_amdgcn_s_memrealtime();  // (the 100 MHz counter: the same on every CU)
   if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
 #define NG_HAVE_LIN have_lin_now
+#define NG_ROBUST ROBUST
 #include "ngicp_pass_group.inc"
+#undef NG_ROBUST
 #undef NG_HAVE_LIN
   if constexpr (FUSED) {
   // ---- the solver in the tail of the launch (R0's final sum, impl/nano_gicp_impl.hpp:260-267, and LsqRegistration's step,

@@ -4,7 +4,12 @@
 // reference changed the register allocation of the launch-per-pass kernels: 131 -> 155 VGPRs, 27 spilled in the 4-waves build).
 // Expects in scope: a (PassArgs, or the same seen through the constant address space), g (Grid), group, lane, wave, sub, grp, S, lds,
 // do_err, do_lin, R, t, Tf, tpt_old / tpt_new, mahal_old / mahal_new, wave_total, ncand, nvalid, nstaged, t_start, the constants B, kWin,
-// kSideStep, FUSED, the macros NG_STAMP and NG_HAVE_LIN.
+// kSideStep, FUSED, the macros NG_STAMP and NG_HAVE_LIN.  NG_ROBUST (a constant expression; false where the includer defines none): the
+// K4 leg and the K3 tail weight their term by the robust kernel in a.robust_kind / robust_c / robust_c2 (robust_term, ngicp_pass.h).
+#ifndef NG_ROBUST
+#define NG_ROBUST false
+#define NG_ROBUST_DEFAULTED
+#endif
   for (int item = group * 4 + wave; item < a.n_batches; item = a.n_batches) {
     // (the batch table is written when the index is built, never by a pass: through the constant address space, a scalar load where the
     // wave's number is in a scalar register)
@@ -118,11 +123,15 @@
         const double tay = R[3] * ax + R[4] * ay + R[5] * az + t[1];
         const double taz = R[6] * ax + R[7] * ay + R[8] * az + t[2];
         const double ex = (double)bp_old.x - tax, ey = (double)bp_old.y - tay, ez = (double)bp_old.z - taz;
+        if constexpr (NG_ROBUST) {
+          k4 = err_term_robust(a.robust_kind, a.robust_c, a.robust_c2, ex, ey, ez, Mold);
+        } else {
         const double m00 = Mold[0], m01 = Mold[1], m02 = Mold[2], m11 = Mold[3], m12 = Mold[4], m22 = Mold[5];
         const double mex = m00 * ex + m01 * ey + m02 * ez;
         const double mey = m01 * ex + m11 * ey + m12 * ez;
         const double mez = m02 * ex + m12 * ey + m22 * ez;
         k4 = ex * mex + ey * mey + ez * mez;
+        }
       }
     }
 
@@ -482,7 +491,8 @@
 
           // K3: residual, Jacobian, normal equations (impl/nano_gicp_impl.hpp:232-257)
           const double ex = (double)bp.x - tax, ey = (double)bp.y - tay, ez = (double)bp.z - taz;
-          lin_terms(acc, tax, tay, taz, ex, ey, ez, M);
+          if constexpr (NG_ROBUST) lin_terms_robust(acc, a.robust_kind, a.robust_c, a.robust_c2, tax, tay, taz, ex, ey, ez, M);
+          else lin_terms(acc, tax, tay, taz, ex, ey, ez, M);
         }
       }
     }
@@ -545,3 +555,7 @@
     if (FUSED) __hip_atomic_store(a.grp_cost + group, cost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else a.grp_cost[group] = cost;
   }
+#ifdef NG_ROBUST_DEFAULTED
+#undef NG_ROBUST
+#undef NG_ROBUST_DEFAULTED
+#endif

@@ -266,6 +266,9 @@ struct VoxelPassArgs {
   unsigned long long* t_first;  // device word: stamped by the first pass of an alignment (block 0), or null
   int nbr;                  // slots per source point (1, 7 or 27); k_vgicp_pass reads neither this nor slot_stride
   int slot_stride;          // k_vgicp_pass_n: corr / mahal are slot-major, slot s of point i at [s * slot_stride + i]
+  // robust kernel (robust_term, ngicp_pass.h): read by the ROBUST instantiations only, which the host launches exactly when kind != NONE
+  int robust_kind;
+  double robust_c, robust_c2;
 };
 
 // The shared-memory arrays of a voxelized pass block (K = 1 has no `vs`).
@@ -317,7 +320,7 @@ __device__ __forceinline__ void voxel_block_row(const double (&acc)[kNumSums], c
 // single kernel and k_vgicp_pass_batch<1> (ngicp_voxel_batch.h) both inline it: the same per-point statements, the same reduction, the
 // same row - a lane of the batch comes out bit for bit as the single alignment.  A: VoxelPassArgs (the kernel's argument) or the same
 // record seen through the constant address space (KernelVoxelPassArgs: a lane's record in device memory, read with scalar loads).
-template <class A>
+template <bool ROBUST = false, class A>
 __device__ __forceinline__ void vgicp_pass_body(A& a, const PassPose& p, VoxelPassLds& sh) {
   const double (&R)[9] = p.R;
   const double (&t)[3] = p.t;
@@ -343,7 +346,8 @@ __device__ __forceinline__ void vgicp_pass_body(A& a, const PassPose& p, VoxelPa
       const int v_old = a.corr[cur][i];
       if ((unsigned int)v_old < (unsigned int)a.n_vox) {  // (-1: none)
         const double* mv = a.rec + (size_t)v_old * kVoxRec;
-        acc[28] += err_term(mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + (size_t)i * 6);
+        if constexpr (ROBUST) acc[28] += err_term_robust(a.robust_kind, a.robust_c, a.robust_c2, mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + (size_t)i * 6);
+        else acc[28] += err_term(mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + (size_t)i * 6);
       }
     }
     if (do_lin) {
@@ -370,7 +374,8 @@ __device__ __forceinline__ void vgicp_pass_body(A& a, const PassPose& p, VoxelPa
 #pragma unroll
         for (int e = 0; e < 6; ++e) Mo[e] = M[e];
         // residual, Jacobian, normal equations: the exact pass's K3 with mean_v for the target point and n_v M for M
-        lin_terms(acc, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
+        if constexpr (ROBUST) lin_terms_robust(acc, a.robust_kind, a.robust_c, a.robust_c2, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
+        else lin_terms(acc, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
       }
     }
   }
@@ -390,11 +395,12 @@ __device__ __forceinline__ bool voxel_pass_begin(const VoxelPassArgs& a, PassPos
   return true;
 }
 
+template <bool ROBUST = false>
 __global__ void __launch_bounds__(kVoxBlock) k_vgicp_pass(VoxelPassArgs a) {
   __shared__ VoxelPassLds sh;
   PassPose p;
   if (!voxel_pass_begin(a, p)) return;
-  vgicp_pass_body(a, p, sh);
+  vgicp_pass_body<ROBUST>(a, p, sh);
 }
 
 // voxel numbers (and float squared distances to (float)mean_v at the pose of the linearisation) back in ORIGINAL source order
@@ -436,7 +442,7 @@ struct VoxelPassLdsN : VoxelPassLds {
 
 // vgicp_pass_body for the neighbourhoods: one block of one DIRECT7 / DIRECT27 pass from the pose on, inlined into k_vgicp_pass_n<K> and
 // k_vgicp_pass_batch<K>.
-template <int K, class A>
+template <int K, bool ROBUST = false, class A>
 __device__ __forceinline__ void vgicp_pass_n_body(A& a, const PassPose& p, VoxelPassLdsN<K>& sh) {
   const double (&R)[9] = p.R;
   const double (&t)[3] = p.t;
@@ -469,7 +475,8 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const PassPose& p, Voxel
       for (int s = 0; s < K; ++s) {
         if ((unsigned int)vo[s] < (unsigned int)a.n_vox) {  // (-1: none)
           const double* mv = a.rec + (size_t)vo[s] * kVoxRec;
-          acc[28] += err_term(mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + ((size_t)s * stride + i) * 6);
+          if constexpr (ROBUST) acc[28] += err_term_robust(a.robust_kind, a.robust_c, a.robust_c2, mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + ((size_t)s * stride + i) * 6);
+          else acc[28] += err_term(mv[0] - tax, mv[1] - tay, mv[2] - taz, a.mahal[cur] + ((size_t)s * stride + i) * 6);
         }
       }
     }
@@ -529,7 +536,8 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const PassPose& p, Voxel
           double* Mo = a.mahal[nxt] + ((size_t)s * stride + i) * 6;
 #pragma unroll
           for (int e = 0; e < 6; ++e) Mo[e] = M[e];
-          lin_terms(acc, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
+          if constexpr (ROBUST) lin_terms_robust(acc, a.robust_kind, a.robust_c, a.robust_c2, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
+          else lin_terms(acc, tax, tay, taz, bx - tax, by - tay, bz - taz, M);
         }
       }
     }
@@ -537,12 +545,12 @@ __device__ __forceinline__ void vgicp_pass_n_body(A& a, const PassPose& p, Voxel
   voxel_block_row(acc, nprobes, nvalid, sh, a.partials);
 }
 
-template <int K>
+template <int K, bool ROBUST = false>
 __global__ void __launch_bounds__(kVoxBlock, 2) k_vgicp_pass_n(VoxelPassArgs a) {
   __shared__ VoxelPassLdsN<K> sh;
   PassPose p;
   if (!voxel_pass_begin(a, p)) return;
-  vgicp_pass_n_body<K>(a, p, sh);
+  vgicp_pass_n_body<K, ROBUST>(a, p, sh);
 }
 
 // the K voxel numbers of every source point, slot-major in sorted order -> row-major [n][K] in ORIGINAL source order

@@ -48,6 +48,13 @@ class NeighborSearchMethod(enum.IntEnum):  # voxelized GICP: voxels a source poi
     DIRECT27 = 27
 
 
+class RobustKernel(enum.IntEnum):  # robust kernel on every term (include/ngicp.h NGICP_ROBUST_*)
+    NONE = 0
+    HUBER = 1
+    CAUCHY = 2
+    GEMAN_MCCLURE = 3
+
+
 class NgicpError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"ngicp error {code}: {msg}")
@@ -91,6 +98,7 @@ EXPORTS = [
     "ngicp_set_voxel_submap_merge", "ngicp_get_voxel_submap_merge", "ngicp_voxelmap_merge_stats", "ngicp_keyframe_voxelmap_get",
     "ngicp_set_voxel_rolling", "ngicp_get_voxel_rolling", "ngicp_voxel_rolling_insert", "ngicp_voxel_rolling_evict", "ngicp_voxel_rolling_clear",
     "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
+    "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -195,6 +203,9 @@ def load_library() -> C.CDLL:
     L.ngicp_voxel_rolling_clear.argtypes = [vp]
     L.ngicp_voxel_rolling_get.argtypes = [vp, c_szp, c_i32p, c_f64p, c_f64p, c_i32p, c_i64p]
     L.ngicp_voxel_rolling_stats.argtypes = [vp, c_i64p, c_szp, c_szp, c_szp, c_f64p, c_f64p]
+    L.ngicp_set_robust_kernel.argtypes = [vp, C.c_int, C.c_double]
+    L.ngicp_get_robust_kernel.argtypes = [vp, c_i32p, c_f64p]
+    L.ngicp_robust_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, C.c_size_t, c_i32p]
     _lib = L
     return L
 
@@ -399,6 +410,30 @@ class NanoGICP:
         ti, te = C.c_double(0), C.c_double(0)
         self._ck(self._L.ngicp_voxel_rolling_stats(self._h, C.byref(ins), C.byref(nv), C.byref(cap), C.byref(sl), C.byref(ti), C.byref(te)))
         return dict(inserts=ins.value, n_vox=nv.value, capacity_vox=cap.value, table_slots=sl.value, last_insert_ms=ti.value, last_evict_ms=te.value)
+
+    def setRobustKernel(self, kind, width: float = 1.0):
+        """A robust kernel on every term of the cost (include/ngicp.h "robust kernel"): HUBER, CAUCHY or GEMAN_MCCLURE of the given width
+        on s = e^T M e, or NONE (the default).  It holds for align, linearize and compute_error on every route (exact, DIRECT1 / 7 / 27,
+        rolling map) and is remembered across mode switches; alignBatch, alignBatchVoxel and the sharded entries raise while it is set."""
+        self._ck(self._L.ngicp_set_robust_kernel(self._h, int(kind), float(width)))
+
+    def getRobustKernel(self):
+        """-> (RobustKernel, width)"""
+        k = C.c_int(0); w = C.c_double(0)
+        self._ck(self._L.ngicp_get_robust_kernel(self._h, C.byref(k), C.byref(w)))
+        return RobustKernel(k.value), w.value
+
+    def robust_terms(self, T=None):
+        """-> (s, w), each (n, K) float64 in original source order: per term s = e^T M e at the pose T (None: the final transformation)
+        under the correspondences and matrices of the last linearisation, and the weight the kernel gives it.  K is 1 on the exact route,
+        else the neighbourhood's.  No correspondence: s = -1, w = 0."""
+        t = _colmajor16(self.final_transformation_ if T is None else T, np.float64)
+        n = self._src.shape[0]
+        K = int(self.getNeighborSearchMethod()) if self.getVoxelResolution() > 0.0 else 1
+        s = np.empty((n, K)); w = np.empty((n, K)); k = C.c_int(0)
+        self._ck(self._L.ngicp_robust_terms(self._h, _p(t, c_f64p), _p(s, c_f64p), _p(w, c_f64p), s.size, C.byref(k)))
+        assert k.value == K
+        return s, w
 
     def setTuning(self, voxel_size: float = 0.0, lanes_per_query: int = 0):
         self._ck(self._L.ngicp_set_tuning(self._h, float(voxel_size), int(lanes_per_query)))

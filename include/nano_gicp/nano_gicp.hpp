@@ -95,6 +95,7 @@ struct SpaciousnessFilter {
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };  // gicp/gicp_settings.hpp:47
 enum class LSQ_OPTIMIZER_TYPE { GaussNewton, LevenbergMarquardt };                         // lsq_registration.hpp:54
 enum class NeighborSearchMethod { DIRECT1 = 1, DIRECT7 = 7, DIRECT27 = 27 };                // voxelized GICP (ngicp.h NGICP_VOX_*); no counterpart in the reference
+enum class RobustKernel { NONE = 0, HUBER = 1, CAUCHY = 2, GEMAN_MCCLURE = 3 };                // robust kernel on every term (ngicp.h NGICP_ROBUST_*); no counterpart in the reference
 
 template <typename PointSource, typename PointTarget>
 class NanoGICP {
@@ -399,6 +400,39 @@ class NanoGICP {
     int K = 0;
     if (!check(ngicp_voxel_correspondences(h_, out.data(), out.size(), &K), "voxelCorrespondences")) out.clear();
     return out;
+  }
+  // A robust kernel on every term of the cost (include/ngicp.h "robust kernel"): Huber, Cauchy or Geman-McClure of the given width on
+  // s = e^T M e; NONE (the default) is the plain cost.  It holds for align() on every route - exact, voxelized with any neighbourhood,
+  // rolling map - and is remembered across mode switches; alignBatch / alignBatchVoxel are not available while it is set.  A bad kind
+  // or width is reported and changes nothing.
+  void setRobustKernel(RobustKernel kind, double width = 1.0) {
+    if (h_) check(ngicp_set_robust_kernel(h_, static_cast<int>(kind), width), "setRobustKernel");
+  }
+  RobustKernel getRobustKernel(double* width = nullptr) const {
+    int k = NGICP_ROBUST_NONE;
+    double w = 1.0;
+    if (h_) check(ngicp_get_robust_kernel(h_, &k, &w), "getRobustKernel");
+    if (width) *width = w;
+    return static_cast<RobustKernel>(k);
+  }
+  // Per term, at the pose T under the correspondences and matrices of the last linearisation: s = e^T M e and the weight the kernel
+  // gives it, row-major n x K in the source's order (K = 1 for exact GICP, else getNeighborSearchMethod()'s value); s = -1, w = 0 where
+  // a slot has no correspondence.  What the kernel down-weighted - e.g. to keep a moving object out of insertIntoVoxelMap.  False (and
+  // both empty) on error.
+  bool robustTerms(const types::Matrix4d& T, std::vector<double>& s, std::vector<double>& w) {
+    s.clear();
+    w.clear();
+    if (!h_ || !input_) return false;
+    const size_t K = voxel_resolution_ > 0.0 ? static_cast<size_t>(getNeighborSearchMethod()) : 1;
+    s.resize(input_->size() * K);
+    w.resize(s.size());
+    int k_out = 0;
+    if (!check(ngicp_robust_terms(h_, T.data(), s.data(), w.data(), s.size(), &k_out), "robustTerms")) {
+      s.clear();
+      w.clear();
+      return false;
+    }
+    return true;
   }
   // setVoxelSubmapMerge(true): the voxel map of a submap assembled by setSubmapKeyframes is merged from per-keyframe voxel sums, which
   // every keyframe carries and which are built once per keyframe and resolution, instead of being summed over all points of the submap

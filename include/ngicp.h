@@ -329,6 +329,52 @@ int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vo
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
 
+/* --- robust kernel: Huber, Cauchy or Geman-McClure on every term (no counterpart in the reference; csrc/ngicp_pass.h robust_term,
+ *     DESIGN.md 4.13) -----------------------------------------------------------------------------------------------------------------
+ * The kernels and their names are this project's own definition; no fidelity to another library is claimed.
+ * A TERM is one (source point, correspondence) pair: the exact route and DIRECT1 have one per source point, DIRECT7 / DIRECT27 up to K.
+ * For a term, s = e^T M e, where M is the matrix the pass computes and stores - (C_B + R C_A R^T)^-1, times n_v in the voxelized mode -
+ * in the order of operations of the passes' error leg.  With the width c > 0 (finite) and c2 = c * c:
+ *
+ *   kind                             rho(s)                                        w(s) = d rho / d s
+ *   NGICP_ROBUST_NONE           0    s                                             1
+ *   NGICP_ROBUST_HUBER          1    s if s <= c2, else 2 c sqrt(s) - c2           1 if s <= c2, else c / sqrt(s)
+ *   NGICP_ROBUST_CAUCHY         2    c2 log1p(s / c2)                              1 / (1 + s / c2)
+ *   NGICP_ROBUST_GEMAN_MCCLURE  3    s q, with q = c2 / (c2 + s)                   q q
+ *
+ * A term with !(s > 0) (M need not be positive definite: covariances are the caller's) is taken as under NONE: rho = s, w = 1.
+ * A linearisation adds w J^T M J to H, w J^T M e to b and rho to the error; a trial (ngicp_compute_error, the error leg of a pass) adds
+ * rho(s), with s from the trial pose and the STORED matrices of the last linearisation.  The stored matrices stay the unweighted M;
+ * the correspondence search, the distance gate, the covariances, the LM / Gauss-Newton schedule and the convergence test are what they
+ * were.  The final Hessian is the weighted H.  A term whose weight is exactly 1 contributes the same bits as under NONE.
+ *
+ * What the width means: s is a squared Mahalanobis distance.  With PLANE covariances M has eigenvalues of about 500 across the plane
+ * and 0.5 within it, so on the exact route c = 1 is roughly 4.5 cm off the plane (1 / sqrt(500)) or 1.4 m along it.  In the voxelized
+ * mode s carries the voxel's point count n_v: the same residual against a voxel of 25 points is 25 times the s, i.e. a width reaches a
+ * fifth as far; widths there are chosen larger, or in view of the typical n_v at the resolution in use.
+ *
+ * ngicp_set_robust_kernel: an unknown kind, or with kind != NONE a width that is not finite and positive, is NGICP_ERR_ARG and changes
+ * nothing.  (With NONE the width is ignored and the remembered one stays.)  The setting is remembered across mode switches (exact /
+ * voxelized, neighbourhood, rolling map) and takes effect at the next ngicp_align / ngicp_linearize / ngicp_compute_error; the state of
+ * the hooks stays valid, since the stored correspondences and matrices do not depend on it.
+ * While kind != NONE these return NGICP_ERR_ARG (the message names the robust kernel): ngicp_align_batch, ngicp_voxel_align_batch,
+ * ngicp_sharded_begin / _pass / _step / _finish, and an exact-route ngicp_align under the kernel-variant switches NGICP_PASS_IMPL=1,
+ * NGICP_FUSED, NGICP_QUEUE, NGICP_PERSIST or NGICP_HEAD (the hooks under NGICP_PASS_IMPL=1): those pass variants have no robust
+ * instantiation.  The voxelized align obeys none of the switches and is not refused.
+ *
+ * ngicp_robust_terms: for the pose T (column-major 4x4 doubles), per term, s and w under the correspondences and matrices of the last
+ * linearisation - ngicp_compute_error's contract term by term - as n_src x K doubles each, row i for source point i in ORIGINAL order
+ * (K = 1 on the exact route; slot order as ngicp_voxel_correspondences).  Where the slot has no correspondence, s = -1 and w = 0.  With
+ * NONE every w is 1.  *K_out (may be NULL) is K; capacity_doubles < n_src * K is NGICP_ERR_ARG (K_out is set first).  Valid when
+ * ngicp_get_correspondences is.  The sum of rho(s) over the terms is ngicp_compute_error(T) up to the order of the additions. */
+#define NGICP_ROBUST_NONE 0
+#define NGICP_ROBUST_HUBER 1
+#define NGICP_ROBUST_CAUCHY 2
+#define NGICP_ROBUST_GEMAN_MCCLURE 3
+int ngicp_set_robust_kernel(ngicp_t* h, int kind, double width);
+int ngicp_get_robust_kernel(const ngicp_t* h, int* kind, double* width);
+int ngicp_robust_terms(ngicp_t* h, const double T_colmajor[16], double* s_out, double* w_out, size_t capacity_doubles, int* K_out);
+
 /* --- more than one initial guess on the same source / target pair (no counterpart in the reference) ------------------------------
  * ngicp_align_batch: n_guesses alignments on this handle at once.  They share the source, the target, both indices, both covariance
  * sets and every parameter; each has its own initial guess.  One kernel launch per pass serves every guess still running, one solver
