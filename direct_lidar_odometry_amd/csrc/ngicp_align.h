@@ -44,6 +44,11 @@ void fill_robust(const ngicp* h, int& kind, double& c, double& c2) {
   c2 = h->robust_width * h->robust_width;
 }
 
+int queue_switch() {  // NGICP_QUEUE=1 (experiment, round 3): a grid of resident blocks that draw their groups from a counter (k_gicp_queue)
+  static const int queue_env = std::getenv("NGICP_QUEUE") ? std::atoi(std::getenv("NGICP_QUEUE")) : 0;
+  return queue_env;
+}
+
 void launch_pass(ngicp* h, const PassArgs& a, int nblocks, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
   // 32-query batches, 2 lanes per query.  Two builds of the kernel: 3 waves per SIMD (129 VGPRs), and 4 (128 VGPRs, two spilled
   // dwords, 4 blocks per CU) for grids of more than two rounds of blocks, where the launch is bound by how many blocks pass through
@@ -64,9 +69,7 @@ void launch_pass(ngicp* h, const PassArgs& a, int nblocks, hipStream_t s, hipEve
       hipExtLaunchKernelGGL((k_gicp_pass_st<3>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, b);
     return;
   }
-  // NGICP_QUEUE=1 (experiment, round 3): a grid of resident blocks that draw their groups from a counter (k_gicp_queue)
-  static const int queue_env = std::getenv("NGICP_QUEUE") ? std::atoi(std::getenv("NGICP_QUEUE")) : 0;
-  if (queue_env && !a.fused && !(a.mode & 4) && !a.dbg_stamps && !a.dbg_span && !a.dbg_qstats) {
+  if (queue_switch() && !a.fused && !(a.mode & 4) && !a.dbg_stamps && !a.dbg_span && !a.dbg_qstats) {
     if (four)
       hipExtLaunchKernelGGL((k_gicp_queue<2, 4>), dim3((unsigned)std::min(nblocks, h->queue_slots[1])), dim3(256), 0, s, start, stop, 0, a);
     else
@@ -219,6 +222,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
   s.order_valid = order_flag[h->order_sel];
   s.t_first = nullptr;
   s.persist = 0;
+  s.pass_honours_word = 0;
   s.pass_ticks = nullptr;
   s.st_out = nullptr;
   s.nrows = 0;
@@ -301,8 +305,10 @@ void publish_alignment(ngicp* h, const LmState& st, float loop_ms, float* aligne
   s.passes = st.hot.passes;
   s.outer_iterations = st.hot.nr_iterations + 1;
   s.lm_trials = st.hot.n_trace;
-  s.mean_candidates = st.hot.passes > 0 ? st.hot.cand_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
-  s.valid_fraction = st.hot.passes > 0 ? st.hot.valid_total / ((double)st.hot.passes * (double)h->src.dev->n) : 0.0;
+  s.search_passes = st.hot.search_passes;
+  // (means over the passes that searched: a K4-only pass tests no candidate and gates nothing in)
+  s.mean_candidates = st.hot.search_passes > 0 ? st.hot.cand_total / ((double)st.hot.search_passes * (double)h->src.dev->n) : 0.0;
+  s.valid_fraction = st.hot.search_passes > 0 ? st.hot.valid_total / ((double)st.hot.search_passes * (double)h->src.dev->n) : 0.0;
   s.pass_ms_total = 0.0;
   s.passes_timed = 0;
 }
@@ -416,6 +422,15 @@ void end_alignment(ngicp* h, Alignment& al, float* aligned, size_t out_stride, b
 void set_pass_mode(const ngicp* h, PassArgs& a) {
   a.mode = (h->p.optimizer == NGICP_OPT_GAUSS_NEWTON) ? 2 : 3;
   if (h->prev_staged_fraction < 0.0 || h->prev_staged_fraction >= 0.12) a.mode |= 32;
+}
+
+// The pass kernel launch_pass picks on the launch-per-pass route honours LmHot::lin_unneeded: k_gicp_pass in its default, 4-waves, robust and
+// fused builds does; k_gicp_pass_st (NGICP_PASS_IMPL=1) and k_gicp_queue keep full passes, and NGICP_FULL_LAST_PASS=1 asks for them.
+// Sets the pass's mode bit and tells the solver, so that search_passes counts what ran and a K4-only pass leaves the launch order alone.
+void honour_lin_unneeded(const ngicp* h, LoopCtx& c) {
+  if (h->full_last_pass || pass_impl() != 0 || queue_switch()) return;
+  c.pa.mode |= 64;
+  c.sa.pass_honours_word = 1;
 }
 
 // NGICP_ORDER=xcd (experiment): instead of the cost-sorted launch order, a FIXED order that hands every XCD (blocks b, b + 8, ...
@@ -660,6 +675,8 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
   if (!(h->order_src == h->src.dev.get() && h->order_groups == c.sa.nblocks)) HIP_TRY(hipMemsetAsync(h->order_flag.p, 0, 4 * sizeof(int), h->stream));  // (both flags)
   const bool xcd_order = install_xcd_order(h, c);
   set_pass_mode(h, c.pa);
+  static const bool persist_one = std::getenv("NGICP_PERSIST_ONE") != nullptr;
+  if (!h->persist && !h->head && !persist_one) honour_lin_unneeded(h, c);  // (k_gicp_persist and k_gicp_head keep full passes)
   if (const char* dbg = std::getenv("NGICP_DEBUG_MODE")) c.pa.mode |= (std::atoi(dbg) & (8 | 16));  // timing experiments only
   begin_alignment(h, al, guess, c.sa, c.pa.t_first);
   const DebugDumps dbg = debug_begin(h, c);
@@ -679,7 +696,6 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
   const bool want_persist = h->persist && plain && h->persist_slots > 0 && !dbg.stamp_path && max_p + 1 <= kMaxPersistPasses;
   const bool persist_done = want_persist && align_persistent(h, c, al, max_p);
   const bool head_mode = h->head && plain && !persist_done && c.nblocks <= 2 * h->pass_slots;  // (grids of more rounds: the head's few microseconds are paid once per round)
-  static const bool persist_one = std::getenv("NGICP_PERSIST_ONE") != nullptr;
   if (persist_done) {
     // (one launch has run the whole alignment)
   } else if (head_mode) {
@@ -702,8 +718,8 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
   ngicp_stats& s = h->stats;
   h->order_src = h->src.dev.get();  // (what the order flag on the device, if set, refers to)
   h->order_groups = c.sa.nblocks;
-  s.staged_fraction = al.st.hot.passes > 0 ? al.st.hot.staged_total / ((double)al.st.hot.passes * (double)h->src.dev->n) : 0.0;
-  if (al.st.hot.passes > 1) h->prev_staged_fraction = s.staged_fraction;
+  s.staged_fraction = al.st.hot.search_passes > 0 ? al.st.hot.staged_total / ((double)al.st.hot.search_passes * (double)h->src.dev->n) : 0.0;
+  if (al.st.hot.search_passes > 1) h->prev_staged_fraction = s.staged_fraction;  // (the first pass lists for every batch or for none: it says nothing)
   if (persist_done && h->profiling) sum_tick_pass_times(h, al.st.hot);
 }
 

@@ -640,6 +640,7 @@ int ngicp_create(int device, ngicp_t** out) {
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_ticks), 2 * kMaxTickPasses * sizeof(unsigned long long), hipHostMallocDefault));
     if (const char* s = std::getenv("NGICP_PERSIST")) h->persist = std::atoi(s);
     if (const char* s = std::getenv("NGICP_HEAD")) h->head = std::atoi(s);
+    if (const char* s = std::getenv("NGICP_FULL_LAST_PASS")) h->full_last_pass = std::atoi(s);
     if (const char* s = std::getenv("NGICP_CELL_BOXES")) h->cell_boxes = std::atoi(s);
     if (const char* s = std::getenv("NGICP_TARGET_OCC")) h->target_occupancy = std::max(1.0, std::atof(s));
     if (const char* s = std::getenv("NGICP_VOXEL")) h->voxel_size = std::atof(s);
@@ -1482,6 +1483,7 @@ int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
     LoopCtx& c = *h->shard_ctx;
     prepare_loop(h, c);
     set_pass_mode(h, c.pa);
+    honour_lin_unneeded(h, c);  // (every rank steps the same lm_step on the same reduced sums: the word is the same on all of them)
     upload_initial_state(h, guess ? guess : kIdentity16);
     HIP_TRY(hipStreamSynchronize(h->stream));  // once per alignment: the caller may step on a stream of its own
     for (int i = 0; i < kShardSlots; ++i) h->h_shard_done[i] = 0;
@@ -1550,6 +1552,9 @@ int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_it
     HIP_TRY(hipStreamSynchronize(s));
     store_result(h->pin_state[1].hot, h->final_T, &h->converged, &h->nr_iterations, h->final_hessian);
     copy_results_out(h, T_out, converged, nr_iterations, final_hessian);
+    h->stats.passes = h->pin_state[1].hot.passes;  // (the stepped alignment's counts; the other fields stay the last ngicp_align's)
+    h->stats.search_passes = h->pin_state[1].hot.search_passes;
+    h->stats.lm_trials = h->pin_state[1].hot.n_trace;
     h->sharded_active = false;
     h->shard_ctx.reset();
     h->shard_stream = nullptr;

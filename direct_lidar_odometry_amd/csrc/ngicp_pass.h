@@ -162,6 +162,8 @@ struct LmHot {
   double final_H[36];  // H of the last accepted step, row-major (final_hessian_, impl/lsq_registration_impl.hpp:155,203); identity until then
   unsigned long long t_first, t_done;  // 100 MHz counter at the start of the alignment's first pass / when the solver set `done`
   float lin_f[12];  // float pose (rows of [R|t]) the CURRENT correspondences were searched with: xi_f of the pass that was adopted last
+  int lin_unneeded;    // the linearisation at xi can never be adopted, whatever the pass of xi finds (set_lin_unneeded): K4's sum is all the solver reads
+  int search_passes;   // passes that searched and linearised: `passes` less the K4-only ones
 };
 // What a pass needs of the state, as 64 dwords (256 bytes, two cache lines of their own).  The persistent kernel reads the view of pass p
 // from entry p of a RING of views that begins at LmState::view and continues behind the state (the solver that ends pass p - 1 stores
@@ -263,6 +265,8 @@ struct SolveArgs {
   int nrows;               // rows of `partials` (0: nblocks, one per group).  k_gicp_head: 32 rows, already added up per subset by the pass's blocks
   int persist;             // the solver runs between two passes of ONE launch: every word other blocks (on other XCDs) wrote or will read
                            // goes through agent-scope loads / write-through stores, and the launch order it builds is for the NEXT alignment
+  int pass_honours_word;   // the pass kernel of this route skips search and linearisation when LmHot::lin_unneeded says so (PassArgs::mode bit 6):
+                           // such a pass counts in `passes` but not in `search_passes`, and its costs do not refresh the launch order
   unsigned long long* pass_ticks;  // persist: [2 * max passes] 100 MHz ticks {last block arrived, next pass released} per pass, or null
 };
 
@@ -292,7 +296,8 @@ struct PassArgs {
                             // are the outer rings of the batch region listed (a wrong guess costs time, not exactness)
   LmState* st;
   double* partials;         // [n_groups][kNumSlots], group-major: a block stores its 32 sums as one 256-byte row
-  int mode;                 // bit0: error part, bit1: linearise part, bit2: ignore st->done (test hooks), bit5: the first pass lists region rows
+  int mode;                 // bit0: error part, bit1: linearise part, bit2: ignore st->done (test hooks), bit5: the first pass lists region rows,
+                            // bit6: honour LmHot::lin_unneeded (k_gicp_pass: K4 alone where the linearisation can never be adopted)
   int stage_grow;           // rings around the batch box that the LDS row list covers (0: no list, search unindexed)
   unsigned long long* dbg_stamps;  // diagnostic only: [wave][kStampStride] s_memtime stamps + counters, or null
   int4* dbg_qstats;                // diagnostic only: per query {ring-1 candidates, ring-1 walks | far walks << 16, far + shell candidates, flags}, or null
@@ -692,6 +697,17 @@ __device__ __forceinline__ void make_trial(LmHot& L, double lambda_add) {
   pose_mul(L.delta, L.x0, L.xi);
 }
 
+// The trial just made (LM) can only END the alignment or be tried again from the SAME linearisation, so the linearisation its pass would
+// produce at xi can never be adopted:
+//   1. its step already satisfies the convergence test: accepted, lm_step sets `converged` and `done` without adopt_new
+//      (impl/lsq_registration_impl.hpp:110,118-127); rejected, lm_advance ends the alignment too (:191-194);
+//   2. it is the trial of the last outer iteration (iter + 1 >= max_iterations): accepted means done (:101-102); rejected means another
+//      trial from the unchanged H, b (for which this holds again) or "lm not converged" (:105-108,207).
+// Both are known here, one pass ahead.  A pass kernel that honours the word (PassArgs::mode bit 6) then evaluates K4 alone.
+__device__ __forceinline__ void set_lin_unneeded(LmHot& L, const LmConfig& cfg) {
+  L.lin_unneeded = (is_converged_dev(L.delta, cfg.rot_eps, cfg.trans_eps) || L.iter + 1 >= cfg.max_iterations) ? 1 : 0;
+}
+
 // new linearisation (reduced sums in LDS) becomes current
 __device__ __forceinline__ void adopt_new(LmHot& L, const double* sums) {
 #pragma unroll
@@ -753,6 +769,7 @@ __device__ __forceinline__ bool lm_advance(LmHot& L, const LmConfig& cfg, const 
       return false;
     }
     make_trial(L, L.lambda);
+    set_lin_unneeded(L, cfg);
     return false;
   }
 
@@ -786,6 +803,7 @@ __device__ __forceinline__ bool lm_advance(LmHot& L, const LmConfig& cfg, const 
       return false;
     }
     make_trial(L, L.lambda);
+    set_lin_unneeded(L, cfg);
     return false;
   }
   // accepted (:201-204); final_hessian_ = H is written by the caller BEFORE the state is advanced
@@ -794,8 +812,10 @@ __device__ __forceinline__ bool lm_advance(LmHot& L, const LmConfig& cfg, const 
 
 // One step of the optimiser's state machine with the sums of a finished pass (the serial lane of the solver; k_gicp_head's blocks run it
 // redundantly, each for itself): lm_advance, and on an accepted trial the bookkeeping of LsqRegistration::align's outer loop.
-__device__ __forceinline__ void lm_step(LmHot& L, const LmConfig& cfg, const double* sums, double* trace, int max_trace_rows) {
+// searched: the pass that produced `sums` searched and linearised (false: K4 alone, a route that honours LmHot::lin_unneeded).
+__device__ __forceinline__ void lm_step(LmHot& L, const LmConfig& cfg, const double* sums, double* trace, int max_trace_rows, const bool searched = true) {
   const bool gn = cfg.optimizer == 0;
+  L.search_passes += searched ? 1 : 0;
   const bool accepted = lm_advance(L, cfg, sums, trace, max_trace_rows);
   if (accepted) {
 #pragma unroll
@@ -820,6 +840,7 @@ __device__ __forceinline__ void lm_step(LmHot& L, const LmConfig& cfg, const dou
         L.nu = 2.0;
         L.trial = 0;
         make_trial(L, L.lambda);
+        set_lin_unneeded(L, cfg);
       }
     }
   }
@@ -892,7 +913,9 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
   // (persistent: the blocks keep their groups for the whole alignment; the order built from the costs of the third pass - warm starts in
   // place - goes to the buffer the NEXT alignment launches with)
   const int passes_at_entry = PERSIST ? __hip_atomic_load(&st->hot.passes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : st->hot.passes;
-  const bool order_it = a.mode == 0 && a.grp_order && a.nblocks <= kMaxOrderGroups && (PERSIST ? passes_at_entry == 2 : (!AGENT || passes_at_entry < 3 || (passes_at_entry & 3) == 3));
+  // (a K4-only pass stores no costs: the order built from the last pass that searched stays, for this alignment's next pass and the next alignment's first)
+  const int k4_only_at_entry = (!PERSIST && a.pass_honours_word) ? st->hot.lin_unneeded : 0;
+  const bool order_it = a.mode == 0 && a.grp_order && a.nblocks <= kMaxOrderGroups && !k4_only_at_entry && (PERSIST ? passes_at_entry == 2 : (!AGENT || passes_at_entry < 3 || (passes_at_entry & 3) == 3));
   int hv[kHotPerThread];
 #pragma unroll
   for (int k = 0; k < kHotPerThread; ++k) {
@@ -1088,7 +1111,7 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
     } else {
       const LmConfig& cfg = a.cfg;
       NG_SSTAMP(3);
-      lm_step(L, cfg, sums, a.trace, a.max_trace_rows);
+      lm_step(L, cfg, sums, a.trace, a.max_trace_rows, !(a.pass_honours_word && L.lin_unneeded));
       NG_SSTAMP(4);
       NG_SSTAMP(5);
       if (!L.done) {
@@ -1195,6 +1218,7 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass(PassArgs a) {
   typedef const int __attribute__((address_space(4))) * ConstIntPtr;
   const int done_now = st->hot.done, have_lin_now = st->hot.have_lin;
   const int cur = st->hot.cur, nxt = cur ^ 1;
+  const int lin_unneeded_now = st->hot.lin_unneeded;
   const int order_is_valid = *(ConstIntPtr)(unsigned long long)a.order_valid;             // (both pointers are set for every launch: prepare_loop)
   const int order_entry = ((ConstIntPtr)(unsigned long long)a.grp_order)[blockIdx.x];    // (read whether valid or not: the buffer exists)
   // trial pose (FP64) and its float cast
@@ -1207,7 +1231,7 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass(PassArgs a) {
 #pragma unroll
   for (int i = 0; i < 12; ++i) Tf[i] = st->xi_f[i];
   // (all of the above is in flight before the first of it is looked at)
-  asm volatile("" ::"s"(done_now), "s"(have_lin_now), "s"(cur), "s"(order_is_valid), "s"(order_entry), "s"(Tf[0]), "s"(Tf[11]), "s"(R[0]), "s"(t[2]));
+  asm volatile("" ::"s"(done_now), "s"(have_lin_now), "s"(cur), "s"(lin_unneeded_now), "s"(order_is_valid), "s"(order_entry), "s"(Tf[0]), "s"(Tf[11]), "s"(R[0]), "s"(t[2]));
   if (!(a.mode & 4) && done_now) return;
 
   const bool do_err = (a.mode & 1) && have_lin_now;
@@ -1233,11 +1257,77 @@ __global__ void __launch_bounds__(256, WPS) k_gicp_pass(PassArgs a) {
   const unsigned long long t_start = a.grp_cost ? __builtin_amdgcn_s_memtime() : 0ull;
   if (a.dbg_span && threadIdx.x == 0) a.dbg_span[(size_t)blockIdx.x * 4] = __builtin_amdgcn_s_memrealtime();  // (the 100 MHz counter: the same on every CU)
   if (a.t_first && blockIdx.x == 0 && threadIdx.x == 0 && !have_lin_now) *a.t_first = __builtin_amdgcn_s_memrealtime();
+  if ((a.mode & 64) && lin_unneeded_now) {  // block-uniform
+    // ---- K4 ALONE: the linearisation at this pose can never be adopted (set_lin_unneeded), so the solver reads slot 28 and nothing
+    //      else.  A path of its own, taken before the search's state exists: the working pass pays one scalar load and this branch
+    //      (folded into the group body's do_lin, the word stayed alive through the search and cost the SGPR-bound kernel 0.5 us per
+    //      pass in spilled scalars).  tpt_new, mahal_new, batch_far and the group's cost stay as the last searching pass left them; the
+    //      row is what the group body stores with do_lin off, bit for bit: K4's term as there, lanes 0..31 added in lane order
+    //      starting from 0.0, the four waves as ((w0 + w1) + w2) + w3, every other slot +0.0. ----
+    const int item = group * 4 + wave;
+    double term = 0.0;  // the tail's acc[28] of this lane's query
+    if (item < a.n_batches) {
+      typedef const int __attribute__((address_space(4))) * ConstBatchPtr;
+      ConstBatchPtr brec = (ConstBatchPtr)(unsigned long long)a.batches + 2 * (size_t)item;
+      const int qbase = brec[0], qcount = brec[1];
+      if (lane < qcount) {
+        const int i = qbase + lane;
+        const float4 sp = a.qpts[i];
+        float4 bp_old = make_float4(0.f, 0.f, 0.f, 0.f);
+        int j_old = -1;
+        double Mold[6] = {0, 0, 0, 0, 0, 0};
+        if (have_lin_now) {
+          bp_old = tpt_old[i];
+          j_old = __float_as_int(bp_old.w);
+        }
+        if (do_err) {
+          const double* M = mahal_old + (size_t)i * 6;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) Mold[e] = M[e];
+        }
+        double k4 = 0.0;
+        if (do_err && j_old >= 0) {  // impl/nano_gicp_impl.hpp:273-296
+          const double ax = (double)sp.x, ay = (double)sp.y, az = (double)sp.z;
+          const double tax = R[0] * ax + R[1] * ay + R[2] * az + t[0];
+          const double tay = R[3] * ax + R[4] * ay + R[5] * az + t[1];
+          const double taz = R[6] * ax + R[7] * ay + R[8] * az + t[2];
+          const double ex = (double)bp_old.x - tax, ey = (double)bp_old.y - tay, ez = (double)bp_old.z - taz;
+          if constexpr (ROBUST) k4 = err_term_robust(a.robust_kind, a.robust_c, a.robust_c2, ex, ey, ez, Mold);
+          else k4 = err_term(ex, ey, ez, Mold);
+        }
+        term += k4;
+      }
+    }
+    double* red = S.red;
+    if (lane < 32) red[lane] = term;
+    wave_lds_sync();
+    if (lane < kNumSlots) {
+      double out = 0.0;
+      if (lane == 28)
+        for (int l = 0; l < 32; ++l) out += red[l];
+      wave_total += out;
+      lds[wave][lane] = lane == 28 ? wave_total : 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < kNumSlots) {
+      const int v = threadIdx.x;
+      const double val = ((lds[0][v] + lds[1][v]) + lds[2][v]) + lds[3][v];
+      if (FUSED) __hip_atomic_store(a.partials + (size_t)group * kNumSlots + v, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else a.partials[(size_t)group * kNumSlots + v] = val;
+    }
+    if (a.dbg_span && threadIdx.x == 0) {
+      unsigned long long* d = a.dbg_span + (size_t)blockIdx.x * 4;
+      d[1] = __builtin_amdgcn_s_memrealtime();
+      d[3] = (unsigned long long)(unsigned int)group;
+    }
+    if constexpr (!FUSED) return;  // (no join with the working path: nothing of this one is alive in it)
+  } else {
 #define NG_HAVE_LIN have_lin_now
 #define NG_ROBUST ROBUST
 #include "ngicp_pass_group.inc"
 #undef NG_ROBUST
 #undef NG_HAVE_LIN
+  }
   if constexpr (FUSED) {
   // ---- the solver in the tail of the launch (R0's final sum, impl/nano_gicp_impl.hpp:260-267, and LsqRegistration's step,
   //      impl/lsq_registration_impl.hpp:161-208).  Every store of this block that another block will read was made by wave 0 as a

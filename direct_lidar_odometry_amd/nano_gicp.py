@@ -67,7 +67,7 @@ class Stats(C.Structure):
                 ("index_build_ms", C.c_double), ("covariance_ms", C.c_double), ("upload_ms", C.c_double), ("voxel_size", C.c_double),
                 ("grid_dims", C.c_int * 3), ("lanes_per_query", C.c_int), ("passes_timed", C.c_int), ("n_src", C.c_longlong), ("n_tgt", C.c_longlong), ("staged_fraction", C.c_double), ("submap_ms", C.c_double),
                 ("device_allocs", C.c_longlong), ("host_wait_spins", C.c_longlong), ("query_ms", C.c_double),
-                ("voxelmap_ms", C.c_double)]
+                ("voxelmap_ms", C.c_double), ("search_passes", C.c_int)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}

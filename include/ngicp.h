@@ -433,11 +433,11 @@ typedef struct ngicp_stats {
   double loop_ms;           /* device time (HIP events on the handle's stream) of the iteration loop */
   double pass_ms_total;     /* device time (HIP events on the handle's stream) summed over the k_gicp_pass launches of the
                                last align that did work; only collected while ngicp_set_profiling(h, 1) */
-  int passes;               /* per-iteration kernels launched that did work (= linearisations incl. the speculative last one) */
+  int passes;               /* per-iteration kernels launched that did work (= lm_trials + 1 under LM; see search_passes) */
   int outer_iterations;     /* nr_iterations_ + 1 */
   int lm_trials;            /* LM trials evaluated */
-  double mean_candidates;   /* C-bar: target points distance-tested per source point per pass */
-  double valid_fraction;    /* fraction of source points with a correspondence in the last pass */
+  double mean_candidates;   /* C-bar: target points distance-tested per source point per pass that searched */
+  double valid_fraction;    /* fraction of source points with a correspondence, mean over the passes that searched */
   double index_build_ms;    /* device time of the last index build on this handle */
   double covariance_ms;     /* device time of the last covariance computation */
   double upload_ms;         /* host wall time of the last cloud upload */
@@ -446,13 +446,17 @@ typedef struct ngicp_stats {
   int lanes_per_query;
   int passes_timed;         /* launches covered by pass_ms_total */
   long long n_src, n_tgt;   /* cloud sizes of the last align */
-  double staged_fraction;   /* fraction of queries served through the LDS row index of their batch region */
+  double staged_fraction;   /* fraction of queries served through the LDS row index of their batch region (mean over the passes that searched) */
   double submap_ms;         /* host wall time of the last ngicp_submap_set() that rebuilt the target (enqueue + index build) */
   long long device_allocs;  /* hipMalloc calls made by this process's engine buffers so far (a call that grows a buffer in the middle of
                                a frame shows up as a latency outlier: two readings around a call attribute it) */
   long long host_wait_spins; /* polls of the solver's progress word during the last ngicp_align() (busy or yielding, see below) */
   double query_ms;          /* device time (HIP events on the handle's stream) of the kernels of the last knn / radius / fitness / range query */
   double voxelmap_ms;       /* device time of the last voxel-map build (voxelized GICP) */
+  int search_passes;        /* passes that searched and linearised.  < passes where the route's pass kernel evaluates only the trial's
+                               error in a pass whose linearisation could never be adopted (the trial can only end the alignment:
+                               its step already meets the convergence test, or it belongs to the last outer iteration); the
+                               denominator of mean_candidates, valid_fraction and staged_fraction */
 } ngicp_stats;
 int ngicp_get_stats(ngicp_t* h, ngicp_stats* out);
 /* HIP-event timing of the k_gicp_pass launches inside align (two event records per timed launch; off by default).
