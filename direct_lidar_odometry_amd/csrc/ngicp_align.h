@@ -223,6 +223,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
   s.t_first = nullptr;
   s.persist = 0;
   s.pass_honours_word = 0;
+  s.serial_step = h->serial_step;
   s.pass_ticks = nullptr;
   s.st_out = nullptr;
   s.nrows = 0;
@@ -707,9 +708,15 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
   } else if (persist_one && h->persist_slots > 0 && max_p + 1 <= kMaxPersistPasses) {
     feed_alignment(h, al, max_p, [&](long i, hipEvent_t start, hipEvent_t stop) { launch_persist_one(h, c, i, start, stop); });
   } else {
-    feed_alignment(h, al, max_p, [&](long, hipEvent_t start, hipEvent_t stop) {
+    // (diagnostic only) NGICP_DEBUG_SOLVE=N, N > 1: the stamps of the solver launch behind pass N - one that makes a trial, where the
+    // last launch of an alignment only ends it; 1: of the last working launch
+    static const long stamp_launch = std::getenv("NGICP_DEBUG_SOLVE") ? std::atol(std::getenv("NGICP_DEBUG_SOLVE")) : 0;
+    feed_alignment(h, al, max_p, [&](long i, hipEvent_t start, hipEvent_t stop) {
       launch_pass(h, c.pa, c.nblocks, h->stream, start, stop);
-      if (!c.pa.fused) hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, c.sa);
+      if (c.pa.fused) return;
+      SolveArgs sa = c.sa;
+      if (stamp_launch > 1 && i + 1 != stamp_launch) sa.dbg_stamps = nullptr;
+      hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, sa);
     });
   }
   HIP_TRY(hipGetLastError());

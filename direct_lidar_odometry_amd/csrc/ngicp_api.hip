@@ -641,6 +641,7 @@ int ngicp_create(int device, ngicp_t** out) {
     if (const char* s = std::getenv("NGICP_PERSIST")) h->persist = std::atoi(s);
     if (const char* s = std::getenv("NGICP_HEAD")) h->head = std::atoi(s);
     if (const char* s = std::getenv("NGICP_FULL_LAST_PASS")) h->full_last_pass = std::atoi(s);
+    if (const char* s = std::getenv("NGICP_SERIAL_STEP")) h->serial_step = std::atoi(s) != 0 ? 1 : 0;
     if (const char* s = std::getenv("NGICP_CELL_BOXES")) h->cell_boxes = std::atoi(s);
     if (const char* s = std::getenv("NGICP_TARGET_OCC")) h->target_occupancy = std::max(1.0, std::atof(s));
     if (const char* s = std::getenv("NGICP_VOXEL")) h->voxel_size = std::atof(s);
@@ -1842,6 +1843,26 @@ int ngicp_math_selftest(ngicp_t* h, int which, const double* in, size_t n_proble
     HIP_TRY(hipMemcpyAsync(di.p, in, n_problems * kIn[which] * sizeof(double), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_math_selftest, dim3((unsigned)((n_problems + 63) / 64)), dim3(64), 0, h->stream, which, di.as<double>(), (int)n_problems, dout.as<double>());
     HIP_TRY(hipMemcpyAsync(out, dout.p, n_problems * kOut[which] * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+  });
+}
+
+// ---- test hook: one optimiser step, serial and wave form (k_step_selftest) ----
+int ngicp_step_selftest(ngicp_t* h, const double* in, size_t n_problems, unsigned char* out_or_null, size_t* record_bytes) {
+  return guarded(h, [&] {
+    if (record_bytes) *record_bytes = kStepSelftestRecord;
+    if (!out_or_null) return;
+    if (!in || n_problems > (size_t)1 << 20) throw ArgError{NGICP_ERR_ARG, "bad arguments"};
+    if (n_problems == 0) return;
+    DevBuf di, dout;
+    const size_t in_bytes = n_problems * kStepSelftestIn * sizeof(double), out_bytes = n_problems * 2 * kStepSelftestRecord;
+    di.ensure(in_bytes);
+    dout.ensure(out_bytes);
+    HIP_TRY(hipMemcpyAsync(di.p, in, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(dout.p, 0, out_bytes, h->stream));
+    hipLaunchKernelGGL(k_step_selftest, dim3((unsigned)n_problems), dim3(64), 0, h->stream, di.as<double>(), (int)n_problems, dout.as<unsigned char>());
+    HIP_TRY(hipMemcpyAsync(out_or_null, dout.p, out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipGetLastError());
   });

@@ -309,6 +309,8 @@ struct ngicp {
   int head = 0;          // env NGICP_HEAD=1: k_gicp_head - no solver launch, every block steps the optimiser at its head
   int full_last_pass = 0;  // env NGICP_FULL_LAST_PASS=1 (diagnostic): every pass searches and linearises, also where LmHot::lin_unneeded says the
                            // result can never be adopted; changes no result
+  int serial_step = 0;   // env NGICP_SERIAL_STEP=1 (A/B timing, tests): the solver steps on one lane (lm_step) instead of on the wave
+                         // (lm_step_wave); changes no result
   DevBuf state_alt;      // k_gicp_head: the second state buffer (a launch's solver block writes the one its blocks are not reading)
   DevBuf head_ws;        // k_gicp_head: {done flag (64 B), subset tickets (128 B), subset rows of even / odd launches (2 x 8 KB)}
   unsigned long long* pin_ticks = nullptr;  // pinned [2 * kMaxTickPasses]: per pass {last block arrived, next pass released} (profiling)

@@ -22,13 +22,23 @@ NG_HD void pose_identity(Pose& p) {
   p.t[0] = p.t[1] = p.t[2] = 0.0;
 }
 
+// The element expressions of pose_mul and ldlt6_solve, ONE definition each: the serial routines below and the solver's wave-level step
+// (lm_step_wave, ngicp_pass.h: one element per lane) both take them from here, so that operand order and the compiler's contraction
+// decisions cannot differ between the two.
+NG_HD double pose_mul_r(double a0, double a1, double a2, double b0, double b1, double b2) { return a0 * b0 + a1 * b1 + a2 * b2; }
+NG_HD double pose_mul_t(double a0, double a1, double a2, double b0, double b1, double b2, double t) { return a0 * b0 + a1 * b1 + a2 * b2 + t; }
+NG_HD double ldlt_scale(double a_ik, double dk) { return a_ik / dk; }
+NG_HD double ldlt_update(double a_ij, double a_ik, double dk, double a_jk) { return a_ij - a_ik * dk * a_jk; }
+NG_HD double ldlt_subst(double y_i, double a, double y_j) { return y_i - a * y_j; }
+NG_HD double ldlt_diag(double y_i, double a_ii) { return (fabs(a_ii) > 2.2250738585072014e-308) ? y_i / a_ii : 0.0; }
+
 // c = a * b  (delta * x0, impl/lsq_registration_impl.hpp:154,179)
 NG_HD void pose_mul(const Pose& a, const Pose& b, Pose& c) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) c.R[i * 3 + j] = a.R[i * 3 + 0] * b.R[0 * 3 + j] + a.R[i * 3 + 1] * b.R[1 * 3 + j] + a.R[i * 3 + 2] * b.R[2 * 3 + j];
-    c.t[i] = a.R[i * 3 + 0] * b.t[0] + a.R[i * 3 + 1] * b.t[1] + a.R[i * 3 + 2] * b.t[2] + a.t[i];
+    for (int j = 0; j < 3; ++j) c.R[i * 3 + j] = pose_mul_r(a.R[i * 3 + 0], a.R[i * 3 + 1], a.R[i * 3 + 2], b.R[0 * 3 + j], b.R[1 * 3 + j], b.R[2 * 3 + j]);
+    c.t[i] = pose_mul_t(a.R[i * 3 + 0], a.R[i * 3 + 1], a.R[i * 3 + 2], b.t[0], b.t[1], b.t[2], a.t[i]);
   }
 }
 
@@ -173,12 +183,12 @@ __host__ __device__ inline void ldlt6_solve(double A[36], const double rhs[6], d
     const double dk = A[k * 6 + k];
     if (dk != 0.0 && isfinite(dk)) {
 #pragma unroll
-      for (int i = k + 1; i < 6; ++i) A[i * 6 + k] /= dk;
+      for (int i = k + 1; i < 6; ++i) A[i * 6 + k] = ldlt_scale(A[i * 6 + k], dk);
 #pragma unroll
       for (int i = k + 1; i < 6; ++i)
 #pragma unroll
         for (int j = k + 1; j <= i; ++j) {
-          A[i * 6 + j] -= A[i * 6 + k] * dk * A[j * 6 + k];
+          A[i * 6 + j] = ldlt_update(A[i * 6 + j], A[i * 6 + k], dk, A[j * 6 + k]);
           A[j * 6 + i] = A[i * 6 + j];
         }
     }
@@ -194,14 +204,13 @@ __host__ __device__ inline void ldlt6_solve(double A[36], const double rhs[6], d
 #pragma unroll
   for (int i = 0; i < 6; ++i)
 #pragma unroll
-    for (int j = 0; j < i; ++j) y[i] -= A[i * 6 + j] * y[j];
-  const double tol = 2.2250738585072014e-308;
+    for (int j = 0; j < i; ++j) y[i] = ldlt_subst(y[i], A[i * 6 + j], y[j]);
 #pragma unroll
-  for (int i = 0; i < 6; ++i) y[i] = (fabs(A[i * 6 + i]) > tol) ? y[i] / A[i * 6 + i] : 0.0;
+  for (int i = 0; i < 6; ++i) y[i] = ldlt_diag(y[i], A[i * 6 + i]);
 #pragma unroll
   for (int i = 5; i >= 0; --i)
 #pragma unroll
-    for (int j = i + 1; j < 6; ++j) y[i] -= A[j * 6 + i] * y[j];
+    for (int j = i + 1; j < 6; ++j) y[i] = ldlt_subst(y[i], A[j * 6 + i], y[j]);
 #pragma unroll
   for (int k = 5; k >= 0; --k)
 #pragma unroll

@@ -267,8 +267,12 @@ struct SolveArgs {
                            // goes through agent-scope loads / write-through stores, and the launch order it builds is for the NEXT alignment
   int pass_honours_word;   // the pass kernel of this route skips search and linearisation when LmHot::lin_unneeded says so (PassArgs::mode bit 6):
                            // such a pass counts in `passes` but not in `search_passes`, and its costs do not refresh the launch order
+  int serial_step;         // env NGICP_SERIAL_STEP=1: lane 0 of wave 0 runs lm_step (the reference form) instead of the wave running lm_step_wave
+                           // (fills the padding in front of the next pointer: the size of the struct, and of PassArgs, does not change)
   unsigned long long* pass_ticks;  // persist: [2 * max passes] 100 MHz ticks {last block arrived, next pass released} per pass, or null
 };
+
+static_assert(offsetof(SolveArgs, pass_ticks) == offsetof(SolveArgs, pass_honours_word) + 8, "serial_step takes no room of its own");
 
 struct PassArgs {
   const float4* qpts;       // source points in Morton-tile query order, w = sorted source position
@@ -678,6 +682,25 @@ __device__ __forceinline__ bool is_converged_dev(const Pose& d, double rot_eps, 
   return fmax(rmax, tmax) < 1;
 }
 
+// The scalar expressions of the LM step, ONE definition each for the serial step (lm_step) and the wave-level one (lm_step_wave):
+// the denominator of the gain ratio (impl/lsq_registration_impl.hpp:196), |d|^2 of the trace row, lambda after an accepted trial (:202).
+__device__ __forceinline__ double lm_gain_den(const double* d, const double* b, const double lambda) {
+  double den = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) den += d[i] * (lambda * d[i] - b[i]);
+  return den;
+}
+__device__ __forceinline__ double lm_step_norm2(const double* d) {
+  double dn = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) dn += d[i] * d[i];
+  return dn;
+}
+__device__ __forceinline__ double lm_lambda_accepted(const double lambda, const double rho) {
+  const double q = 2 * rho - 1;
+  return lambda * fmax(1.0 / 3.0, 1 - q * q * q);
+}
+
 // d = (H + lambda I)^-1 (-b); delta = (so3_exp(d[0:3]), d[3:6]); xi = delta * x0
 __device__ __forceinline__ void make_trial(LmHot& L, double lambda_add) {
   double A[36], rhs[6];
@@ -773,12 +796,7 @@ __device__ __forceinline__ bool lm_advance(LmHot& L, const LmConfig& cfg, const 
     return false;
   }
 
-  double den = 0.0, dn = 0.0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    den += L.d[i] * (L.lambda * L.d[i] - L.b[i]);
-    dn += L.d[i] * L.d[i];
-  }
+  const double den = lm_gain_den(L.d, L.b, L.lambda), dn = lm_step_norm2(L.d);
   const double rho = (L.y0 - yi) / den;
   const bool rejected = rho < 0;  // NaN is accepted, as upstream
   if (trace && L.n_trace < max_trace_rows) {
@@ -822,13 +840,9 @@ __device__ __forceinline__ void lm_step(LmHot& L, const LmConfig& cfg, const dou
     for (int i = 0; i < 36; ++i) L.final_H[i] = L.H[i];
     if (!gn) {
       // LM accept: x0 = xi, lambda update, convergence, next outer iteration (impl/lsq_registration_impl.hpp:201-204,110)
-      double den = 0.0;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) den += L.d[i] * (L.lambda * L.d[i] - L.b[i]);
-      const double rho = (L.y0 - sums[28]) / den;
+      const double rho = (L.y0 - sums[28]) / lm_gain_den(L.d, L.b, L.lambda);
       L.x0 = L.xi;
-      const double q = 2 * rho - 1;
-      L.lambda = L.lambda * fmax(1.0 / 3.0, 1 - q * q * q);
+      L.lambda = lm_lambda_accepted(L.lambda, rho);
       L.converged = is_converged_dev(L.delta, cfg.rot_eps, cfg.trans_eps) ? 1 : 0;
       L.iter += 1;
       if (L.converged || L.iter >= cfg.max_iterations) {
@@ -845,6 +859,256 @@ __device__ __forceinline__ void lm_step(LmHot& L, const LmConfig& cfg, const dou
     }
   }
   if (gn && !L.done) L.xi = L.x0;  // GN: the next pass linearises at the updated estimate
+}
+
+// ---- the same step on a whole wave (lm_step_wave) --------------------------------------------------------------------------------
+// Every lane of ONE wave calls these with the same arguments; L and sums lie in LDS.  Whatever has at most 36 independent elements
+// runs one element per lane (the factorisation, the division by the pivots, pose_mul, the copies and the float casts); what is a short
+// dependent chain (the gain ratio, the substitutions, so3_exp, the convergence test) is computed by every lane on values all lanes
+// agree on.  Decisions are taken from such values only, so control flow is wave-uniform.  The element expressions are lm_step's own
+// (ngicp_math.h, lm_gain_den ...): the two forms agree bit for bit (ngicp_step_selftest).
+__device__ __forceinline__ void wave_sync() {  // LDS written by some lanes of the wave is read by others
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ double wave_lane_f64(const double v, const int src_lane) {  // src_lane: a compile-time constant
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src_lane), __builtin_amdgcn_readlane(__double2loint(v), src_lane));
+}
+__device__ __forceinline__ double wave_fetch_f64(const double v, const int src_lane) {  // per-lane source
+  return __hiloint2double(__builtin_amdgcn_ds_bpermute(src_lane << 2, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v)));
+}
+__device__ __forceinline__ bool wave_agree(const bool b) { return __builtin_amdgcn_readfirstlane(b ? 1 : 0) != 0; }
+// where element e of a Pose (R row-major, then t) sits in a float pose (rows of [R|t])
+__device__ __forceinline__ int pose_elem_to_rows(const int e) { return e < 9 ? (e / 3) * 4 + e % 3 : (e - 9) * 4 + 3; }
+
+__device__ __forceinline__ void adopt_new_wave(LmHot& L, const double* sums, const int lane) {
+  if (lane < 36) {
+    const int i = lane / 6, j = lane - 6 * i;
+    L.H[lane] = sums[tri21(min(i, j), max(i, j))];
+  }
+  if (lane < 6) L.b[lane] = sums[21 + lane];
+  if (lane < 12) L.lin_f[pose_elem_to_rows(lane)] = (float)reinterpret_cast<const double*>(&L.xi)[lane];
+  if (lane == 0) {
+    L.y0 = sums[27];
+    L.cur ^= 1;
+    L.have_lin = 1;
+  }
+}
+
+// make_trial and, when `lin_word`, set_lin_unneeded (iter: the value L.iter has by then)
+__device__ __forceinline__ void make_trial_wave(LmHot& L, const LmConfig& cfg, const double lambda_add, const bool lin_word, const int iter, const int lane) {
+  wave_sync();
+  const bool act = lane < 36;
+  const int i = act ? lane / 6 : 0, j = act ? lane - 6 * i : 0;
+  const int r = max(i, j), c = min(i, j);
+  double a = act ? L.H[lane] : 0.0;
+  if (act && i == j) a += lambda_add;
+  double y[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) y[e] = -L.b[e];
+  // pose_mul's right-hand operand for this lane's output: column (lane % 3) of x0.R, or x0.t
+  const bool out_t = lane >= 9;
+  const int orow = lane < 12 ? (out_t ? lane - 9 : lane / 3) : 0, ocol = lane < 9 ? lane % 3 : 0;
+  double xb[3];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) xb[m] = out_t ? L.x0.t[m] : L.x0.R[m * 3 + ocol];
+  // ---- ldlt6_solve's factorisation, element (i, j) on lane 6 i + j ----
+  int piv[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    int p = k;
+    double best = fabs(wave_lane_f64(a, 7 * k));
+#pragma unroll
+    for (int q = k + 1; q < 6; ++q) {
+      const double v = fabs(wave_lane_f64(a, 7 * q));
+      if (v > best) {
+        best = v;
+        p = q;
+      }
+    }
+    p = __builtin_amdgcn_readfirstlane(p);
+    piv[k] = p;
+    if (p != k) {  // rows k and p, then columns k and p: element (i, j) comes from (s(i), s(j)), s the transposition
+      const int si = i == k ? p : (i == p ? k : i), sj = j == k ? p : (j == p ? k : j);
+      a = wave_fetch_f64(a, si * 6 + sj);
+    }
+    if (k < 5) {
+      const double dk = wave_lane_f64(a, 7 * k);
+      if (dk != 0.0 && isfinite(dk)) {
+        const double scaled = ldlt_scale(a, dk);
+        if (act && j == k && i > k) a = scaled;
+        // (the serial form updates the lower triangle and mirrors it: lane (i, j) evaluates element (max, min))
+        const double upd = ldlt_update(wave_fetch_f64(a, r * 6 + c), wave_fetch_f64(a, r * 6 + k), dk, wave_fetch_f64(a, c * 6 + k));
+        if (act && i > k && j > k) a = upd;
+      }
+    }
+  }
+  // ---- the substitutions: every lane, on the factor's 21 entries as wave-uniform values; the six divisions on the diagonal's lanes ----
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+#pragma unroll
+    for (int q = k + 1; q < 6; ++q)
+      if (piv[k] == q) {
+        const double t = y[k];
+        y[k] = y[q];
+        y[q] = t;
+      }
+  double lo[15];
+#pragma unroll
+  for (int q = 1; q < 6; ++q)
+#pragma unroll
+    for (int e = 0; e < q; ++e) lo[q * (q - 1) / 2 + e] = wave_lane_f64(a, q * 6 + e);
+#pragma unroll
+  for (int q = 0; q < 6; ++q)
+#pragma unroll
+    for (int e = 0; e < q; ++e) y[q] = ldlt_subst(y[q], lo[q * (q - 1) / 2 + e], y[e]);
+  {
+    double mine = y[0];
+#pragma unroll
+    for (int q = 1; q < 6; ++q) mine = lane == 7 * q ? y[q] : mine;
+    const double dv = ldlt_diag(mine, a);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) y[q] = wave_lane_f64(dv, 7 * q);
+  }
+#pragma unroll
+  for (int q = 5; q >= 0; --q)
+#pragma unroll
+    for (int e = q + 1; e < 6; ++e) y[q] = ldlt_subst(y[q], lo[e * (e - 1) / 2 + q], y[e]);
+#pragma unroll
+  for (int k = 5; k >= 0; --k)
+#pragma unroll
+    for (int q = k + 1; q < 6; ++q)
+      if (piv[k] == q) {
+        const double t = y[k];
+        y[k] = y[q];
+        y[q] = t;
+      }
+  // ---- delta = (so3_exp(d[0:3]), d[3:6]) on every lane; xi = delta * x0, one output per lane ----
+  Pose delta;
+  so3_exp_matrix(y, delta.R);
+  delta.t[0] = y[3];
+  delta.t[1] = y[4];
+  delta.t[2] = y[5];
+  double ar[3];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) ar[m] = orow == 0 ? delta.R[m] : (orow == 1 ? delta.R[3 + m] : delta.R[6 + m]);
+  const double at = orow == 0 ? delta.t[0] : (orow == 1 ? delta.t[1] : delta.t[2]);
+  const double xr = pose_mul_r(ar[0], ar[1], ar[2], xb[0], xb[1], xb[2]), xt = pose_mul_t(ar[0], ar[1], ar[2], xb[0], xb[1], xb[2], at);
+  if (lane < 12) reinterpret_cast<double*>(&L.xi)[lane] = out_t ? xt : xr;
+  const bool conv = lin_word ? is_converged_dev(delta, cfg.rot_eps, cfg.trans_eps) : false;
+  if (lane == 0) {
+#pragma unroll
+    for (int e = 0; e < 6; ++e) L.d[e] = y[e];
+    L.delta = delta;
+    if (lin_word) L.lin_unneeded = (conv || iter + 1 >= cfg.max_iterations) ? 1 : 0;
+  }
+}
+
+// lm_step, executed by the 64 lanes of one wave.  The image L is complete (for any lane of this wave) after a wave_sync().
+__device__ __forceinline__ void lm_step_wave(LmHot& L, const LmConfig& cfg, const double* sums, double* trace, int max_trace_rows, const bool searched, const int lane) {
+  const double yi = sums[28];
+  int iter = L.iter;
+  double lambda = L.lambda;
+  const int have_lin = L.have_lin;
+  if (lane == 0) {
+    L.search_passes += searched ? 1 : 0;
+    L.passes += 1;
+    L.cand_total += sums[29];
+    L.valid_total += sums[30];
+    L.staged_total += sums[31];
+  }
+  // Every path that goes on makes ONE trial, at the end (make_trial_wave is the bulk of the code: one copy of it, not one per path).
+  const bool gn = cfg.optimizer == 0;
+  bool go_on = true;  // wave-uniform
+  if (gn) {
+    // ---- Gauss-Newton (lm_advance's first branch; the rest behind the trial) ----
+    adopt_new_wave(L, sums, lane);
+    lambda = 0.0;
+  } else if (!wave_agree(have_lin != 0)) {
+    // ---- Levenberg-Marquardt, first pass: linearisation at the initial guess ----
+    adopt_new_wave(L, sums, lane);
+    if (wave_agree(lambda < 0.0)) {
+      double m = 0.0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) m = fmax(m, fabs(sums[tri21(i, i)]));
+      lambda = cfg.lm_init_lambda_factor * m;
+    }
+    go_on = cfg.lm_max_iterations > 0;
+    if (lane == 0) {
+      L.nr_iterations = 0;
+      L.lambda = lambda;
+      L.nu = 2.0;
+      L.trial = 0;
+      if (!go_on) L.lm_failed = 1, L.done = 1;
+    }
+  } else {
+    double d[6], b[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) d[e] = L.d[e], b[e] = L.b[e];
+    const double y0 = L.y0, nu = L.nu;
+    const int trial = L.trial, n_trace = L.n_trace;
+    const double rho = (y0 - yi) / lm_gain_den(d, b, lambda);
+    const bool rejected = wave_agree(rho < 0);  // NaN is accepted, as upstream
+    if (trace && n_trace < max_trace_rows && lane == 0) {
+      double* row = trace + (size_t)n_trace * kTraceCols;
+      row[0] = iter; row[1] = trial; row[2] = y0; row[3] = yi;
+      row[4] = rho; row[5] = lambda; row[6] = sqrt(lm_step_norm2(d)); row[7] = rejected ? 0.0 : 1.0;
+      L.n_trace = n_trace + 1;
+    }
+    const bool conv = wave_agree(is_converged_dev(L.delta, cfg.rot_eps, cfg.trans_eps));  // (of the trial just evaluated: both branches ask)
+    if (rejected) {
+      const bool failed = !conv && trial + 1 >= cfg.lm_max_iterations;
+      go_on = !conv && !failed;
+      if (!conv) lambda = nu * lambda;
+      if (lane == 0) {
+        if (conv) {
+          L.converged = 1, L.done = 1;
+        } else {
+          L.lambda = lambda;
+          L.nu = 2 * nu;
+          L.trial = trial + 1;
+          if (failed) L.lm_failed = 1, L.converged = 0, L.done = 1;
+        }
+      }
+    } else {
+      // accepted: final_H = H, x0 = xi, lambda, convergence, next outer iteration
+      if (lane < 36) L.final_H[lane] = L.H[lane];
+      if (lane < 12) reinterpret_cast<double*>(&L.x0)[lane] = reinterpret_cast<const double*>(&L.xi)[lane];
+      lambda = lm_lambda_accepted(lambda, rho);
+      iter += 1;
+      go_on = !(conv || iter >= cfg.max_iterations);
+      if (lane == 0) {
+        L.lambda = lambda;
+        L.converged = conv ? 1 : 0;
+        L.iter = iter;
+        if (!go_on) L.done = 1;
+      }
+      if (go_on) {
+        adopt_new_wave(L, sums, lane);
+        if (lane == 0) {
+          L.nr_iterations = iter;
+          L.nu = 2.0;
+          L.trial = 0;
+        }
+      }
+    }
+  }
+  if (!wave_agree(go_on)) return;
+  make_trial_wave(L, cfg, lambda, !gn, iter, lane);
+  if (gn) {
+    // lm_advance's Gauss-Newton bookkeeping and lm_step's final_H (its `xi = x0` copies what x0 was just given)
+    wave_sync();
+    if (lane < 12) reinterpret_cast<double*>(&L.x0)[lane] = reinterpret_cast<const double*>(&L.xi)[lane];
+    if (lane < 36) L.final_H[lane] = L.H[lane];
+    const bool conv = wave_agree(is_converged_dev(L.delta, cfg.rot_eps, cfg.trans_eps));
+    if (lane == 0) {
+      L.nr_iterations = iter;
+      L.converged = conv ? 1 : 0;
+      L.iter = iter + 1;
+      if (conv || iter + 1 >= cfg.max_iterations) L.done = 1;
+    }
+  }
 }
 
 // The solver's block-shared scratch.  k_lm_solve owns one; the fused tail of k_gicp_pass lays it over the (then idle) search tables.
@@ -1105,7 +1369,19 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
     if (lane == 0) st->hot.y0 = sums[28];
     return;
   }
-  if (lane == 0) {
+  if (a.mode != 1 && !a.serial_step) {
+    // the step on the whole wave (lm_step_wave); the float pose of the next pass goes out as one store by twelve lanes
+    NG_SSTAMP(3);
+    lm_step_wave(L, a.cfg, sums, a.trace, a.max_trace_rows, !(a.pass_honours_word && L.lin_unneeded), lane);
+    NG_SSTAMP(4);
+    wave_sync();
+    NG_SSTAMP(5);
+    if (!L.done && lane < 12) {
+      const float f = (float)reinterpret_cast<const double*>(&L.xi)[lane];
+      if constexpr (PERSIST) __hip_atomic_store(&st->xi_f[pose_elem_to_rows(lane)], f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else sto->xi_f[pose_elem_to_rows(lane)] = f;
+    }
+  } else if (lane == 0) {
     if (a.mode == 1) {  // linearize hook
       adopt_new(L, sums);
     } else {
@@ -1183,6 +1459,65 @@ __global__ void __launch_bounds__(kSolveThreads) k_lm_solve(SolveArgs a) {
   __shared__ SolveShared<kSolveThreads> sh;
   lm_solve_body<kSolveThreads, false>(a, sh);
 }
+
+// Test hook: ONE optimiser step in both forms, lm_step on lane 0 and lm_step_wave on the wave, from the same state image, sums and
+// configuration; one block of one wave per problem.
+//   in  (kStepSelftestIn doubles): x0 12, xi 12, delta 12, H 36, b 6, y0, d 6, lambda, nu | iter, trial, have_lin, cur, n_trace,
+//       lin_unneeded | max_iterations, lm_max_iterations, optimizer, rot_eps, trans_eps, lm_init_lambda_factor | sums 32 | searched
+//   out (2 records of kStepSelftestRecord bytes, serial then wave; zeroed by the caller): the LmHot image, the trace row (8 doubles;
+//       written when n_trace == 0), d (6 doubles), {done, converged, lm_failed, trial} as doubles
+constexpr int kStepSelftestIn = 132;
+constexpr size_t kStepSelftestRecord = sizeof(LmHot) + 18 * sizeof(double);
+static_assert(sizeof(LmHot) % 8 == 0, "the trace row behind the image is 8-byte aligned");
+__global__ void __launch_bounds__(64) k_step_selftest(const double* __restrict__ in, int n_problems, unsigned char* __restrict__ out) {
+  __shared__ LmHot L;
+  __shared__ double sums[kPartialStride];
+  static_assert(kPartialStride >= 32, "32 reduced sums");
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x >= n_problems) return;
+  const double* p = in + (size_t)blockIdx.x * kStepSelftestIn;
+  LmConfig cfg;
+  cfg.max_iterations = (int)p[93];
+  cfg.lm_max_iterations = (int)p[94];
+  cfg.optimizer = (int)p[95];
+  cfg.rot_eps = p[96];
+  cfg.trans_eps = p[97];
+  cfg.lm_init_lambda_factor = p[98];
+  const bool searched = p[131] != 0.0;
+  for (int form = 0; form < 2; ++form) {
+    unsigned char* rec = out + ((size_t)blockIdx.x * 2 + form) * kStepSelftestRecord;
+    double* tail = reinterpret_cast<double*>(rec + sizeof(LmHot));
+    __syncthreads();
+    for (int w = lane; w < (int)(sizeof(LmHot) / 4); w += 64) reinterpret_cast<int*>(&L)[w] = 0;
+    if (lane < 32) sums[lane] = p[99 + lane];
+    __syncthreads();
+    if (lane < 36) reinterpret_cast<double*>(&L.x0)[lane] = p[lane];  // x0, xi, delta are contiguous
+    if (lane < 36) L.H[lane] = p[36 + lane];
+    if (lane < 6) L.b[lane] = p[72 + lane], L.d[lane] = p[79 + lane];
+    if (lane == 0) {
+      L.y0 = p[78];
+      L.lambda = p[85];
+      L.nu = p[86];
+      L.iter = (int)p[87];
+      L.trial = (int)p[88];
+      L.have_lin = (int)p[89];
+      L.cur = (int)p[90];
+      L.n_trace = max(0, (int)p[91]);
+      L.lin_unneeded = (int)p[92];
+    }
+    __syncthreads();
+    if (form == 0) {
+      if (lane == 0) lm_step(L, cfg, sums, tail, 1, searched);
+    } else {
+      lm_step_wave(L, cfg, sums, tail, 1, searched, lane);
+    }
+    __syncthreads();
+    for (int w = lane; w < (int)(sizeof(LmHot) / 4); w += 64) reinterpret_cast<int*>(rec)[w] = reinterpret_cast<const int*>(&L)[w];
+    if (lane < 6) tail[8 + lane] = L.d[lane];
+    if (lane == 0) tail[14] = L.done, tail[15] = L.converged, tail[16] = L.lm_failed, tail[17] = L.trial;
+  }
+}
+static_assert(offsetof(LmHot, xi) == offsetof(LmHot, x0) + sizeof(Pose) && offsetof(LmHot, delta) == offsetof(LmHot, xi) + sizeof(Pose), "x0, xi, delta are contiguous");
 
 constexpr int kStampStride = 24;
 #define NG_STAMP(k)                                                                                   \

@@ -88,7 +88,7 @@ EXPORTS = [
     "ngicp_keyframe_add", "ngicp_keyframe_add_transformed", "ngicp_keyframe_add_transformed_filtered", "ngicp_keyframe_count", "ngicp_keyframe_size", "ngicp_keyframe_clear",
     "ngicp_submap_set", "ngicp_get_target_points", "ngicp_transform_source", "ngicp_transform_cloud", "ngicp_measure_copy_bandwidth",
     "ngicp_preprocess_scan", "ngicp_set_source_preprocessed", "ngicp_map_add", "ngicp_map_voxel_filter", "ngicp_map_size", "ngicp_map_get",
-    "ngicp_map_clear", "ngicp_math_selftest", "ngicp_set_host_wait", "ngicp_covs_shard_begin", "ngicp_covs_shard_compute", "ngicp_covs_shard_commit",
+    "ngicp_map_clear", "ngicp_math_selftest", "ngicp_step_selftest", "ngicp_set_host_wait", "ngicp_covs_shard_begin", "ngicp_covs_shard_compute", "ngicp_covs_shard_commit",
     "ngicp_knn_search", "ngicp_radius_search", "ngicp_radius_fetch", "ngicp_fitness_score",
     "ngicp_align_batch", "ngicp_batch_get_lm_trace", "ngicp_fitness_score_batch",
     "ngicp_range_select", "ngicp_range_median",
@@ -184,6 +184,7 @@ def load_library() -> C.CDLL:
     L.ngicp_map_get.argtypes = [vp, c_f32p, C.c_size_t]
     L.ngicp_map_clear.argtypes = [vp]
     L.ngicp_math_selftest.argtypes = [vp, C.c_int, c_f64p, C.c_size_t, c_f64p]
+    L.ngicp_step_selftest.argtypes = [vp, c_f64p, C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(C.c_size_t)]
     L.ngicp_set_voxel_resolution.argtypes = [vp, C.c_double]
     L.ngicp_voxelmap_size.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.ngicp_voxelmap_get.argtypes = [vp, c_i32p, c_f64p, c_f64p, c_i32p]
@@ -800,6 +801,18 @@ class NanoGICP:
         a = np.ascontiguousarray(problems, dtype=np.float64)
         out = np.empty((a.shape[0], (9, 6, 12, 6)[which]))
         self._ck(self._L.ngicp_math_selftest(self._h, int(which), _p(a, c_f64p), a.shape[0], _p(out, c_f64p)))
+        return out
+
+    def stepSelftest(self, problems) -> np.ndarray:
+        """One optimiser step per row of `problems` (132 doubles, include/ngicp.h) in both forms -> uint8 [n][2][record]: the serial
+        step, then the wave-level one.  A record is the state image, then 18 doubles: trace row 8, d 6, done, converged, lm_failed, trial."""
+        a = np.ascontiguousarray(problems, dtype=np.float64)
+        assert a.ndim == 2 and a.shape[1] == 132
+        rec = C.c_size_t(0)
+        self._ck(self._L.ngicp_step_selftest(self._h, None, 0, None, C.byref(rec)))
+        out = np.zeros((a.shape[0], 2, rec.value), dtype=np.uint8)
+        if a.shape[0]:
+            self._ck(self._L.ngicp_step_selftest(self._h, _p(a, c_f64p), a.shape[0], _p(out, C.POINTER(C.c_ubyte)), C.byref(rec)))
         return out
 
     def measureCopyBandwidth(self, nbytes: int = 1 << 30, reps: int = 10) -> float:

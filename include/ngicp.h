@@ -426,6 +426,15 @@ int ngicp_fitness_score_batch(ngicp_t* h, size_t n, const float* T_n16_colmajor,
  * symmetric 3x3 eigen-decomposition that stands in for JacobiSVD (impl/nano_gicp_impl.hpp:332; in: {xx,xy,xz,yy,yz,zz}, out:
  * w 3 + V row-major 9), 3 the symmetric 3x3 inverse (impl/nano_gicp_impl.hpp:205-209; in 6, out 6). */
 int ngicp_math_selftest(ngicp_t* h, int which, const double* in, size_t n_problems, double* out);
+/* One step of the optimiser on the device in both of its forms (unit-test hook): the serial step on one lane and the wave-level step the
+ * solver runs by default (NGICP_SERIAL_STEP=1 selects the serial one), from the same state, sums and configuration.  in: 132 doubles
+ * per problem - x0 12, xi 12, delta 12 (each R row-major 9, t 3), H 36, b 6, y0, d 6, lambda, nu, then iter, trial, have_lin, cur,
+ * n_trace, lin_unneeded, then max_iterations, lm_max_iterations, optimizer, rot_eps, trans_eps, lm_init_lambda_factor, then the 32
+ * reduced sums of the pass (H upper triangle 21, b 6, y0, yi, three counters), then `searched`.  out: per problem two records of
+ * *record_bytes bytes, serial then wave: the state image after the step (it begins with the 87 doubles x0 .. nu in the input's order;
+ * record_bytes - 144 bytes in all), the LM trace row (8 doubles, written when n_trace == 0),
+ * d (6 doubles) and {done, converged, lm_failed, trial} as doubles.  out_or_null == NULL: only *record_bytes is set. */
+int ngicp_step_selftest(ngicp_t* h, const double* in, size_t n_problems, unsigned char* out_or_null, size_t* record_bytes);
 
 /* --- measurement ----------------------------------------------------------- */
 typedef struct ngicp_stats {
