@@ -44,6 +44,17 @@ void fill_robust(const ngicp* h, int& kind, double& c, double& c2) {
   c2 = h->robust_width * h->robust_width;
 }
 
+// The pose prior is applied by the solver's body (lm_solve_body), so every route whose optimiser steps there alone applies it: the
+// default route, NGICP_PASS_IMPL=1, NGICP_QUEUE, NGICP_FUSED, NGICP_PERSIST, NGICP_SERIAL_STEP, the voxelized routes and both batches.
+// k_gicp_head steps in every block from its own sums, without the row: refused.  The sharded entries step on all-reduced sums: refused.
+void refuse_if_prior(const ngicp* h, const char* entry) {
+  if (h->prior_set) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": not available with a pose prior set (ngicp_set_pose_prior(h, NULL, NULL) clears it)"};
+}
+void refuse_prior_under_switch(const ngicp* h, const char* entry) {
+  if (h->prior_set && h->head)
+    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the pose prior is not applied by the route NGICP_HEAD selects (unset it, or ngicp_set_pose_prior(h, NULL, NULL))"};
+}
+
 int queue_switch() {  // NGICP_QUEUE=1 (experiment, round 3): a grid of resident blocks that draw their groups from a counter (k_gicp_queue)
   static const int queue_env = std::getenv("NGICP_QUEUE") ? std::atoi(std::getenv("NGICP_QUEUE")) : 0;
   return queue_env;
@@ -225,6 +236,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
   s.pass_honours_word = 0;
   s.serial_step = h->serial_step;
   s.pass_ticks = nullptr;
+  s.prior = h->prior_set ? h->prior_dev.as<double>() : nullptr;
   s.st_out = nullptr;
   s.nrows = 0;
   a.crow_in = nullptr;
@@ -665,6 +677,7 @@ void launch_persist_one(ngicp* h, const LoopCtx& c, long launched, hipEvent_t st
 
 void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride) {
   refuse_robust_under_switch(h, "ngicp_align");
+  refuse_prior_under_switch(h, "ngicp_align");
   Alignment al;
   reset_results(h);
   LoopCtx c;

@@ -1134,6 +1134,69 @@ int ngicp_robust_terms(ngicp_t* h, const double T_colmajor[16], double* s_out, d
   });
 }
 
+int ngicp_set_pose_prior(ngicp_t* h, const double T_prior_colmajor[16], const double info_colmajor[36]) {
+  return guarded(h, [&] {
+    if (!T_prior_colmajor) {  // clear
+      h->prior_set = false;
+      return;
+    }
+    if (!info_colmajor) throw ArgError{NGICP_ERR_ARG, "pose prior: null information matrix"};
+    const double* T = T_prior_colmajor;
+    const double* I = info_colmajor;
+    for (int i = 0; i < 16; ++i)
+      if (!std::isfinite(T[i])) throw ArgError{NGICP_ERR_ARG, "pose prior: the pose has a non-finite entry"};
+    for (int i = 0; i < 36; ++i)
+      if (!std::isfinite(I[i])) throw ArgError{NGICP_ERR_ARG, "pose prior: the information matrix has a non-finite entry"};
+    if (T[3] != 0.0 || T[7] != 0.0 || T[11] != 0.0 || T[15] != 1.0) throw ArgError{NGICP_ERR_ARG, "pose prior: the pose's last row must be (0, 0, 0, 1)"};
+    for (int r = 0; r < 6; ++r) {
+      if (I[r * 6 + r] < 0.0) throw ArgError{NGICP_ERR_ARG, "pose prior: the information matrix has a negative diagonal entry"};
+      for (int c = r + 1; c < 6; ++c)
+        if (I[c * 6 + r] != I[r * 6 + c]) throw ArgError{NGICP_ERR_ARG, "pose prior: the information matrix must be exactly symmetric"};
+    }
+    double rec[kPriorDoubles];
+    const Pose p = pose_from_colmajor(T);
+    for (int i = 0; i < 9; ++i) rec[i] = p.R[i];
+    for (int i = 0; i < 3; ++i) rec[9 + i] = p.t[i];
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) rec[12 + r * 6 + c] = I[c * 6 + r];
+    // (in stream order behind everything this handle has enqueued; the copy has left `rec` when the call returns)
+    h->prior_dev.ensure(sizeof(rec));
+    HIP_TRY(hipMemcpyAsync(h->prior_dev.p, rec, sizeof(rec), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::memcpy(h->prior_T, T, sizeof(h->prior_T));
+    std::memcpy(h->prior_info, I, sizeof(h->prior_info));
+    h->prior_set = true;
+    // (the stored correspondences and matrices do not depend on the prior: the hooks' state stays valid)
+  });
+}
+
+int ngicp_get_pose_prior(const ngicp_t* h, int* set, double T_prior_colmajor[16], double info_colmajor[36]) {
+  if (!h) return NGICP_ERR_ARG;
+  if (set) *set = h->prior_set ? 1 : 0;
+  if (h->prior_set && T_prior_colmajor) std::memcpy(T_prior_colmajor, h->prior_T, sizeof(h->prior_T));
+  if (h->prior_set && info_colmajor) std::memcpy(info_colmajor, h->prior_info, sizeof(h->prior_info));
+  return NGICP_OK;
+}
+
+int ngicp_pose_prior_terms(ngicp_t* h, const double T_colmajor[16], double r[6], double* cost, double H[36], double b[6]) {
+  return guarded(h, [&] {
+    if (!T_colmajor) throw ArgError{NGICP_ERR_ARG, "null pose"};
+    if (!h->prior_set) throw ArgError{NGICP_ERR_STATE, "no pose prior set (ngicp_set_pose_prior)"};
+    double out[kPriorRowSums + 6];
+    h->prior_out.ensure(sizeof(out));
+    hipLaunchKernelGGL(k_prior_terms, dim3(1), dim3(64), 0, h->stream, pose_from_colmajor(T_colmajor), h->prior_dev.as<double>(), h->prior_out.as<double>());
+    HIP_TRY(hipMemcpyAsync(out, h->prior_out.p, sizeof(out), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    if (H)
+      for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) H[i * 6 + j] = H[j * 6 + i] = out[tri21(i, j)];
+    if (b) std::memcpy(b, out + 21, 6 * sizeof(double));
+    if (cost) *cost = out[27];
+    if (r) std::memcpy(r, out + kPriorRowSums, 6 * sizeof(double));
+  });
+}
+
 int ngicp_voxelmap_builds(const ngicp_t* h, long long* n_builds) {
   if (!h || !n_builds) return NGICP_ERR_ARG;
   *n_builds = h->voxel_builds;
@@ -1480,6 +1543,7 @@ int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_begin");
     refuse_if_robust(h, "ngicp_sharded_begin");
+    refuse_if_prior(h, "ngicp_sharded_begin");
     h->shard_ctx.reset(new LoopCtx);
     LoopCtx& c = *h->shard_ctx;
     prepare_loop(h, c);
@@ -1498,6 +1562,7 @@ int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_pass");
     refuse_if_robust(h, "ngicp_sharded_pass");
+    refuse_if_prior(h, "ngicp_sharded_pass");
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -1516,6 +1581,7 @@ int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_nul
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_step");
     refuse_if_robust(h, "ngicp_sharded_step");
+    refuse_if_prior(h, "ngicp_sharded_step");
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -1547,6 +1613,7 @@ int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_it
   return guarded(h, [&] {
     refuse_if_voxelized(h, "ngicp_sharded_finish");
     refuse_if_robust(h, "ngicp_sharded_finish");
+    refuse_if_prior(h, "ngicp_sharded_finish");
     if (!h->sharded_active) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     hipStream_t s = h->shard_stream ? h->shard_stream : h->stream;  // the steps were enqueued there
     HIP_TRY(hipMemcpyAsync(&h->pin_state[1], h->state.p, sizeof(LmState), hipMemcpyDeviceToHost, s));
@@ -1834,8 +1901,8 @@ int ngicp_transform_cloud(ngicp_t* h, const float* xyz, size_t n, size_t stride_
 // ---- test hook: ngicp_math.h on the device ----
 int ngicp_math_selftest(ngicp_t* h, int which, const double* in, size_t n_problems, double* out) {
   return guarded(h, [&] {
-    static const int kIn[4] = {3, 42, 6, 6}, kOut[4] = {9, 6, 12, 6};
-    if (which < 0 || which > 3 || !in || !out) throw ArgError{NGICP_ERR_ARG, "bad arguments"};
+    static const int kIn[6] = {3, 42, 6, 6, 9, 12 + kPriorDoubles}, kOut[6] = {9, 6, 12, 6, 3, kPriorRowSums};
+    if (which < 0 || which > 5 || !in || !out) throw ArgError{NGICP_ERR_ARG, "bad arguments"};
     if (n_problems == 0) return;
     DevBuf di, dout;
     di.ensure(n_problems * kIn[which] * sizeof(double));

@@ -170,6 +170,8 @@ __global__ void __launch_bounds__(256) k_xyzi_to_unsorted(const float4* __restri
 //         1: ldlt6_solve      in 42 -> out 6      (A row-major 36, rhs 6; impl/lsq_registration_impl.hpp:147-148,172-173)
 //         2: eig3_sym         in 6  -> out 12     (w 3, V 9; stands in for JacobiSVD, impl/nano_gicp_impl.hpp:332)
 //         3: inv3_sym         in 6  -> out 6      (impl/nano_gicp_impl.hpp:205-209)
+//         4: so3_log          in 9  -> out 3      (R row-major; the inverse of so3_exp_matrix)
+//         5: prior_row        in 60 -> out 28     (pose R 9 + t 3, prior R_p 9 + t_p 3 + Lambda 36; H's triangle 21, b 6, cost 1)
 __global__ void __launch_bounds__(64) k_math_selftest(int which, const double* __restrict__ in, int n_problems, double* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_problems) return;
@@ -190,12 +192,34 @@ __global__ void __launch_bounds__(64) k_math_selftest(int which, const double* _
     eig3_sym(C, w, V);
     for (int e = 0; e < 3; ++e) out[i * 12 + e] = w[e];
     for (int e = 0; e < 9; ++e) out[i * 12 + 3 + e] = V[e];
-  } else {
+  } else if (which == 3) {
     double C[6], M[6];
     for (int e = 0; e < 6; ++e) C[e] = in[i * 6 + e];
     inv3_sym(C, M);
     for (int e = 0; e < 6; ++e) out[i * 6 + e] = M[e];
+  } else if (which == 4) {
+    double R[9], phi[3];
+    for (int e = 0; e < 9; ++e) R[e] = in[i * 9 + e];
+    so3_log(R, phi);
+    for (int e = 0; e < 3; ++e) out[i * 3 + e] = phi[e];
+  } else {
+    const double* p = in + (size_t)i * (12 + kPriorDoubles);
+    Pose xi;
+    for (int e = 0; e < 9; ++e) xi.R[e] = p[e];
+    for (int e = 0; e < 3; ++e) xi.t[e] = p[9 + e];
+    double row[kPriorRowSums];
+    prior_row(xi, p + 12, row);
+    for (int e = 0; e < kPriorRowSums; ++e) out[(size_t)i * kPriorRowSums + e] = row[e];
   }
+}
+
+// ngicp_pose_prior_terms: the prior's row (28 sums) and its residual (6) at one pose, by prior_row itself; one thread.
+__global__ void __launch_bounds__(64) k_prior_terms(Pose xi, const double* __restrict__ prior, double* __restrict__ out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double row[kPriorRowSums], r[6];
+  prior_row(xi, prior, row, r);
+  for (int e = 0; e < kPriorRowSums; ++e) out[e] = row[e];
+  for (int e = 0; e < 6; ++e) out[kPriorRowSums + e] = r[e];
 }
 
 // device stream copy (the measured copy bandwidth reported next to the nominal HBM peak): one block moves a

@@ -381,6 +381,11 @@ struct ngicp {
   double robust_width = 1.0;
   DevBuf robust_s, robust_w;             // ngicp_robust_terms: [n_src][K] doubles each
 
+  // pose prior (include/ngicp.h "pose prior"): remembered across mode switches; every SolveArgs is filled from it
+  bool prior_set = false;
+  double prior_T[16] = {}, prior_info[36] = {};  // as given (column-major), for ngicp_get_pose_prior
+  DevBuf prior_dev, prior_out;           // the record the solver reads (kPriorDoubles); ngicp_pose_prior_terms' 28 + 6 doubles
+
   // voxelized GICP (ngicp_voxel.h)
   double voxel_res = 0.0;  // ngicp_set_voxel_resolution: > 0 selects the mode
   int voxel_nbr = NGICP_VOX_DIRECT1;  // ngicp_set_voxel_neighbors: slots per source point (1, 7, 27); remembered while the mode is off

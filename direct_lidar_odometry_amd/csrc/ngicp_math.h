@@ -221,4 +221,116 @@ __host__ __device__ inline void ldlt6_solve(double A[36], const double rhs[6], d
 }
 #undef NG_SWAP
 
+// ---- pose prior (include/ngicp.h, "pose prior"; restated in numpy by tests/_prior_model.py) ----------------------
+// The prior record in device memory: R_p row-major (9), t_p (3), Lambda row-major (36).
+constexpr int kPriorDoubles = 48;
+constexpr int kPriorRowSums = 28;  // H's upper triangle (21, tri21's order), b (6), r^T Lambda r (1)
+constexpr double kSo3LogTaylorS2 = 1e-6;     // so3_log: the series below |sin(theta) axis|^2 = 1e-6 (theta < 1e-3 rad), atan2 from there
+constexpr double kSo3JinvTaylorTh2 = 1e-2;   // so3_jinv_coeff: the series below theta^2 = 1e-2 (theta < 0.1 rad), the half-angle form from there
+
+// The inverse of so3_exp_matrix: phi with exp(phi) = R, for rotation angles up to 3 rad (beyond: finite, otherwise unspecified).
+// v = (R - R^T)^vee / 2 = sin(theta) axis, c = (tr R - 1) / 2 = cos(theta); phi = v * theta / sin(theta).
+NG_HD void so3_log(const double R[9], double phi[3]) {
+  const double vx = 0.5 * (R[7] - R[5]), vy = 0.5 * (R[2] - R[6]), vz = 0.5 * (R[3] - R[1]);
+  const double c = 0.5 * ((R[0] + R[4] + R[8]) - 1.0);
+  const double s2 = vx * vx + vy * vy + vz * vz;
+  double f;
+  if (s2 < kSo3LogTaylorS2 && c > 0.0) {
+    f = 1.0 + s2 * (1.0 / 6.0 + s2 * (3.0 / 40.0 + s2 * (15.0 / 336.0)));  // asin(s) / s
+  } else {
+    const double s = sqrt(s2);
+    f = s > 0.0 ? atan2(s, c) / s : 0.0;
+  }
+  phi[0] = f * vx;
+  phi[1] = f * vy;
+  phi[2] = f * vz;
+}
+
+// J_l^{-1}(phi) = I - [phi]x / 2 + c(theta) [phi]x^2,  c = (1 - (theta/2) cot(theta/2)) / theta^2  (-> 1/12 at 0)
+NG_HD double so3_jinv_coeff(const double theta_sq) {
+  if (theta_sq < kSo3JinvTaylorTh2)
+    return 1.0 / 12.0 + theta_sq * (1.0 / 720.0 + theta_sq * (1.0 / 30240.0 + theta_sq * (1.0 / 1209600.0 + theta_sq * (1.0 / 47900160.0))));
+  const double half = 0.5 * sqrt(theta_sq);
+  return (1.0 - half * cos(half) / sin(half)) / theta_sq;
+}
+NG_HD double sel3(const int i, const double a, const double b, const double c) { return i == 0 ? a : (i == 1 ? b : c); }
+// element (k, i) of [v]x = {{0, -z, y}, {z, 0, -x}, {-y, x, 0}}
+NG_HD double skew_elem(const int k, const int i, const double x, const double y, const double z) {
+  if (k == i) return 0.0;
+  const double m = sel3(3 - k - i, x, y, z);
+  return ((i - k + 3) % 3 == 1) ? -m : m;
+}
+// The element expressions of the prior's row, ONE definition each: prior_row below runs them in a loop, the solver (lm_solve_body,
+// ngicp_pass.h) one element per lane.
+NG_HD double so3_jinv_elem(const int k, const int i, const double px, const double py, const double pz, const double theta_sq, const double c) {
+  const double d = k == i ? 1.0 : 0.0;
+  return (d - 0.5 * skew_elem(k, i, px, py, pz)) + c * (sel3(k, px, py, pz) * sel3(i, px, py, pz) - d * theta_sq);
+}
+NG_HD void so3_left_jacobian_inv(const double phi[3], double J[9]) {
+  const double theta_sq = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+  const double c = so3_jinv_coeff(theta_sq);
+  for (int m = 0; m < 9; ++m) J[m] = so3_jinv_elem(m / 3, m % 3, phi[0], phi[1], phi[2], theta_sq, c);
+}
+// element (k, i) of J_p = [[J_l^{-1}(phi), 0], [-[t]x, I]]: d r / d d under T <- (so3_exp(d[0:3]), d[3:6]) * T
+NG_HD double prior_jac_elem(const int k, const int i, const double px, const double py, const double pz, const double theta_sq, const double c, const double tx,
+                            const double ty, const double tz) {
+  if (k < 3) return i < 3 ? so3_jinv_elem(k, i, px, py, pz, theta_sq, c) : 0.0;
+  if (i < 3) return -skew_elem(k - 3, i, tx, ty, tz);
+  return k == i ? 1.0 : 0.0;
+}
+// r = (log_SO3(R R_p^T), t - t_p), and what J_l^{-1} needs of phi
+NG_HD void prior_residual(const Pose& xi, const double* P, double r[6], double& theta_sq, double& c) {
+  double Rrel[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) Rrel[i * 3 + j] = pose_mul_r(xi.R[i * 3 + 0], xi.R[i * 3 + 1], xi.R[i * 3 + 2], P[j * 3 + 0], P[j * 3 + 1], P[j * 3 + 2]);
+  so3_log(Rrel, r);
+  for (int i = 0; i < 3; ++i) r[3 + i] = xi.t[i] - P[9 + i];
+  theta_sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+  c = so3_jinv_coeff(theta_sq);
+}
+// Sum e of the row: u^T (Lambda w) = sum_k u[k] * (sum_l Lambda[k][l] * w[l]), k and l ascending, where
+//   e < 21 (H entry (i, j), tri21's order): u = column i of J, w = column j of J;   e in 21..26 (b[i]): u = column i of J, w = r;
+//   e == 27 (the cost): u = w = r.
+NG_HD double prior_row_elem(const int e, const double* J, const double* Lam, const double* r) {
+  int i = 0, j = 0;
+  if (e < 21) {
+    int base = 0;  // row i of the triangle starts at entry 6 i - i (i - 1) / 2
+#pragma unroll
+    for (int q = 1; q < 6; ++q)
+      if (e >= q * 6 - (q * (q - 1)) / 2) i = q, base = q * 6 - (q * (q - 1)) / 2;
+    j = i + (e - base);
+  } else if (e < 27) {
+    i = e - 21;
+  }
+  // every operand is fetched before the first product (in the solver they lie in LDS: 48 loads in flight instead of 78 round trips)
+  double u[6], w[6], L[36];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double jc_i = J[k * 6 + i], jc_j = J[k * 6 + j], rk = r[k];
+    u[k] = e < 27 ? jc_i : rk;
+    w[k] = e < 21 ? jc_j : rk;
+  }
+#pragma unroll
+  for (int m = 0; m < 36; ++m) L[m] = Lam[m];
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double lw = 0.0;
+#pragma unroll
+    for (int l = 0; l < 6; ++l) lw += L[k * 6 + l] * w[l];
+    acc += u[k] * lw;
+  }
+  return acc;
+}
+// The prior's virtual block row at the pose xi: out[0..20] += to H's upper triangle, out[21..26] to b, out[27] to y0 and to yi.
+// r_out (6), when not null, receives the residual.
+NG_HD void prior_row(const Pose& xi, const double* P, double out[kPriorRowSums], double* r_out = nullptr) {
+  double r[6], J[36], theta_sq, c;
+  prior_residual(xi, P, r, theta_sq, c);
+  for (int m = 0; m < 36; ++m) J[m] = prior_jac_elem(m / 6, m % 6, r[0], r[1], r[2], theta_sq, c, xi.t[0], xi.t[1], xi.t[2]);
+  for (int e = 0; e < kPriorRowSums; ++e) out[e] = prior_row_elem(e, J, P + 12, r);
+  if (r_out)
+    for (int i = 0; i < 6; ++i) r_out[i] = r[i];
+}
+
 }  // namespace ngk

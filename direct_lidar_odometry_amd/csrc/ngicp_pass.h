@@ -270,6 +270,8 @@ struct SolveArgs {
   int serial_step;         // env NGICP_SERIAL_STEP=1: lane 0 of wave 0 runs lm_step (the reference form) instead of the wave running lm_step_wave
                            // (fills the padding in front of the next pointer: the size of the struct, and of PassArgs, does not change)
   unsigned long long* pass_ticks;  // persist: [2 * max passes] 100 MHz ticks {last block arrived, next pass released} per pass, or null
+  const double* prior;     // the pose prior's record in device memory (kPriorDoubles: R_p 9, t_p 3, Lambda 36; written by the host before
+                           // the launch, never by a kernel), or null: no prior.  Wave 0 adds prior_row at xi to the reduced sums (modes 0, 1, 2)
 };
 
 static_assert(offsetof(SolveArgs, pass_ticks) == offsetof(SolveArgs, pass_honours_word) + 8, "serial_step takes no room of its own");
@@ -1218,6 +1220,11 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
     if constexpr (PERSIST) oc[k] = (order_it && gi <= last_grp) ? __hip_atomic_load(a.grp_cost + gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
     else oc[k] = (order_it && gi <= last_grp) ? a.grp_cost[gi] : 0;
   }
+  // the pose prior's record, one double per lane of wave 0, behind the last load of the same batch and in front of its first wait (no
+  // kernel writes the record: a plain load on every route).  Here, where the flag's test ends the basic block anyway: a branch among the
+  // loads above would split the block they are scheduled in.
+  double prior_v = 0.0;
+  if (a.prior && threadIdx.x < kPriorDoubles) prior_v = a.prior[threadIdx.x];
   if (a.mode == 0 && done_at_entry) return;  // (a scalar load issued at the top: it does not wait for the vector loads above)
   if (a.dbg_stamps && threadIdx.x == 0) a.dbg_stamps[0] = t_solver_entry;  // (working launches only)
   // The serial lane works on the LDS image of the state in place (a register-resident copy needs ~260 VGPRs: it spills at two
@@ -1365,6 +1372,26 @@ __device__ __forceinline__ void lm_solve_body(const SolveArgs& a, SolveShared<TH
     if (a.dbg_stamps && sw == 0 && lane == 0) a.dbg_stamps[7] = __builtin_amdgcn_s_memtime() - t_ord;
   }
   if (wave != 0) return;
+  if (a.prior) {
+    // ---- the pose prior: one more (virtual) block row, evaluated at xi - the pose the pass was evaluated at - and added to the sums
+    //      AFTER the fixed-order reduction, one addition per sum (include/ngicp.h, "pose prior").  Every mode below then sees the summed
+    //      H, b, y0, yi.  The residual (so3_log: one dependent chain) is computed by every lane on values all lanes agree on; the 36
+    //      elements of J_p and the 28 sums run one per lane (prior_jac_elem, prior_row_elem: prior_row's own expressions).
+    //      Scratch: wsum, idle since the barrier above (only threads of this wave read it, before that barrier). ----
+    double* const P = &wsum[0][0];  // [0, 48) the record, [48, 84) J_p row-major, [84, 90) r
+    if (lane < kPriorDoubles) P[lane] = prior_v;
+    wave_sync();
+    double r[6], theta_sq, jc;
+    prior_residual(L.xi, P, r, theta_sq, jc);
+    if (lane < 36) P[kPriorDoubles + lane] = prior_jac_elem(lane / 6, lane % 6, r[0], r[1], r[2], theta_sq, jc, L.xi.t[0], L.xi.t[1], L.xi.t[2]);
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+      if (lane == 36 + q) P[kPriorDoubles + 36 + q] = r[q];
+    wave_sync();
+    // lanes 0..26: H's triangle and b; lane 27: the cost into y0; lane 28: the cost into yi
+    if (lane < kPriorRowSums + 1) sums[lane] += prior_row_elem(lane < kPriorRowSums ? lane : kPriorRowSums - 1, P + kPriorDoubles, P + 12, P + kPriorDoubles + 36);
+    wave_sync();
+  }
   if (a.mode == 2) {  // compute_error hook
     if (lane == 0) st->hot.y0 = sums[28];
     return;

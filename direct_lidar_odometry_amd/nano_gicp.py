@@ -99,6 +99,7 @@ EXPORTS = [
     "ngicp_set_voxel_rolling", "ngicp_get_voxel_rolling", "ngicp_voxel_rolling_insert", "ngicp_voxel_rolling_evict", "ngicp_voxel_rolling_clear",
     "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
     "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
+    "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
 ]
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
@@ -207,6 +208,9 @@ def load_library() -> C.CDLL:
     L.ngicp_set_robust_kernel.argtypes = [vp, C.c_int, C.c_double]
     L.ngicp_get_robust_kernel.argtypes = [vp, c_i32p, c_f64p]
     L.ngicp_robust_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, C.c_size_t, c_i32p]
+    L.ngicp_set_pose_prior.argtypes = [vp, c_f64p, c_f64p]
+    L.ngicp_get_pose_prior.argtypes = [vp, c_i32p, c_f64p, c_f64p]
+    L.ngicp_pose_prior_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]
     _lib = L
     return L
 
@@ -435,6 +439,31 @@ class NanoGICP:
         self._ck(self._L.ngicp_robust_terms(self._h, _p(t, c_f64p), _p(s, c_f64p), _p(w, c_f64p), s.size, C.byref(k)))
         assert k.value == K
         return s, w
+
+    def setPosePrior(self, T, info):
+        """A Gaussian prior on the pose (include/ngicp.h "pose prior"): the cost gains r^T info r with r = (log_SO3(R R_p^T), t - t_p),
+        T = (R_p, t_p) a 4x4 pose and info a symmetric 6x6 information matrix (rotation first).  It holds for align, alignBatch,
+        alignBatchVoxel, linearize and compute_error on every route and is remembered across mode switches; the sharded entries and an
+        align under NGICP_HEAD raise while it is set."""
+        t = _colmajor16(T, np.float64)
+        i = np.ascontiguousarray(np.asarray(info, dtype=np.float64).reshape(6, 6).T.reshape(36))
+        self._ck(self._L.ngicp_set_pose_prior(self._h, _p(t, c_f64p), _p(i, c_f64p)))
+
+    def clearPosePrior(self):
+        self._ck(self._L.ngicp_set_pose_prior(self._h, None, None))
+
+    def getPosePrior(self):
+        """-> (T (4, 4), info (6, 6)), or None when no prior is set"""
+        k = C.c_int(0); t = np.empty(16); i = np.empty(36)
+        self._ck(self._L.ngicp_get_pose_prior(self._h, C.byref(k), _p(t, c_f64p), _p(i, c_f64p)))
+        return (t.reshape(4, 4).T.copy(), i.reshape(6, 6).T.copy()) if k.value else None
+
+    def pose_prior_terms(self, T):
+        """-> (r (6,), cost, H (6, 6), b (6,)): the prior's share alone at the pose T, evaluated on the device by the solver's functions."""
+        t = _colmajor16(T, np.float64)
+        r = np.empty(6); H = np.empty(36); b = np.empty(6); c = C.c_double(0)
+        self._ck(self._L.ngicp_pose_prior_terms(self._h, _p(t, c_f64p), _p(r, c_f64p), C.byref(c), _p(H, c_f64p), _p(b, c_f64p)))
+        return r, c.value, H.reshape(6, 6).T.copy(), b
 
     def setTuning(self, voxel_size: float = 0.0, lanes_per_query: int = 0):
         self._ck(self._L.ngicp_set_tuning(self._h, float(voxel_size), int(lanes_per_query)))
@@ -797,9 +826,9 @@ class NanoGICP:
     def mapClear(self): self._ck(self._L.ngicp_map_clear(self._h))
 
     def mathSelftest(self, which: int, problems) -> np.ndarray:
-        """ngicp_math.h on the device (0 so3_exp, 1 ldlt6_solve, 2 eig3_sym, 3 inv3_sym), one problem per row."""
+        """ngicp_math.h on the device (0 so3_exp, 1 ldlt6_solve, 2 eig3_sym, 3 inv3_sym, 4 so3_log, 5 prior_row), one problem per row."""
         a = np.ascontiguousarray(problems, dtype=np.float64)
-        out = np.empty((a.shape[0], (9, 6, 12, 6)[which]))
+        out = np.empty((a.shape[0], (9, 6, 12, 6, 3, 28)[which]))
         self._ck(self._L.ngicp_math_selftest(self._h, int(which), _p(a, c_f64p), a.shape[0], _p(out, c_f64p)))
         return out
 

@@ -434,6 +434,28 @@ class NanoGICP {
     }
     return true;
   }
+  // A Gaussian prior on the pose (include/ngicp.h "pose prior"): the cost of every align() - exact, voxelized with any neighbourhood,
+  // rolling map, alignBatch / alignBatchVoxel - gains r^T info r, r = (log_SO3(R R_p^T), t - t_p), with T_prior = (R_p, t_p) and info a
+  // symmetric 6x6 information matrix, rotation first (rad^-2, m^-2).  E.g. an IMU or wheel-odometry prediction with its inverse
+  // covariance; info = diag(w, w, 0, 0, 0, w) at T_prior = guess holds roll, pitch and height (planar motion).  Remembered across mode
+  // switches.  A bad argument is reported and changes nothing (false).  (With Eigen: Matrix4d, Matrix<double, 6, 6>.)
+  bool setPosePrior(const types::Matrix4d& T_prior, const types::Matrix6d& info) {
+    return h_ && check(ngicp_set_pose_prior(h_, T_prior.data(), info.data()), "setPosePrior");
+  }
+  void clearPosePrior() {
+    if (h_) check(ngicp_set_pose_prior(h_, nullptr, nullptr), "clearPosePrior");
+  }
+  // true when a prior is set (then T_prior and info, where not null, receive it)
+  bool getPosePrior(types::Matrix4d* T_prior = nullptr, types::Matrix6d* info = nullptr) const {
+    int set = 0;
+    if (h_) check(ngicp_get_pose_prior(h_, &set, T_prior ? T_prior->data() : nullptr, info ? info->data() : nullptr), "getPosePrior");
+    return set != 0;
+  }
+  // The prior's share alone at the pose T: the residual r (6), the cost r^T info r, H_p = J_p^T info J_p and b_p = J_p^T info r (6),
+  // evaluated on the device by the solver's own functions.  Any output may be null.  False on error (no prior set).
+  bool posePriorTerms(const types::Matrix4d& T, double* r6, double* cost, types::Matrix6d* H, double* b6) {
+    return h_ && check(ngicp_pose_prior_terms(h_, T.data(), r6, cost, H ? H->data() : nullptr, b6), "posePriorTerms");
+  }
   // setVoxelSubmapMerge(true): the voxel map of a submap assembled by setSubmapKeyframes is merged from per-keyframe voxel sums, which
   // every keyframe carries and which are built once per keyframe and resolution, instead of being summed over all points of the submap
   // at every change (include/ngicp.h "merged voxel map").  The voxels, their numbers and their counts are the same; means and covariances

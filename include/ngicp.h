@@ -375,6 +375,44 @@ int ngicp_set_robust_kernel(ngicp_t* h, int kind, double width);
 int ngicp_get_robust_kernel(const ngicp_t* h, int* kind, double* width);
 int ngicp_robust_terms(ngicp_t* h, const double T_colmajor[16], double* s_out, double* w_out, size_t capacity_doubles, int* K_out);
 
+/* --- pose prior: a Gaussian prior on the pose, applied in the solver (no counterpart in the reference; csrc/ngicp_math.h prior_row,
+ * csrc/ngicp_pass.h lm_solve_body; restated in numpy by tests/_prior_model.py) -----------------------------------------
+ * With a prior set, every route minimises  y(T) = y_data(T) + r(T)^T L r(T)  - the scaling of sum e^T M e, no factor 1/2.
+ *   prior      a pose T_p = (R_p, t_p) in double and a symmetric 6x6 information matrix L, rotation first, then translation (H's
+ *              order); units rad^-2, m^-2 and their mixtures.
+ *   residual   at T = (R, t):  phi = log_SO3(R R_p^T),  tau = t - t_p,  r = (phi, tau).
+ *   log_SO3    the inverse of the engine's so3_exp.  v = ((R - R^T)^vee) / 2, c = (tr R - 1) / 2, s2 = |v|^2.  If s2 < 1e-6 and c > 0
+ *              (angles below 1e-3 rad): phi = v (1 + s2 (1/6 + s2 (3/40 + s2 15/336))); otherwise phi = v atan2(sqrt(s2), c) / sqrt(s2)
+ *              (0 where s2 == 0).  Domain: rotation angles of at most 3 rad; beyond that the result is unspecified but finite.
+ *   Jacobian   under the engine's update T <- (so3_exp(d[0:3]), d[3:6]) * T:  J_p = [[J_l^{-1}(phi), 0], [-[t]x, I]], with the exact
+ *              inverse left Jacobian of SO(3)  J_l^{-1} = I - [phi]x / 2 + k [phi]x^2,  [phi]x^2 = phi phi^T - th2 I,  th2 = |phi|^2,
+ *              k = (1 - (th/2) cos(th/2) / sin(th/2)) / th2 for th2 >= 1e-2 (0.1 rad), and below that the series
+ *              k = 1/12 + th2 (1/720 + th2 (1/30240 + th2 (1/1209600 + th2 / 47900160))).
+ *   a pass     evaluated at the trial pose xi gains  H += J_p^T L J_p,  b += J_p^T L r,  y0 += r^T L r,  yi += r^T L r,  all at xi:
+ *              one addition per sum, made by the solver after its fixed-order reduction of the block rows.
+ *   order      every one of the 28 sums is  u^T (L w) = sum_k u[k] * (sum_l L[k][l] * w[l]),  k and l ascending from 0, both sums
+ *              starting from 0.0:  H(i, j), i <= j:  u = column i of J_p, w = column j of J_p;  b[i]: u = column i of J_p, w = r;
+ *              the cost: u = w = r.  J_p is formed as a dense 6x6 first.  (R R_p^T)[i][j] = R[i][0] R_p[j][0] + R[i][1] R_p[j][1] + R[i][2] R_p[j][2].
+ * The prior is not re-weighted by a robust kernel.  The search, the distance gate, the covariances, lambda's initialisation (which sees
+ * the summed H), the convergence test and the trace format are unchanged; the final Hessian is the summed H.  ngicp_linearize and
+ * ngicp_compute_error include the prior; ngicp_pose_prior_terms reports its share alone.
+ *
+ * ngicp_set_pose_prior: T_prior and info are column-major doubles.  A NULL T_prior clears the prior.  A non-finite entry, a last row of
+ * T_prior other than (0, 0, 0, 1), an info that is not exactly symmetric or has a negative diagonal entry is NGICP_ERR_ARG and changes
+ * nothing.  The setting is remembered across mode switches (exact / voxelized, neighbourhood, rolling map), leaves the state of the
+ * hooks valid and takes effect at the next ngicp_align / ngicp_align_batch / ngicp_voxel_align_batch / ngicp_linearize /
+ * ngicp_compute_error.  The batch entries share the one prior among their lanes; lane g equals ngicp_align(guess g) bit for bit.
+ * Every kernel-variant switch whose optimiser steps in the solver's body applies the prior, bit-equal to the default route:
+ * NGICP_PASS_IMPL=1, NGICP_FUSED, NGICP_QUEUE, NGICP_PERSIST, NGICP_SERIAL_STEP.  While a prior is set these return NGICP_ERR_ARG (the
+ * message names the pose prior): ngicp_align under NGICP_HEAD (every block steps from its own sums there), and ngicp_sharded_begin /
+ * _pass / _step / _finish.
+ * ngicp_get_pose_prior: *set is 0 or 1; T and info are written only when a prior is set.  Every pointer may be NULL.
+ * ngicp_pose_prior_terms: at the pose T, the residual r, the cost r^T L r, H_p = J_p^T L J_p (6x6, symmetric) and b_p = J_p^T L r,
+ * evaluated on the device by the functions the solver calls.  Every output pointer may be NULL.  NGICP_ERR_STATE when no prior is set. */
+int ngicp_set_pose_prior(ngicp_t* h, const double T_prior_colmajor[16], const double info_colmajor[36]);
+int ngicp_get_pose_prior(const ngicp_t* h, int* set, double T_prior_colmajor[16], double info_colmajor[36]);
+int ngicp_pose_prior_terms(ngicp_t* h, const double T_colmajor[16], double r[6], double* cost, double H[36], double b[6]);
+
 /* --- more than one initial guess on the same source / target pair (no counterpart in the reference) ------------------------------
  * ngicp_align_batch: n_guesses alignments on this handle at once.  They share the source, the target, both indices, both covariance
  * sets and every parameter; each has its own initial guess.  One kernel launch per pass serves every guess still running, one solver
@@ -424,7 +462,9 @@ int ngicp_fitness_score_batch(ngicp_t* h, size_t n, const float* T_n16_colmajor,
  * (gicp/so3.hpp:99-118 followed by Quaternion::toRotationMatrix; in: 3 doubles, out: R row-major 9), 1 the 6x6 LDLT solve that
  * stands in for Eigen::LDLT (impl/lsq_registration_impl.hpp:147-148,172-173; in: A row-major 36 + rhs 6, out: 6), 2 the
  * symmetric 3x3 eigen-decomposition that stands in for JacobiSVD (impl/nano_gicp_impl.hpp:332; in: {xx,xy,xz,yy,yz,zz}, out:
- * w 3 + V row-major 9), 3 the symmetric 3x3 inverse (impl/nano_gicp_impl.hpp:205-209; in 6, out 6). */
+ * w 3 + V row-major 9), 3 the symmetric 3x3 inverse (impl/nano_gicp_impl.hpp:205-209; in 6, out 6), 4 so3_log ("pose prior"; in: R
+ * row-major 9, out: 3), 5 the pose prior's row (in: pose R row-major 9 + t 3, prior R_p row-major 9 + t_p 3 + L row-major 36; out: H's
+ * upper triangle row by row 21 + b 6 + the cost 1). */
 int ngicp_math_selftest(ngicp_t* h, int which, const double* in, size_t n_problems, double* out);
 /* One step of the optimiser on the device in both of its forms (unit-test hook): the serial step on one lane and the wave-level step the
  * solver runs by default (NGICP_SERIAL_STEP=1 selects the serial one), from the same state, sums and configuration.  in: 132 doubles
