@@ -14,29 +14,33 @@ std::mutex& persist_mutex(int device) {  // one persistent alignment per device 
   return m[(unsigned)device % 64u];
 }
 
-int pass_impl() {
-  static const int impl = std::getenv("NGICP_PASS_IMPL") ? std::atoi(std::getenv("NGICP_PASS_IMPL")) : 0;
-  return impl;
+// ---- the handle's side of ngicp_route.h: the facts it contributes, and the refusals as errors ----
+route::Facts route_facts(const ngicp* h, route::Caller caller, int nblocks = 1) {
+  route::Facts f;
+  f.caller = caller;
+  f.persist = h->persist;
+  f.robust = h->robust_kind != NGICP_ROBUST_NONE;
+  f.prior = h->prior_set;
+  f.iterating = h->p.max_iter > 0;
+  f.nblocks = nblocks;
+  f.pass_slots = h->pass_slots;
+  f.persist_slots = h->persist_slots;
+  f.max_passes = max_passes(h->p);
+  return f;
 }
-
-// The kernel variants that have no robust instantiation: with a robust kernel set, a route that would run one of them is refused
-// (a pass that silently ignored the kernel would be a wrong answer, not a slower one).
-const char* robust_unsupported_switch(const ngicp* h) {
-  if (pass_impl() == 1) return "NGICP_PASS_IMPL=1";
-  if (const char* s = std::getenv("NGICP_FUSED")) if (std::atoi(s) != 0) return "NGICP_FUSED";
-  if (const char* s = std::getenv("NGICP_QUEUE")) if (std::atoi(s) != 0) return "NGICP_QUEUE";
-  if (h->persist) return "NGICP_PERSIST";
-  if (h->head) return "NGICP_HEAD";
-  return nullptr;
+// what the entry point refuses outright (route::kEntries), as its error
+void refuse_for(const ngicp* h, route::Entry e) {
+  const std::string why = route::entry_refusal(e, h->voxel_res > 0.0, h->robust_kind != NGICP_ROBUST_NONE, h->prior_set);
+  if (!why.empty()) throw ArgError{NGICP_ERR_ARG, why};
 }
-void refuse_if_robust(const ngicp* h, const char* entry) {
-  if (h->robust_kind != NGICP_ROBUST_NONE)
-    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": not available with a robust kernel set (ngicp_set_robust_kernel(h, NGICP_ROBUST_NONE, 0) turns it off)"};
+// what the switches that are set cannot do with the handle's robust kernel or pose prior (route::refusal), as the entry's error
+void refuse_route(const ngicp* h, route::Caller caller, const char* entry) {
+  const std::string why = route::refusal(route::switches(), h->sw, route_facts(h, caller), entry);
+  if (!why.empty()) throw ArgError{NGICP_ERR_ARG, why};
 }
-void refuse_robust_under_switch(const ngicp* h, const char* entry) {
-  if (h->robust_kind == NGICP_ROBUST_NONE) return;
-  if (const char* sw = robust_unsupported_switch(h))
-    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the robust kernel has no instantiation of the pass variant " + sw + " selects (unset it, or ngicp_set_robust_kernel(h, NGICP_ROBUST_NONE, 0))"};
+// the pass kernel of a caller that has one launch-per-pass route to take (the hooks, ngicp_sharded_pass)
+route::Variant pass_variant(const ngicp* h, route::Caller caller, int nblocks) {
+  return route::choose_route(route::switches(), h->sw, route_facts(h, caller, nblocks)).variant;
 }
 void fill_robust(const ngicp* h, int& kind, double& c, double& c2) {
   kind = h->robust_kind;
@@ -44,67 +48,35 @@ void fill_robust(const ngicp* h, int& kind, double& c, double& c2) {
   c2 = h->robust_width * h->robust_width;
 }
 
-// The pose prior is applied by the solver's body (lm_solve_body), so every route whose optimiser steps there alone applies it: the
-// default route, NGICP_PASS_IMPL=1, NGICP_QUEUE, NGICP_FUSED, NGICP_PERSIST, NGICP_SERIAL_STEP, the voxelized routes and both batches.
-// k_gicp_head steps in every block from its own sums, without the row: refused.  The sharded entries step on all-reduced sums: refused.
-void refuse_if_prior(const ngicp* h, const char* entry) {
-  if (h->prior_set) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": not available with a pose prior set (ngicp_set_pose_prior(h, NULL, NULL) clears it)"};
-}
-void refuse_prior_under_switch(const ngicp* h, const char* entry) {
-  if (h->prior_set && h->head)
-    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the pose prior is not applied by the route NGICP_HEAD selects (unset it, or ngicp_set_pose_prior(h, NULL, NULL))"};
-}
-
-int queue_switch() {  // NGICP_QUEUE=1 (experiment, round 3): a grid of resident blocks that draw their groups from a counter (k_gicp_queue)
-  static const int queue_env = std::getenv("NGICP_QUEUE") ? std::atoi(std::getenv("NGICP_QUEUE")) : 0;
-  return queue_env;
-}
-
-void launch_pass(ngicp* h, const PassArgs& a, int nblocks, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
-  // 32-query batches, 2 lanes per query.  Two builds of the kernel: 3 waves per SIMD (129 VGPRs), and 4 (128 VGPRs, two spilled
-  // dwords, 4 blocks per CU) for grids of more than two rounds of blocks, where the launch is bound by how many blocks pass through
-  // the chip rather than by its slowest block.
-  static const int force = std::getenv("NGICP_PASS_WPS") ? std::atoi(std::getenv("NGICP_PASS_WPS")) : 0;  // (A/B timing only)
-  const int impl = pass_impl();  // 0: walks in global memory (default), 1: the staged search of ngicp_pass_st.h (round 3 experiment: exact, slower - DESIGN.md §5)
-  const bool four = force ? force == 4 : nblocks > 2 * h->pass_slots;
-  if (impl == 1) {
-    PassArgs b = a;
-    b.fused = 0;
-    // cells that cover the distance gate around a query's own cell (its reach box is clamped there; beyond it the shell walk takes over)
-    int need = kStGrowMax;
-    if (h->p.max_corr_dist < 1e30) need = (int)std::ceil(h->p.max_corr_dist / (double)a.grid.h);
-    b.stage_grow = std::max(1, std::min(kStGrowMax, need));
-    if (force ? force == 4 : true)  // (128 VGPRs either way; the 4-wave build's smaller tables leave room for a fourth block per CU)
-      hipExtLaunchKernelGGL((k_gicp_pass_st<4>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, b);
-    else
-      hipExtLaunchKernelGGL((k_gicp_pass_st<3>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, b);
-    return;
+// One launch of the pass kernel route::choose_route picked.  32-query batches, 2 lanes per query.  Two builds of every kernel: 3 waves per
+// SIMD (129 VGPRs), and 4 (128 VGPRs, two spilled dwords, 4 blocks per CU) for grids of more than two rounds of blocks, where the launch
+// is bound by how many blocks pass through the chip rather than by its slowest block.
+void launch_pass(ngicp* h, const PassArgs& a, const route::Variant& v, int nblocks, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
+  using K = void (*)(PassArgs);
+  const bool four = v.waves == 4;
+  K kernel = nullptr;
+  PassArgs b = a;
+  unsigned grid = (unsigned)nblocks;
+  switch (v.family) {
+    case route::Family::Staged: {  // the staged search of ngicp_pass_st.h (round 3 experiment: exact, slower - DESIGN.md §5)
+      // cells that cover the distance gate around a query's own cell (its reach box is clamped there; beyond it the shell walk takes over)
+      int need = kStGrowMax;
+      if (h->p.max_corr_dist < 1e30) need = (int)std::ceil(h->p.max_corr_dist / (double)a.grid.h);
+      b.stage_grow = std::max(1, std::min(kStGrowMax, need));
+      kernel = four ? K(k_gicp_pass_st<4>) : K(k_gicp_pass_st<3>);
+      break;
+    }
+    case route::Family::Queue:  // a grid of resident blocks that draw their groups from a counter (round 3 experiment)
+      grid = (unsigned)std::min(nblocks, h->queue_slots[four]);
+      kernel = four ? K(k_gicp_queue<2, 4>) : K(k_gicp_queue<2, 3>);
+      break;
+    case route::Family::Walks:  // walks in global memory; fused: the solver in the tail of the launch; robust: the term weighted in its K4 leg and K3 tail
+      if (v.fused) kernel = four ? K(k_gicp_pass<2, 4, true>) : K(k_gicp_pass<2, 3, true>);
+      else if (v.robust) kernel = four ? K(k_gicp_pass<2, 4, false, true>) : K(k_gicp_pass<2, 3, false, true>);
+      else kernel = four ? K(k_gicp_pass<2, 4>) : K(k_gicp_pass<2, 3>);
+      break;
   }
-  if (queue_switch() && !a.fused && !(a.mode & 4) && !a.dbg_stamps && !a.dbg_span && !a.dbg_qstats) {
-    if (four)
-      hipExtLaunchKernelGGL((k_gicp_queue<2, 4>), dim3((unsigned)std::min(nblocks, h->queue_slots[1])), dim3(256), 0, s, start, stop, 0, a);
-    else
-      hipExtLaunchKernelGGL((k_gicp_queue<2, 3>), dim3((unsigned)std::min(nblocks, h->queue_slots[0])), dim3(256), 0, s, start, stop, 0, a);
-    return;
-  }
-  if (a.fused) {  // (the solver in the tail of the launch: a build of its own)
-    if (four)
-      hipExtLaunchKernelGGL((k_gicp_pass<2, 4, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
-    else
-      hipExtLaunchKernelGGL((k_gicp_pass<2, 3, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
-    return;
-  }
-  if (a.robust_kind != NGICP_ROBUST_NONE) {  // (the robust instantiations: the same kernel with the term weighted in its K4 leg and its K3 tail)
-    if (four)
-      hipExtLaunchKernelGGL((k_gicp_pass<2, 4, false, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
-    else
-      hipExtLaunchKernelGGL((k_gicp_pass<2, 3, false, true>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
-    return;
-  }
-  if (four)
-    hipExtLaunchKernelGGL((k_gicp_pass<2, 4>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
-  else
-    hipExtLaunchKernelGGL((k_gicp_pass<2, 3>), dim3(nblocks), dim3(256), 0, s, start, stop, 0, a);
+  hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, start, stop, 0, b);
 }
 
 struct LoopCtx {
@@ -167,7 +139,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
     a.tgt3 = T.xyz3();
     a.tgtp = T.xyzp();
     a.tgt_cell_start = T.cells();
-    a.tgt_cell_box = (h->cell_boxes && T.has_boxes) ? T.cell_box.as<unsigned int>() + kCellPad : nullptr;
+    a.tgt_cell_box = (h->sw.cell_boxes && T.has_boxes) ? T.cell_box.as<unsigned int>() + kCellPad : nullptr;
     a.cov_tgt = covs_for(h, h->tgt_covs, h->tgt.dev);
     a.grid = T.grid;
   } else {
@@ -208,7 +180,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
     // rings worth staging: enough to cover the distance gate (the search never looks farther), at most kStageMaxGrow
     int need = kStageMaxGrow;
     if (with_target && h->p.max_corr_dist < 1e30) need = (int)std::ceil(h->p.max_corr_dist / (double)a.grid.h);
-    a.stage_grow = h->stage_grow <= 0 ? 0 : std::max(1, std::min(std::min(kStageMaxGrow, h->stage_grow), need));  // 0: search straight from global memory
+    a.stage_grow = h->sw.stage_grow <= 0 ? 0 : std::max(1, std::min(std::min(kStageMaxGrow, h->sw.stage_grow), need));  // 0: search straight from global memory
   }
 
   SolveArgs& s = c.sa;
@@ -234,7 +206,7 @@ void prepare_loop(ngicp* h, LoopCtx& c, bool own_buffers = true, bool with_targe
   s.t_first = nullptr;
   s.persist = 0;
   s.pass_honours_word = 0;
-  s.serial_step = h->serial_step;
+  s.serial_step = h->sw.serial_step;
   s.pass_ticks = nullptr;
   s.prior = h->prior_set ? h->prior_dev.as<double>() : nullptr;
   s.st_out = nullptr;
@@ -389,7 +361,7 @@ void feed_alignment(ngicp* h, Alignment& al, long max_launches, Launch&& launch)
     HIP_TRY(hipStreamSynchronize(h->stream));  // (max_iterations <= 0: nothing was launched; the state is the initial one)
     return;
   }
-  const int depth = h->chunk_pairs;
+  const int depth = h->sw.chunk;
   long launched = 0;
   while (launched < max_launches) {
     const int prog = *reinterpret_cast<volatile int*>(h->h_progress);
@@ -437,11 +409,11 @@ void set_pass_mode(const ngicp* h, PassArgs& a) {
   if (h->prev_staged_fraction < 0.0 || h->prev_staged_fraction >= 0.12) a.mode |= 32;
 }
 
-// The pass kernel launch_pass picks on the launch-per-pass route honours LmHot::lin_unneeded: k_gicp_pass in its default, 4-waves, robust and
-// fused builds does; k_gicp_pass_st (NGICP_PASS_IMPL=1) and k_gicp_queue keep full passes, and NGICP_FULL_LAST_PASS=1 asks for them.
-// Sets the pass's mode bit and tells the solver, so that search_passes counts what ran and a K4-only pass leaves the launch order alone.
-void honour_lin_unneeded(const ngicp* h, LoopCtx& c) {
-  if (h->full_last_pass || pass_impl() != 0 || queue_switch()) return;
+// Where the switches leave the passes free to honour LmHot::lin_unneeded (route::honours_lin_unneeded: k_gicp_pass in its default, 4-waves,
+// robust and fused builds does, the other kernels keep full passes): sets the pass's mode bit and tells the solver, so that search_passes
+// counts what ran and a K4-only pass leaves the launch order alone.
+void allow_k4_only_passes(const ngicp* h, LoopCtx& c, const route::Facts& f) {
+  if (!route::honours_lin_unneeded(route::switches(), h->sw, f)) return;
   c.pa.mode |= 64;
   c.sa.pass_honours_word = 1;
 }
@@ -450,8 +422,7 @@ void honour_lin_unneeded(const ngicp* h, LoopCtx& c) {
 // are observed to share one) a contiguous eighth of the Morton-ordered groups: each XCD's L2 then sees an eighth of the target.
 // true: the order is installed and the solver leaves it alone.
 bool install_xcd_order(ngicp* h, LoopCtx& c) {
-  static const bool xcd_order = std::getenv("NGICP_ORDER") && std::string(std::getenv("NGICP_ORDER")) == "xcd";
-  if (!xcd_order) return false;
+  if (!route::switches().xcd_order) return false;
   const int nb = c.nblocks, per = (nb + 7) / 8;
   std::vector<int> ord((size_t)nb);
   std::vector<int> lists[8];
@@ -556,9 +527,8 @@ bool align_persistent(ngicp* h, const LoopCtx& c, Alignment& al, long max_passes
   pa.sa.pass_ticks = (h->profiling && max_passes <= kMaxTickPasses) ? h->pin_ticks : nullptr;
   const int grid = std::min(c.nblocks, h->persist_slots);
   void* kargs[] = {&pa};
-  static const bool coop = !(std::getenv("NGICP_PERSIST_COOP") && std::atoi(std::getenv("NGICP_PERSIST_COOP")) == 0);
   bool launched_ok = true;
-  if (coop) {
+  if (route::switches().persist_coop) {
     const hipError_t le = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&k_gicp_persist<2, 3>), dim3((unsigned)grid), dim3(256), kargs, 0, h->stream);
     if (le != hipSuccess) {  // (e.g. the runtime finds the grid too large to be resident: one launch per pass then)
       (void)hipGetLastError();
@@ -665,7 +635,7 @@ void launch_head(ngicp* h, const LoopCtx& c, long launched, hipEvent_t start, hi
 void launch_persist_one(ngicp* h, const LoopCtx& c, long launched, hipEvent_t start, hipEvent_t stop) {
   PassArgs pa = c.pa;
   pa.fused = 1;
-  pa.persist = std::atoi(std::getenv("NGICP_PERSIST_ONE")) == 2 ? 2 : 1;
+  pa.persist = route::switches().persist_one;
   pa.first_pass = (int)launched;
   pa.max_passes = 1;
   pa.sa = c.sa;
@@ -675,9 +645,9 @@ void launch_persist_one(ngicp* h, const LoopCtx& c, long launched, hipEvent_t st
   hipExtLaunchKernelGGL((k_gicp_persist<2, 3>), dim3((unsigned)std::min(c.nblocks, h->persist_slots)), dim3(256), 0, h->stream, start, stop, 0, pa);
 }
 
+// Refuse, prepare, choose the route (route::choose_route: the precedence is written down there), feed it.
 void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride) {
-  refuse_robust_under_switch(h, "ngicp_align");
-  refuse_prior_under_switch(h, "ngicp_align");
+  refuse_route(h, route::Caller::Align, "ngicp_align");
   Alignment al;
   reset_results(h);
   LoopCtx c;
@@ -687,50 +657,57 @@ void do_align(ngicp* h, const float guess[16], float* aligned, size_t out_stride
   // (the flag lives in a device word of its own: the solver sets it when an order is complete, the host only clears it when the
   // source index or the group count changed - it never has to read it back)
   if (!(h->order_src == h->src.dev.get() && h->order_groups == c.sa.nblocks)) HIP_TRY(hipMemsetAsync(h->order_flag.p, 0, 4 * sizeof(int), h->stream));  // (both flags)
-  const bool xcd_order = install_xcd_order(h, c);
+  route::Facts f = route_facts(h, route::Caller::Align, c.nblocks);
+  f.xcd_installed = install_xcd_order(h, c);
   set_pass_mode(h, c.pa);
-  static const bool persist_one = std::getenv("NGICP_PERSIST_ONE") != nullptr;
-  if (!h->persist && !h->head && !persist_one) honour_lin_unneeded(h, c);  // (k_gicp_persist and k_gicp_head keep full passes)
+  allow_k4_only_passes(h, c, f);
   if (const char* dbg = std::getenv("NGICP_DEBUG_MODE")) c.pa.mode |= (std::atoi(dbg) & (8 | 16));  // timing experiments only
   begin_alignment(h, al, guess, c.sa, c.pa.t_first);
   const DebugDumps dbg = debug_begin(h, c);
-  // NGICP_FUSED=1: one dispatch per iteration - the last block of the pass reduces and advances the optimiser (PassArgs::fused).
-  // Measured on MI355X (round 3, profiles/r03_fused_solver.txt): bit-identical results, but no faster than the separate launch (c3
-  // 46.3 vs 45.4 us per iteration, c5 70 vs 56): the write-through rows come back from memory, not from L2, through ONE CU
-  // (8.7 k cycles for 222 KB against 5.5 k in k_lm_solve), plus the acquire (~1.7 us) - so the default stays two launches.
-  static const bool fused_env = std::getenv("NGICP_FUSED") && std::atoi(std::getenv("NGICP_FUSED")) != 0;
-  if (fused_env && pass_impl() == 0) {
-    c.pa.fused = 1;
-    c.pa.sa = c.sa;
-    HIP_TRY(hipMemsetAsync(c.pa.ticket, 0, sizeof(int), h->stream));
-  }
-  const long max_p = max_passes(h->p);
-  // what the persistent and the head route both ask for: the default pass kernel, unfused, in the measured launch order, no per-block dumps
-  const bool plain = h->p.max_iter > 0 && pass_impl() == 0 && !c.pa.fused && !xcd_order && !dbg.span_path && !dbg.qstat_path && !c.sa.dbg_stamps;
-  const bool want_persist = h->persist && plain && h->persist_slots > 0 && !dbg.stamp_path && max_p + 1 <= kMaxPersistPasses;
-  const bool persist_done = want_persist && align_persistent(h, c, al, max_p);
-  const bool head_mode = h->head && plain && !persist_done && c.nblocks <= 2 * h->pass_slots;  // (grids of more rounds: the head's few microseconds are paid once per round)
-  if (persist_done) {
-    // (one launch has run the whole alignment)
-  } else if (head_mode) {
-    head_begin(h);
-    feed_alignment(h, al, max_p + 1, [&](long i, hipEvent_t start, hipEvent_t stop) { launch_head(h, c, i, start, stop); });
-    // (k_gicp_head: the head of launch `passes` ended the alignment and left the final state in the buffer it does not read; the handle's
-    // other entry points look for it in h->state)
-    if ((al.st.hot.passes + 1) & 1) HIP_TRY(hipMemcpyAsync(h->state.p, h->state_alt.p, sizeof(LmState), hipMemcpyDeviceToDevice, h->stream));
-  } else if (persist_one && h->persist_slots > 0 && max_p + 1 <= kMaxPersistPasses) {
-    feed_alignment(h, al, max_p, [&](long i, hipEvent_t start, hipEvent_t stop) { launch_persist_one(h, c, i, start, stop); });
-  } else {
-    // (diagnostic only) NGICP_DEBUG_SOLVE=N, N > 1: the stamps of the solver launch behind pass N - one that makes a trial, where the
-    // last launch of an alignment only ends it; 1: of the last working launch
-    static const long stamp_launch = std::getenv("NGICP_DEBUG_SOLVE") ? std::atol(std::getenv("NGICP_DEBUG_SOLVE")) : 0;
-    feed_alignment(h, al, max_p, [&](long i, hipEvent_t start, hipEvent_t stop) {
-      launch_pass(h, c.pa, c.nblocks, h->stream, start, stop);
-      if (c.pa.fused) return;
-      SolveArgs sa = c.sa;
-      if (stamp_launch > 1 && i + 1 != stamp_launch) sa.dbg_stamps = nullptr;
-      hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, sa);
-    });
+  f.dump_stamps = dbg.stamp_path != nullptr;
+  f.dump_span = dbg.span_path != nullptr;
+  f.dump_qstats = dbg.qstat_path != nullptr;
+  f.dump_solve = c.sa.dbg_stamps != nullptr;
+  const route::Choice pick = route::choose_route(route::switches(), h->sw, f);
+  const long max_p = f.max_passes;
+  const bool persist_done = pick.route == route::Route::Persist && align_persistent(h, c, al, max_p);
+  switch (persist_done ? route::Route::Persist : pick.fallback) {
+    case route::Route::Persist:  // (one launch has run the whole alignment)
+      break;
+    case route::Route::Head:
+      head_begin(h);
+      feed_alignment(h, al, max_p + 1, [&](long i, hipEvent_t start, hipEvent_t stop) { launch_head(h, c, i, start, stop); });
+      // (k_gicp_head: the head of launch `passes` ended the alignment and left the final state in the buffer it does not read; the handle's
+      // other entry points look for it in h->state)
+      if ((al.st.hot.passes + 1) & 1) HIP_TRY(hipMemcpyAsync(h->state.p, h->state_alt.p, sizeof(LmState), hipMemcpyDeviceToDevice, h->stream));
+      break;
+    case route::Route::PersistOne:
+      feed_alignment(h, al, max_p, [&](long i, hipEvent_t start, hipEvent_t stop) { launch_persist_one(h, c, i, start, stop); });
+      break;
+    case route::Route::Fused:
+      // NGICP_FUSED=1: one dispatch per iteration - the last block of the pass reduces and advances the optimiser (PassArgs::fused).
+      // Measured on MI355X (round 3, profiles/r03_fused_solver.txt): bit-identical results, but no faster than the separate launch (c3
+      // 46.3 vs 45.4 us per iteration, c5 70 vs 56): the write-through rows come back from memory, not from L2, through ONE CU
+      // (8.7 k cycles for 222 KB against 5.5 k in k_lm_solve), plus the acquire (~1.7 us) - so the default stays two launches.
+      c.pa.fused = 1;
+      c.pa.sa = c.sa;
+      HIP_TRY(hipMemsetAsync(c.pa.ticket, 0, sizeof(int), h->stream));
+      [[fallthrough]];
+    case route::Route::Default:
+    case route::Route::Staged:
+    case route::Route::Queue: {
+      // (diagnostic only) NGICP_DEBUG_SOLVE=N, N > 1: the stamps of the solver launch behind pass N - one that makes a trial, where the
+      // last launch of an alignment only ends it; 1: of the last working launch
+      const long stamp_launch = route::switches().debug_solve_launch;
+      feed_alignment(h, al, max_p, [&](long i, hipEvent_t start, hipEvent_t stop) {
+        launch_pass(h, c.pa, pick.variant, c.nblocks, h->stream, start, stop);
+        if (!route::row(pick.fallback).own_solver) return;
+        SolveArgs sa = c.sa;
+        if (stamp_launch > 1 && i + 1 != stamp_launch) sa.dbg_stamps = nullptr;
+        hipLaunchKernelGGL(k_lm_solve, dim3(1), dim3(kSolveThreads), 0, h->stream, sa);
+      });
+      break;
+    }
   }
   HIP_TRY(hipGetLastError());
   debug_end(h, c, dbg);
@@ -749,24 +726,27 @@ struct VoxelCtx {
   int nblocks;
 };
 
+// (neighbourhood, robust) -> the instantiation: f(integral_constant<int, K>, bool_constant<ROBUST>) for the K of DIRECT1 / 7 / 27
+template <class F>
+void with_voxel_variant(int nbr, bool robust, F&& f) {
+  auto with_k = [&](auto k) { robust ? f(k, std::true_type{}) : f(k, std::false_type{}); };
+  switch (nbr) {
+    case NGICP_VOX_DIRECT1: with_k(std::integral_constant<int, 1>{}); break;
+    case NGICP_VOX_DIRECT7: with_k(std::integral_constant<int, 7>{}); break;
+    case NGICP_VOX_DIRECT27: with_k(std::integral_constant<int, 27>{}); break;
+    default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
+  }
+}
+
 // the pass of the neighbourhood in c.pa.nbr: k_vgicp_pass for DIRECT1, k_vgicp_pass_n<K> for DIRECT7 / DIRECT27; the same grid
 void launch_voxel_pass(ngicp* h, const VoxelCtx& c, hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
   const dim3 grid((unsigned)c.nblocks), block(kVoxBlock);
-  if (c.pa.robust_kind != NGICP_ROBUST_NONE) {  // (the robust instantiations of the same three kernels)
-    switch (c.pa.nbr) {
-      case NGICP_VOX_DIRECT1: hipExtLaunchKernelGGL(k_vgicp_pass<true>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
-      case NGICP_VOX_DIRECT7: hipExtLaunchKernelGGL((k_vgicp_pass_n<7, true>), grid, block, 0, h->stream, start, stop, 0, c.pa); break;
-      case NGICP_VOX_DIRECT27: hipExtLaunchKernelGGL((k_vgicp_pass_n<27, true>), grid, block, 0, h->stream, start, stop, 0, c.pa); break;
-      default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
-    }
-    return;
-  }
-  switch (c.pa.nbr) {
-    case NGICP_VOX_DIRECT1: hipExtLaunchKernelGGL(k_vgicp_pass<>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
-    case NGICP_VOX_DIRECT7: hipExtLaunchKernelGGL(k_vgicp_pass_n<7>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
-    case NGICP_VOX_DIRECT27: hipExtLaunchKernelGGL(k_vgicp_pass_n<27>, grid, block, 0, h->stream, start, stop, 0, c.pa); break;
-    default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
-  }
+  with_voxel_variant(c.pa.nbr, c.pa.robust_kind != NGICP_ROBUST_NONE, [&](auto k, auto robust) {
+    constexpr int K = decltype(k)::value;
+    constexpr bool R = decltype(robust)::value;
+    if constexpr (K == 1) hipExtLaunchKernelGGL(k_vgicp_pass<R>, grid, block, 0, h->stream, start, stop, 0, c.pa);
+    else hipExtLaunchKernelGGL((k_vgicp_pass_n<K, R>), grid, block, 0, h->stream, start, stop, 0, c.pa);
+  });
 }
 
 // the fields of a voxelized pass that do not depend on the alignment (or the lane): the source, the map, the neighbourhood
@@ -821,7 +801,7 @@ void prepare_voxel_loop(ngicp* h, VoxelCtx& v) {
   v.nblocks = nblocks;
 }
 
-// do_align for a voxelized target: the same loop - state upload, (pass, solve) pairs fed `chunk_pairs` ahead of the solver's published
+// do_align for a voxelized target: the same loop - state upload, (pass, solve) pairs fed NGICP_CHUNK ahead of the solver's published
 // progress, the final state read from pinned memory - with k_vgicp_pass in k_gicp_pass's place.  None of the exact path's kernel-variant
 // switches applies.
 void do_align_voxel(ngicp* h, const float guess[16], float* aligned, size_t out_stride) {
@@ -846,13 +826,17 @@ struct HookCtx {
   bool vox;
   LoopCtx c;
   VoxelCtx vc;
+  route::Variant variant;  // the exact pass's kernel
 };
 void prepare_hook(ngicp* h, HookCtx& k) {
   k.vox = h->voxel_res > 0.0;
-  if (!k.vox && h->robust_kind != NGICP_ROBUST_NONE && pass_impl() == 1)  // (the one switch the hooks' pass obeys)
-    throw ArgError{NGICP_ERR_ARG, "linearize / compute_error: the robust kernel has no instantiation of the pass variant NGICP_PASS_IMPL=1 selects"};
-  if (k.vox) prepare_voxel_loop(h, k.vc);
-  else prepare_loop(h, k.c);
+  if (k.vox) {
+    prepare_voxel_loop(h, k.vc);
+    return;
+  }
+  refuse_route(h, route::Caller::Hook, "linearize / compute_error");
+  prepare_loop(h, k.c);
+  k.variant = pass_variant(h, route::Caller::Hook, k.c.nblocks);
 }
 void launch_hook(ngicp* h, HookCtx& k, int pass_mode, int solve_mode) {
   if (k.vox) {
@@ -860,7 +844,7 @@ void launch_hook(ngicp* h, HookCtx& k, int pass_mode, int solve_mode) {
     launch_voxel_pass(h, k.vc);
   } else {
     k.c.pa.mode = pass_mode;
-    launch_pass(h, k.c.pa, k.c.nblocks, h->stream);
+    launch_pass(h, k.c.pa, k.variant, k.c.nblocks, h->stream);
   }
   SolveArgs sa = k.vox ? k.vc.sa : k.c.sa;
   sa.mode = solve_mode;
@@ -887,7 +871,7 @@ void feed_batch(ngicp* h, int B, BatchLaunch& bl, long max_passes, std::vector<L
   BatchWs& w = h->batch;
   // The feeding discipline of do_align: (pass, solve) pairs kept `depth` ahead of the slowest live lane's progress word.  A lane that
   // reports done leaves the list; its blocks in the launches already enqueued return at their head.
-  const int depth = h->chunk_pairs;
+  const int depth = h->sw.chunk;
   const double t_loop = now_ms();
   unsigned long spins = 0;
   bool idle_seen = false;
@@ -1079,7 +1063,7 @@ void do_align_batch(ngicp* h, int B, const float* guesses, float* T_out, int* co
     r.sa_host[g] = sa;
   }
   run_batch(h, r, T_out, converged, nr_iterations, hessians, [&](const BatchLaunch& l, int n_live) {
-    const bool four = (long)nblocks * n_live > 2L * h->pass_slots;  // launch_pass's rule on the whole grid
+    const bool four = (long)nblocks * n_live > 2L * h->pass_slots;  // route::choose_route's rule on the whole grid
     if (four)
       hipLaunchKernelGGL((k_gicp_pass_batch<2, 4>), dim3((unsigned)nblocks, (unsigned)n_live), dim3(256), 0, h->stream, l);
     else
@@ -1130,12 +1114,8 @@ void do_align_voxel_batch(ngicp* h, int B, const float* guesses, float* T_out, i
   }
   run_batch(h, r, T_out, converged, nr_iterations, hessians, [&](const BatchLaunch& l, int n_live) {
     const dim3 grid((unsigned)nblocks, (unsigned)n_live), block(kVoxBlock);
-    switch ((int)K) {
-      case NGICP_VOX_DIRECT1: hipLaunchKernelGGL(k_vgicp_pass_batch<1>, grid, block, 0, h->stream, l); break;
-      case NGICP_VOX_DIRECT7: hipLaunchKernelGGL(k_vgicp_pass_batch<7>, grid, block, 0, h->stream, l); break;
-      case NGICP_VOX_DIRECT27: hipLaunchKernelGGL(k_vgicp_pass_batch<27>, grid, block, 0, h->stream, l); break;
-      default: throw ArgError{NGICP_ERR_STATE, "voxelized GICP: unknown neighbourhood"};
-    }
+    // (no robust build: the entry refuses the kernel)
+    with_voxel_variant((int)K, false, [&](auto k, auto) { hipLaunchKernelGGL(k_vgicp_pass_batch<decltype(k)::value>, grid, block, 0, h->stream, l); });
   });
 }
 

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "ngicp_route.h"
 #include "ngicp_pass.h"
 #include "ngicp_cloudops.h"
 #include "ngicp_filters.h"
@@ -53,7 +54,7 @@ int pick_blocks(size_t work_items, int per_block, int max_blocks) {
 // ring-1 (query, row) pairs with them.  Exact, a quarter fewer candidates (c3 68.4 -> 52.2 per query, c5 25.9 -> 23.8), 25 % fewer
 // ring-1 units per wave - and the launch exactly as long as before (c3 33.7 us either way, c5 41.3 -> 42.5: the second load per row):
 // the units it removes were served in parallel by lanes that would otherwise idle.  Off by default.
-// (read at ngicp_create: ngicp::cell_boxes; an index carries boxes when the handle that built it had the switch on)
+// (read at ngicp_create: ngicp::sw.cell_boxes; an index carries boxes when the handle that built it had the switch on)
 
 Grid make_grid(const float mn[3], const float mx[3], double h, int max_cells) {
   Grid g{};
@@ -181,7 +182,7 @@ std::shared_ptr<DeviceCloud> index_unsorted(ngicp* h, size_t n, const float mn[3
     // strided sample is not a thinned copy of the cloud, and the estimate settled on cells 2.4x too small - measured, withdrawn.)
     for (int it = 0; it < 4; ++it) {
       const double lam = (double)occ / (double)n;
-      const double ratio = h->target_occupancy / std::max(lam, 1.0);
+      const double ratio = h->sw.target_occ / std::max(lam, 1.0);
       if (ratio > 0.75 && ratio < 1.33) break;
       double scale = std::pow(ratio, 1.0 / 1.5);
       scale = std::min(4.0, std::max(0.25, scale));
@@ -198,7 +199,7 @@ std::shared_ptr<DeviceCloud> index_unsorted(ngicp* h, size_t n, const float mn[3
                      h->tmp.as<float4>());
   hipLaunchKernelGGL(k_cell_rank, dim3(pick_blocks(n, 256, 4096)), dim3(256), 0, h->stream, h->tmp.as<float4>(), ni, g, dc->cells(), dc->pts(),
                      dc->perm.as<int>());
-  dc->has_boxes = h->cell_boxes != 0;
+  dc->has_boxes = h->sw.cell_boxes != 0;
   if (dc->has_boxes) {
   dc->cell_box.ensure((size_t)(g.ncells + 2 * kCellPad) * sizeof(unsigned int));
   hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(2 * kCellPad), 0, h->stream, dc->cell_box.as<unsigned int>(), dc->cell_box.as<unsigned int>() + kCellPad + g.ncells, kCellPad, kCellBoxEmpty);
@@ -249,7 +250,7 @@ std::shared_ptr<DeviceCloud> index_unsorted(ngicp* h, size_t n, const float mn[3
     double next_h = (double)dc->grid.h;
     if (memo_hit) {
       HIP_TRY(hipStreamSynchronize(h->stream));
-      const double lam = (double)occ / (double)n, ratio = h->target_occupancy / std::max(lam, 1.0);
+      const double lam = (double)occ / (double)n, ratio = h->sw.target_occ / std::max(lam, 1.0);
       if (!(ratio > 0.75 && ratio < 1.33)) next_h = std::max(0.01, next_h * std::min(4.0, std::max(0.25, std::pow(ratio, 1.0 / 1.5))));
     }
     int slot = -1;
@@ -413,10 +414,6 @@ void download_transformed(ngicp* h, DeviceCloud& dc, const float T_colmajor[16],
 // ------------------------------------------------------------------------------------------
 // Voxelized GICP (ngicp_voxel.h): a mode the caller selects with ngicp_set_voxel_resolution
 // ------------------------------------------------------------------------------------------
-void refuse_if_voxelized(ngicp* h, const char* entry) {
-  if (h->voxel_res > 0.0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": not available with a voxelized target (ngicp_set_voxel_resolution(h, 0) selects exact GICP)"};
-}
-
 // The target, or its covariances, changed: the voxel map goes, and while the mode is on so do the correspondences, which are its voxel
 // numbers (ngicp_get_correspondences would read the next map's records with them).  Exact GICP's correspondences are left as they were.
 void drop_voxel_map(ngicp* h) {
@@ -638,15 +635,9 @@ int ngicp_create(int device, ngicp_t** out) {
       if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, device) != hipSuccess || !coop) h->persist_slots = 0;
     }
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_ticks), 2 * kMaxTickPasses * sizeof(unsigned long long), hipHostMallocDefault));
-    if (const char* s = std::getenv("NGICP_PERSIST")) h->persist = std::atoi(s);
-    if (const char* s = std::getenv("NGICP_HEAD")) h->head = std::atoi(s);
-    if (const char* s = std::getenv("NGICP_FULL_LAST_PASS")) h->full_last_pass = std::atoi(s);
-    if (const char* s = std::getenv("NGICP_SERIAL_STEP")) h->serial_step = std::atoi(s) != 0 ? 1 : 0;
-    if (const char* s = std::getenv("NGICP_CELL_BOXES")) h->cell_boxes = std::atoi(s);
-    if (const char* s = std::getenv("NGICP_TARGET_OCC")) h->target_occupancy = std::max(1.0, std::atof(s));
-    if (const char* s = std::getenv("NGICP_VOXEL")) h->voxel_size = std::atof(s);
-    if (const char* s = std::getenv("NGICP_CHUNK")) h->chunk_pairs = std::max(1, std::min(64, std::atoi(s)));
-    if (const char* s = std::getenv("NGICP_STAGE_GROW")) h->stage_grow = std::max(0, std::min(kStageMaxGrow, std::atoi(s)));
+    h->sw = route::read_handle_switches(route::from_environment, kStageMaxGrow);
+    h->persist = h->sw.persist;
+    h->voxel_size = h->sw.voxel;
     {
       HandleRegistry& r = registry();
       std::lock_guard<std::mutex> lock(r.m);
@@ -884,8 +875,7 @@ int ngicp_align(ngicp_t* h, const float guess[16], float T_out[16], int* converg
 
 int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_align_batch");
-    refuse_if_robust(h, "ngicp_align_batch");
+    refuse_for(h, route::Entry::AlignBatch);
     check_batch_args("ngicp_align_batch", n_guesses, guesses, T_out, converged, nr_iterations);
     do_align_batch(h, (int)n_guesses, guesses, T_out, converged, nr_iterations, final_hessians);
   });
@@ -894,7 +884,7 @@ int ngicp_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float*
 int ngicp_voxel_align_batch(ngicp_t* h, size_t n_guesses, const float* guesses, float* T_out, int* converged, int* nr_iterations, double* final_hessians) {
   return guarded(h, [&] {
     if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, "ngicp_voxel_align_batch: the voxelized mode is off (ngicp_set_voxel_resolution)"};
-    refuse_if_robust(h, "ngicp_voxel_align_batch");
+    refuse_for(h, route::Entry::VoxelAlignBatch);
     check_batch_args("ngicp_voxel_align_batch", n_guesses, guesses, T_out, converged, nr_iterations);
     do_align_voxel_batch(h, (int)n_guesses, guesses, T_out, converged, nr_iterations, final_hessians);
   });
@@ -1541,14 +1531,12 @@ int ngicp_set_profiling(ngicp_t* h, int on) {
 // the extra kShardLag passes after the end are no-ops (both kernels return at once when the state says done).
 int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_sharded_begin");
-    refuse_if_robust(h, "ngicp_sharded_begin");
-    refuse_if_prior(h, "ngicp_sharded_begin");
+    refuse_for(h, route::Entry::ShardedBegin);
     h->shard_ctx.reset(new LoopCtx);
     LoopCtx& c = *h->shard_ctx;
     prepare_loop(h, c);
     set_pass_mode(h, c.pa);
-    honour_lin_unneeded(h, c);  // (every rank steps the same lm_step on the same reduced sums: the word is the same on all of them)
+    allow_k4_only_passes(h, c, route_facts(h, route::Caller::Sharded));  // (every rank steps the same lm_step on the same reduced sums: the word is the same on all of them)
     upload_initial_state(h, guess ? guess : kIdentity16);
     HIP_TRY(hipStreamSynchronize(h->stream));  // once per alignment: the caller may step on a stream of its own
     for (int i = 0; i < kShardSlots; ++i) h->h_shard_done[i] = 0;
@@ -1560,14 +1548,12 @@ int ngicp_sharded_begin(ngicp_t* h, const float guess[16]) {
 
 int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_sharded_pass");
-    refuse_if_robust(h, "ngicp_sharded_pass");
-    refuse_if_prior(h, "ngicp_sharded_pass");
+    refuse_for(h, route::Entry::ShardedPass);
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
     LoopCtx& c = *h->shard_ctx;
-    launch_pass(h, c.pa, c.nblocks, s);
+    launch_pass(h, c.pa, pass_variant(h, route::Caller::Sharded, c.nblocks), c.nblocks, s);
     SolveArgs sa = c.sa;
     sa.mode = 3;  // reduce only: this rank's 32 sums, for the caller's all-reduce
     sa.sums_out = sums32_dev;
@@ -1579,9 +1565,7 @@ int ngicp_sharded_pass(ngicp_t* h, double* sums32_dev, void* stream_or_null) {
 
 int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_null, int* done) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_sharded_step");
-    refuse_if_robust(h, "ngicp_sharded_step");
-    refuse_if_prior(h, "ngicp_sharded_step");
+    refuse_for(h, route::Entry::ShardedStep);
     if (!h->sharded_active || !h->shard_ctx) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     if (!sums32_dev) throw ArgError{NGICP_ERR_ARG, "null sums buffer"};
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : h->stream;
@@ -1611,9 +1595,7 @@ int ngicp_sharded_step(ngicp_t* h, const double* sums32_dev, void* stream_or_nul
 
 int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_iterations, double final_hessian[36]) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_sharded_finish");
-    refuse_if_robust(h, "ngicp_sharded_finish");
-    refuse_if_prior(h, "ngicp_sharded_finish");
+    refuse_for(h, route::Entry::ShardedFinish);
     if (!h->sharded_active) throw ArgError{NGICP_ERR_STATE, "ngicp_sharded_begin not called"};
     hipStream_t s = h->shard_stream ? h->shard_stream : h->stream;  // the steps were enqueued there
     HIP_TRY(hipMemcpyAsync(&h->pin_state[1], h->state.p, sizeof(LmState), hipMemcpyDeviceToHost, s));
@@ -1632,7 +1614,7 @@ int ngicp_sharded_finish(ngicp_t* h, float T_out[16], int* converged, int* nr_it
 // ---- K1 sharded over ranks: every rank computes a block of the packed covariance array, the caller all-gathers ----
 int ngicp_covs_shard_begin(ngicp_t* h, int which, double** covs6_dev, size_t* n_points) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_covs_shard_begin");
+    refuse_for(h, route::Entry::CovsShardBegin);
     if ((which != 0 && which != 1) || !covs6_dev || !n_points) throw ArgError{NGICP_ERR_ARG, "bad argument"};
     Slot& slot = which ? h->tgt : h->src;
     ensure_slot_ready(h, slot, which ? "target" : "source");
@@ -1647,7 +1629,7 @@ int ngicp_covs_shard_begin(ngicp_t* h, int which, double** covs6_dev, size_t* n_
 }
 int ngicp_covs_shard_compute(ngicp_t* h, int which, size_t lo, size_t hi, void* stream_or_null) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_covs_shard_compute");
+    refuse_for(h, route::Entry::CovsShardCompute);
     if (which != 0 && which != 1) throw ArgError{NGICP_ERR_ARG, "bad argument"};
     CovSet& cs = h->shard_covs[which];
     Slot& slot = which ? h->tgt : h->src;
@@ -1659,7 +1641,7 @@ int ngicp_covs_shard_compute(ngicp_t* h, int which, size_t lo, size_t hi, void* 
 }
 int ngicp_covs_shard_commit(ngicp_t* h, int which) {
   return guarded(h, [&] {
-    refuse_if_voxelized(h, "ngicp_covs_shard_commit");
+    refuse_for(h, route::Entry::CovsShardCommit);
     if (which != 0 && which != 1) throw ArgError{NGICP_ERR_ARG, "bad argument"};
     CovSet& cs = h->shard_covs[which];
     Slot& slot = which ? h->tgt : h->src;

@@ -225,7 +225,7 @@ struct VoxelMapView {
 };
 
 struct LoopCtx;  // the per-alignment launch arguments (defined with the registration loop)
-constexpr int kMaxPersistPasses = 2048;  // alignments with more possible passes than this take one launch per pass (the ring of views is 512 bytes per pass)
+using route::kMaxPersistPasses;
 constexpr int kMaxTickPasses = 1024;  // passes of an alignment whose timestamps the persistent kernel records when profiling is on
 constexpr int kShardSlots = 4, kShardLag = 2;  // point-sharded stepping: the `done` word of step k is read at step k + kShardLag
 constexpr float kIdentity16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -279,12 +279,10 @@ struct ngicp {
   bool cov_timing_pending = false;
   std::string err;
   Params p;
-  double voxel_size = 0.0;  // 0 = auto
-  double target_occupancy = 24.0;  // mean points a random point sees in its own cell; tuned on MI355X (c2/c3/c5 workloads)
+  route::HandleSwitches sw;  // the NGICP_* switches read in ngicp_create (ngicp_route.h); never written afterwards
+  double voxel_size = 0.0;  // the grid's voxel edge, 0 = auto: sw.voxel until ngicp_set_tuning writes it
   int host_wait = 0;        // 0: poll without giving the core up, 1: sched_yield between polls (ngicp_set_host_wait)
   CovSet shard_covs[2];     // covariance sets being computed in blocks by several ranks (ngicp_covs_shard_*), uncommitted
-  int chunk_pairs = 3;      // (pass, solve) pairs kept in flight ahead of the solver's published progress (env NGICP_CHUNK)
-  int stage_grow = 6;       // upper limit of rings served from the LDS stage
   // {cloud size, auto voxel edge} of recent builds, one entry per size class (a factor of two around the size): a DLO pipeline has three
   // or four - the scan, the voxel-filtered keyframe made from it, the submap - and each would otherwise pay the refinement passes again
   std::pair<size_t, double> voxel_memo[4] = {{0, 0.0}, {0, 0.0}, {0, 0.0}, {0, 0.0}};
@@ -300,17 +298,11 @@ struct ngicp {
   int pass_slots = 768;  // blocks of the 3-waves-per-SIMD pass kernel resident on this device at once
   int persist_slots = 0; // blocks of the persistent pass kernel resident at once (its grid), 0: not available
   int queue_slots[2] = {768, 1024};  // blocks of k_gicp_queue<2, 3> / <2, 4> resident at once
-  int persist = 0;       // env NGICP_PERSIST=1: ONE launch per alignment (k_gicp_persist).  Exact and complete, but measured no faster than one
-                         // launch per pass: off by default
+  int persist = 0;       // sw.persist until a persistent launch fails or gives up (align_persistent clears it): ONE launch per alignment
+                         // (k_gicp_persist).  Exact and complete, but measured no faster than one launch per pass: off by default
   int order_sel = 0;     // which of the two launch-order buffers (and flag words) the next alignment reads
   DevBuf grp_order_alt;  // the second order buffer: the persistent kernel's solver builds the NEXT alignment's order there
   DevBuf gen_lines;      // the persistent kernel's release word, kGenLines copies (PassArgs::gen)
-  int cell_boxes = 0;    // env NGICP_CELL_BOXES=1: per-cell (y,z) extents built with every index and used by the pass (see "Index build")
-  int head = 0;          // env NGICP_HEAD=1: k_gicp_head - no solver launch, every block steps the optimiser at its head
-  int full_last_pass = 0;  // env NGICP_FULL_LAST_PASS=1 (diagnostic): every pass searches and linearises, also where LmHot::lin_unneeded says the
-                           // result can never be adopted; changes no result
-  int serial_step = 0;   // env NGICP_SERIAL_STEP=1 (A/B timing, tests): the solver steps on one lane (lm_step) instead of on the wave
-                         // (lm_step_wave); changes no result
   DevBuf state_alt;      // k_gicp_head: the second state buffer (a launch's solver block writes the one its blocks are not reading)
   DevBuf head_ws;        // k_gicp_head: {done flag (64 B), subset tickets (128 B), subset rows of even / odd launches (2 x 8 KB)}
   unsigned long long* pin_ticks = nullptr;  // pinned [2 * kMaxTickPasses]: per pass {last block arrived, next pass released} (profiling)

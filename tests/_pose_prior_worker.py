@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_pose_prior.py: an exact-route align with a pose prior set under the process-wide kernel-variant switch
-its environment carries (NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_PERSIST, NGICP_HEAD, NGICP_SERIAL_STEP: read once per process,
+its environment carries (NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_PERSIST, NGICP_HEAD, NGICP_SERIAL_STEP: read once per process or per handle by the two readers of ngicp_route.h,
 so each needs a process of its own - tests/_robust_worker.py's pattern).  The file named on the command line holds what the DEFAULT
 route returned for the same inputs with the prior (T, trace, H) and without it (T0).  Either the align is refused with NGICP_ERR_ARG
 naming the pose prior - then the setting must stay and, the prior cleared, the align under the switch must equal T0 - and the last

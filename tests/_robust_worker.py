@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_robust.py: an exact-route align with a robust kernel set under the process-wide kernel-variant switch
-its environment carries (NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_PERSIST, NGICP_HEAD: read once per process, so each needs a
+its environment carries (NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_PERSIST, NGICP_HEAD: read once per process or per handle by the two readers of ngicp_route.h, so each needs a
 process of its own - tests/_variant_worker.py's pattern).  The align must be refused with NGICP_ERR_ARG naming the robust kernel, the
 setting must stay, and with NONE the align under the same switch must equal the one before the kernel was set, bit for bit.  A failed
 check raises (non-zero exit); on success the last line is RESULT refused.

@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_solver_step.py: small alignments under the switches its environment carries (NGICP_SERIAL_STEP is
-read at ngicp_create, NGICP_FUSED once per process; the parent runs this with and without NGICP_SERIAL_STEP=1 and compares the outputs).
+read at ngicp_create by ngicp_route.h's read_handle_switches, NGICP_FUSED once per process by its read_process_switches; the parent runs this with and without NGICP_SERIAL_STEP=1 and compares the outputs).
 The last line is RESULT {json}: per scenario the results as hex strings (bit-exact comparison) and the counters that measure no time.
 usage: python tests/_solver_step_worker.py
 """

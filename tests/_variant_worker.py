@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_variants.py: the per-pass oracle checks of _pass_check.py under the process-wide kernel variant
-its environment selects (NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_ORDER, NGICP_PASS_WPS: read once per process, so each
+its environment selects (NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_ORDER, NGICP_PASS_WPS: read once per process by ngicp_route.h's read_process_switches, so each
 variant needs a process of its own).  A failed check raises (non-zero exit); on success the last line is RESULT {json}.
 usage: python tests/_variant_worker.py <case> [<case> ...]   (cases: _pass_check.make_rig's names)
 """

@@ -1,7 +1,7 @@
 """The process-wide kernel variants, each in a child process of its own, under the per-pass oracle check (-m gpu).
 
-NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_ORDER and NGICP_PASS_WPS are read once per process (ngicp_api.hip: pass_impl(),
-launch_pass(), do_align's statics), so monkeypatch cannot reach them: every variant runs tests/_variant_worker.py in a fresh child, one
+NGICP_PASS_IMPL, NGICP_FUSED, NGICP_QUEUE, NGICP_ORDER and NGICP_PASS_WPS are read once per process (csrc/ngicp_route.h:
+read_process_switches, behind switches()'s static), so monkeypatch cannot reach them: every variant runs tests/_variant_worker.py in a fresh child, one
 at a time, on the 10k scan-to-scan cases, two adversarial shapes and c3 FIXED20.  Without NGICP_PASS_WPS the grid size picks the
 3- or 4-waves-per-SIMD build (nblocks > 2 * pass_slots), so a workload meets only one of them: each variant also runs with each build
 forced.  Left out on purpose: NGICP_PERSIST_COOP=0 and NGICP_PERSIST_ONE (timing only; their blocks wait for each other without a
