@@ -15,7 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libngicp_hip.so")
 SOURCES = ["ngicp_api.hip", "ngicp_filters.hip"]
-HEADERS = ["ngicp_pass_group.inc", "ngicp_math.h", "ngicp_grid.h", "ngicp_knn.h", "ngicp_pass.h", "ngicp_pass_st.h", "ngicp_cloudops.h", "ngicp_filters.h", "ngicp_query.h", "ngicp_range.h", "ngicp_batch.h", "ngicp_voxel.h", "ngicp_voxel_batch.h", "ngicp_voxel_roll.h", "ngicp_robust.h", "ngicp_route.h", "ngicp_handle.h", "ngicp_voxelmap.h", "ngicp_rollmap.h", "ngicp_align.h", os.path.join("..", "..", "include", "ngicp.h")]
+PUBLIC_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "ngicp.h"))
+DEP_SUFFIXES = (".h", ".inc", ".hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wno-unused-function"]
 
 
@@ -26,12 +27,18 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
+def dependencies() -> list[str]:
+    """Every file the library is compiled from: what is on disk under csrc/ (a header nobody listed cannot leave a stale library
+    behind), the public header, and this file for its flags."""
+    found = [os.path.join(d, f) for d, _, files in os.walk(CSRC) for f in files if f.endswith(DEP_SUFFIXES)]
+    return sorted(found) + [PUBLIC_HEADER, os.path.abspath(__file__)]
+
+
 def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in dependencies())
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | None = None) -> str:

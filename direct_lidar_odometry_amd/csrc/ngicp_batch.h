@@ -33,7 +33,7 @@ typedef const BatchLaunch __attribute__((address_space(4))) KernelBatchLaunch;
 // One group of one pass of one lane: the prologue of persist_group_body<.., RING = false> (arguments through the constant address space,
 // the pose from the state itself, rows stored plainly: the solver is a launch of its own) with k_gicp_pass's scalar wave number, then the
 // body every pass kernel includes.  Inlined into the kernel: no call, the search keeps its registers.  (The pose is read here and not
-// with load_pose, ngicp_pass.h: with it k_gicp_pass_batch's code came out different, six instructions shorter, and the exact route's
+// with load_pose, ngicp_lm.h: with it k_gicp_pass_batch's code came out different, six instructions shorter, and the exact route's
 // code objects are kept as they are.)
 #define NG_STAMP(k) \
   do {              \

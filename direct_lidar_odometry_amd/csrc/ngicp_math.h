@@ -23,7 +23,7 @@ NG_HD void pose_identity(Pose& p) {
 }
 
 // The element expressions of pose_mul and ldlt6_solve, ONE definition each: the serial routines below and the solver's wave-level step
-// (lm_step_wave, ngicp_pass.h: one element per lane) both take them from here, so that operand order and the compiler's contraction
+// (lm_step_wave, ngicp_lm.h: one element per lane) both take them from here, so that operand order and the compiler's contraction
 // decisions cannot differ between the two.
 NG_HD double pose_mul_r(double a0, double a1, double a2, double b0, double b1, double b2) { return a0 * b0 + a1 * b1 + a2 * b2; }
 NG_HD double pose_mul_t(double a0, double a1, double a2, double b0, double b1, double b2, double t) { return a0 * b0 + a1 * b1 + a2 * b2 + t; }
@@ -261,7 +261,7 @@ NG_HD double skew_elem(const int k, const int i, const double x, const double y,
   return ((i - k + 3) % 3 == 1) ? -m : m;
 }
 // The element expressions of the prior's row, ONE definition each: prior_row below runs them in a loop, the solver (lm_solve_body,
-// ngicp_pass.h) one element per lane.
+// ngicp_solve.h) one element per lane.
 NG_HD double so3_jinv_elem(const int k, const int i, const double px, const double py, const double pz, const double theta_sq, const double c) {
   const double d = k == i ? 1.0 : 0.0;
   return (d - 0.5 * skew_elem(k, i, px, py, pz)) + c * (sel3(k, px, py, pz) * sel3(i, px, py, pz) - d * theta_sq);

@@ -5,7 +5,7 @@
 // Expects in scope: a (PassArgs, or the same seen through the constant address space), g (Grid), group, lane, wave, sub, grp, S, lds,
 // do_err, do_lin, R, t, Tf, tpt_old / tpt_new, mahal_old / mahal_new, wave_total, ncand, nvalid, nstaged, t_start, the constants B, kWin,
 // kSideStep, FUSED, the macros NG_STAMP and NG_HAVE_LIN.  NG_ROBUST (a constant expression; false where the includer defines none): the
-// K4 leg and the K3 tail weight their term by the robust kernel in a.robust_kind / robust_c / robust_c2 (robust_term, ngicp_pass.h).
+// K4 leg and the K3 tail weight their term by the robust kernel in a.robust_kind / robust_c / robust_c2 (robust_term, ngicp_terms.h).
 #ifndef NG_ROBUST
 #define NG_ROBUST false
 #define NG_ROBUST_DEFAULTED

@@ -2,7 +2,7 @@
 // last linearisation - ngicp_compute_error's contract, term by term instead of summed (include/ngicp.h, "robust kernel").
 //
 // A thread serves one source point and its K slots (K = 1: the exact route and DIRECT1).  Per term it writes s = e^T M e (err_term's
-// order of operations, as the passes' error leg) and w(s) (robust_term, ngicp_pass.h: the passes' own definition); where the slot has no
+// order of operations, as the passes' error leg) and w(s) (robust_term, ngicp_terms.h: the passes' own definition); where the slot has no
 // correspondence, s = -1 and w = 0.  Rows are in ORIGINAL source order, (n_src, K) doubles each:
 //   exact      points come in the pass's query order (qpts, w = sorted source position); correspondence and target point from tpt,
 //              the matrix from mahal[i]; the row is that of ngicp_get_correspondences (k_corr_to_original)

@@ -31,8 +31,8 @@
 //                                 k_vgicp_pass_batch<K> (ngicp_voxel_batch.h) runs the same bodies on a lane's record.
 //   shared pieces, each defined once   voxel_cell / voxel_pack (-> voxel_key), voxel_probe_from (-> voxel_lookup, and the neighbourhoods'
 //                                 probe continuation), voxel_segment_sums and voxel_table_insert (the map's fill kernels), voxel_pass_begin
-//                                 (the single kernels' head), voxel_block_row (a pass block's row); from ngicp_pass.h: load_pose,
-//                                 transform_point_rowmajor_f, lin_terms / err_term (the exact pass's K3 and its error leg).
+//                                 (the single kernels' head), voxel_block_row (a pass block's row); through ngicp_pass.h: load_pose (ngicp_lm.h),
+//                                 transform_point_rowmajor_f (ngicp_search.h), lin_terms / err_term (ngicp_terms.h: the exact pass's K3 and its error leg).
 //   merged voxel map              (a setting, off by default) the map of a submap from sums its keyframes carry:
 //                                 k_voxel_part_fill (one keyframe's per-voxel sums, no division), k_voxel_part_gather (the parts' keys in
 //                                 the order of the id list, value = global record position), the same stable sort and numbering, and
@@ -266,7 +266,7 @@ struct VoxelPassArgs {
   unsigned long long* t_first;  // device word: stamped by the first pass of an alignment (block 0), or null
   int nbr;                  // slots per source point (1, 7 or 27); k_vgicp_pass reads neither this nor slot_stride
   int slot_stride;          // k_vgicp_pass_n: corr / mahal are slot-major, slot s of point i at [s * slot_stride + i]
-  // robust kernel (robust_term, ngicp_pass.h): read by the ROBUST instantiations only, which the host launches exactly when kind != NONE
+  // robust kernel (robust_term, ngicp_terms.h): read by the ROBUST instantiations only, which the host launches exactly when kind != NONE
   int robust_kind;
   double robust_c, robust_c2;
 };

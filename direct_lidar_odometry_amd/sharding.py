@@ -31,7 +31,7 @@ def shard_bounds(n: int, world_size: int, rank: int) -> tuple[int, int]:
 
 
 def tri21(r: int, c: int) -> int:
-    """Index of H(r,c), r <= c, in the packed upper triangle (csrc/ngicp_pass.h tri21)."""
+    """Index of H(r,c), r <= c, in the packed upper triangle (csrc/ngicp_lm.h tri21)."""
     return r * 6 - (r * (r - 1)) // 2 + (c - r)
 
 

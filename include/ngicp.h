@@ -329,7 +329,7 @@ int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vo
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
 
-/* --- robust kernel: Huber, Cauchy or Geman-McClure on every term (no counterpart in the reference; csrc/ngicp_pass.h robust_term,
+/* --- robust kernel: Huber, Cauchy or Geman-McClure on every term (no counterpart in the reference; csrc/ngicp_terms.h robust_term,
  *     DESIGN.md 4.13) -----------------------------------------------------------------------------------------------------------------
  * The kernels and their names are this project's own definition; no fidelity to another library is claimed.
  * A TERM is one (source point, correspondence) pair: the exact route and DIRECT1 have one per source point, DIRECT7 / DIRECT27 up to K.
@@ -376,7 +376,7 @@ int ngicp_get_robust_kernel(const ngicp_t* h, int* kind, double* width);
 int ngicp_robust_terms(ngicp_t* h, const double T_colmajor[16], double* s_out, double* w_out, size_t capacity_doubles, int* K_out);
 
 /* --- pose prior: a Gaussian prior on the pose, applied in the solver (no counterpart in the reference; csrc/ngicp_math.h prior_row,
- * csrc/ngicp_pass.h lm_solve_body; restated in numpy by tests/_prior_model.py) -----------------------------------------
+ * csrc/ngicp_solve.h lm_solve_body; restated in numpy by tests/_prior_model.py) -----------------------------------------
  * With a prior set, every route minimises  y(T) = y_data(T) + r(T)^T L r(T)  - the scaling of sum e^T M e, no factor 1/2.
  *   prior      a pose T_p = (R_p, t_p) in double and a symmetric 6x6 information matrix L, rotation first, then translation (H's
  *              order); units rad^-2, m^-2 and their mixtures.

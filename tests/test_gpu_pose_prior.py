@@ -1,4 +1,4 @@
-"""The pose prior on the GPU (ngicp_set_pose_prior; csrc/ngicp_math.h prior_row, csrc/ngicp_pass.h lm_solve_body) against the numpy model
+"""The pose prior on the GPU (ngicp_set_pose_prior; csrc/ngicp_math.h prior_row, csrc/ngicp_solve.h lm_solve_body) against the numpy model
 of its definition (tests/_prior_model.py, which proves itself in test_prior_model_cpu.py): the two self-tests, the hooks on every
 route, whole alignments pass by pass, neutrality, the batch entries, the robust kernel together with the prior, the corridor, and
 what is refused."""

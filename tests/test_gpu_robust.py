@@ -1,4 +1,4 @@
-"""The robust kernels on the GPU (ngicp_set_robust_kernel; csrc/ngicp_pass.h robust_term, csrc/ngicp_robust.h) against the numpy model
+"""The robust kernels on the GPU (ngicp_set_robust_kernel; csrc/ngicp_terms.h robust_term, csrc/ngicp_robust.h) against the numpy model
 of their definition (tests/_robust_model.py, which proves itself in test_robust_model_cpu.py): the hooks on every route, whole
 alignments pass by pass, the bit anchors to the code without a kernel, ngicp_robust_terms, the outlier scenario, the rolling map, and
 what is refused."""

@@ -1,5 +1,5 @@
 """K4-only passes (-m gpu): a pass whose linearisation can never be adopted evaluates only the trial's error (DESIGN.md 4.1,
-LmHot::lin_unneeded, ngicp_pass.h set_lin_unneeded), and nothing an alignment leaves may tell.
+LmHot::lin_unneeded, ngicp_lm.h set_lin_unneeded), and nothing an alignment leaves may tell.
 
 Every scenario runs in two fresh child processes (tests/_terminal_pass_worker.py; the switch is read at ngicp_create), one as built and
 one with NGICP_FULL_LAST_PASS=1, which makes every pass search and linearise as before.  Bit-equal between the two: the final
@@ -160,7 +160,7 @@ def test_sharded_loop(sharded_runs):
 
 
 def _solver_order(costs):
-    """k_lm_solve's launch order of the groups with these costs (ngicp_pass.h lm_solve_body): sixteen classes relative to the slowest
+    """k_lm_solve's launch order of the groups with these costs (ngicp_solve.h build_launch_order): sixteen classes relative to the slowest
     group, heaviest class first, ascending group index inside a class; float32 arithmetic as on the device."""
     c = np.asarray(costs, np.int32)
     to_class = np.float32(16.0) / (np.float32(max(1, int(c.max()))) + np.float32(1.0))

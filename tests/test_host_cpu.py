@@ -51,6 +51,26 @@ def test_product_package_never_imports_oracle():
                 assert "import oracle" not in src and "from oracle" not in src and "liboracle" not in src, f
 
 
+def test_build_depends_on_every_source_file():
+    """A header the build does not know of leaves a stale library behind when it changes: the dependency set is what is on disk
+    under csrc/, and every project header a csrc/ file includes exists there."""
+    from direct_lidar_odometry_amd import build
+    deps = {os.path.realpath(d) for d in build.dependencies()}
+    on_disk = [os.path.join(dp, f) for dp, _, fs in os.walk(build.CSRC) for f in fs]
+    assert len(on_disk) >= 20
+    for path in on_disk:
+        assert os.path.realpath(path) in deps, f"{path} is not a dependency of the build"
+    assert os.path.realpath(os.path.join(ROOT, "include", "ngicp.h")) in deps
+    for s in build.SOURCES:
+        assert os.path.realpath(os.path.join(build.CSRC, s)) in deps
+    included = 0
+    for path in on_disk:
+        for name in re.findall(r'^\s*#\s*include\s+"(ngicp_\w+\.(?:h|inc))"', open(path).read(), flags=re.M):
+            assert os.path.isfile(os.path.join(build.CSRC, name)), f"{path} includes {name}, which csrc/ does not hold"
+            included += 1
+    assert included >= 20
+
+
 def test_shard_bounds_and_packing():
     from direct_lidar_odometry_amd import sharding as sh
     for n in (0, 1, 7, 100_000, 250_001):

@@ -1,4 +1,4 @@
-"""The rule behind K4-only passes (ngicp_pass.h set_lin_unneeded), pinned on oracle/numpy_model.py's LM loop (no GPU).
+"""The rule behind K4-only passes (ngicp_lm.h set_lin_unneeded), pinned on oracle/numpy_model.py's LM loop (no GPU).
 
 A trial is flagged when its step already meets the convergence test, or when it belongs to the last outer iteration
 (it + 1 >= max_iterations).  The claim: the linearisation at a flagged trial's pose is never used - in the model's sequence of events every
