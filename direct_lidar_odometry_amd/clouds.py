@@ -138,6 +138,59 @@ def to_xyzi(pts: np.ndarray) -> np.ndarray:
     return out
 
 
+# ---- motion distortion of a sweep (the inverse of the engine's deskew: include/ngicp.h "motion deskew") ----
+def sweep_times(n: int, rings: int = 16, sweep_s: float = 0.1, t0: float = 0.0) -> np.ndarray:
+    """Per-point times of a spinning sweep for the azimuth-major scans above: every point of azimuth column c = i // rings is taken
+    at t0 + sweep_s * c / cols (float64 seconds, ascending; the sweep covers [t0, t0 + sweep_s))."""
+    cols = max(1, -(-n // rings))
+    return t0 + sweep_s * ((np.arange(n) // rings).astype(np.float64) / cols)
+
+
+def _rotvec_to_matrix(w: np.ndarray) -> np.ndarray:
+    """Rodrigues: (N, 3) rotation vectors -> (N, 3, 3)."""
+    th = np.linalg.norm(w, axis=1)
+    small = th < 1e-8
+    safe = np.where(small, 1.0, th)
+    a = np.where(small, 1.0 - th * th / 6.0, np.sin(safe) / safe)
+    b = np.where(small, 0.5 - th * th / 24.0, (1.0 - np.cos(safe)) / (safe * safe))
+    K = np.zeros((len(w), 3, 3))
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 2] = -w[:, 2], w[:, 1], -w[:, 0]
+    K[:, 1, 0], K[:, 2, 0], K[:, 2, 1] = w[:, 2], -w[:, 1], w[:, 0]
+    return np.eye(3) + a[:, None, None] * K + b[:, None, None] * (K @ K)
+
+
+def _matrix_to_rotvec(R: np.ndarray) -> np.ndarray:
+    """(3, 3) rotation (angle < pi) -> rotation vector."""
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = float(np.linalg.norm(v)), 0.5 * (float(np.trace(R)) - 1.0)
+    return v if s < 1e-12 else v * (math.atan2(s, c) / s)
+
+
+def trajectory_poses(times: np.ndarray, pose_times: np.ndarray, poses: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """The trajectory at each time: geodesic in rotation and linear in translation between consecutive poses, held at pose 0 before
+    pose_times[0] and at the last pose from pose_times[-1] on.  Returns (R (N, 3, 3), t (N, 3)), float64."""
+    s = np.asarray(times, np.float64)
+    tau = np.asarray(pose_times, np.float64)
+    P = np.asarray(poses, np.float64)
+    k = np.clip(np.searchsorted(tau, s, side="right") - 1, 0, len(tau) - 2)
+    alpha = np.clip((s - tau[k]) / (tau[k + 1] - tau[k]), 0.0, 1.0)
+    phi = np.stack([_matrix_to_rotvec(P[j, :3, :3].T @ P[j + 1, :3, :3]) for j in range(len(tau) - 1)])
+    R = P[k, :3, :3] @ _rotvec_to_matrix(alpha[:, None] * phi[k])
+    t = P[k, :3, 3] + alpha[:, None] * (P[k + 1, :3, 3] - P[k, :3, 3])
+    return R, t
+
+
+def skew_scan(points: np.ndarray, times: np.ndarray, pose_times: np.ndarray, poses: np.ndarray, T_ref: np.ndarray | None = None) -> np.ndarray:
+    """The motion-distorted sweep of an undistorted scan: `points` (N, 3) are in T_ref's frame (None: identity); point i was taken
+    at times[i] from the pose T(times[i]) of the trajectory, so the sensor reported p_raw = T(s)^-1 T_ref p.  numpy float64,
+    rounded once to float32.  Deskewing the result with the same trajectory and T_ref returns `points`."""
+    p = np.asarray(points, np.float64)[:, :3]
+    Tr = np.eye(4) if T_ref is None else np.asarray(T_ref, np.float64)
+    R, t = trajectory_poses(times, pose_times, poses)
+    world = p @ Tr[:3, :3].T + Tr[:3, 3]
+    return np.ascontiguousarray(np.einsum("nji,nj->ni", R, world - t), dtype=np.float32)
+
+
 @dataclasses.dataclass
 class Workload:
     name: str

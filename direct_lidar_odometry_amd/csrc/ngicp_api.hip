@@ -1942,6 +1942,8 @@ int ngicp_measure_copy_bandwidth(ngicp_t* h, size_t bytes, int reps, double* gbp
 }  // extern "C"
 
 // ---- scan preprocessing and map accumulation + voxel filter ----
+#include "ngicp_deskew.h"  // (here, after every other kernel: the code object up to this point is laid out as it was without it)
+
 namespace {
 // host cloud (strided xyz [+ intensity]) -> device float4 {x, y, z, intensity} at dst[0..n)
 void upload_xyzi(ngicp* h, const float* pts, size_t n, size_t stride, long intensity_off, float4* dst) {
@@ -1957,6 +1959,78 @@ void download_xyzi(ngicp* h, const float4* src, size_t n, float* out) {
   if (n == 0) return;
   HIP_TRY(hipMemcpyAsync(out, src, n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
+}
+
+// ---- motion deskew (csrc/ngicp_deskew.h) ----
+void deskew_check_pose(const double* T, const char* field) {
+  for (int e = 0; e < 16; ++e)
+    if (!std::isfinite(T[e])) throw ArgError{NGICP_ERR_ARG, std::string(field) + ": non-finite entry"};
+  if (T[3] != 0.0 || T[7] != 0.0 || T[11] != 0.0 || T[15] != 1.0) throw ArgError{NGICP_ERR_ARG, std::string(field) + ": the last row must be (0, 0, 0, 1)"};
+}
+
+// Validates *d and the layout, uploads the cloud, its times and the trajectory, builds the table and runs k_deskew_unpack into `out`
+// (device memory: n float4, or n x 3 floats when packed).  Nothing is enqueued before every argument has been accepted.
+void deskew_upload_unpack(ngicp* h, const float* pts, size_t n, size_t stride, long intensity_off, const ngicp_deskew_t* d, bool packed, float* out) {
+  if (!d) throw ArgError{NGICP_ERR_ARG, "d: null deskew description"};
+  if (d->n_poses < 2 || d->n_poses > (size_t)NGICP_DESKEW_MAX_POSES) throw ArgError{NGICP_ERR_ARG, "n_poses must be between 2 and NGICP_DESKEW_MAX_POSES (256)"};
+  if (!d->pose_times) throw ArgError{NGICP_ERR_ARG, "pose_times: null pointer"};
+  if (!d->poses_colmajor) throw ArgError{NGICP_ERR_ARG, "poses_colmajor: null pointer"};
+  const int M = (int)d->n_poses;
+  for (int k = 0; k < M; ++k)
+    if (!std::isfinite(d->pose_times[k]) || (k > 0 && !(d->pose_times[k] > d->pose_times[k - 1])))
+      throw ArgError{NGICP_ERR_ARG, "pose_times must be finite and strictly ascending"};
+  for (int k = 0; k < M; ++k) deskew_check_pose(d->poses_colmajor + (size_t)k * 16, "poses_colmajor");
+  if (d->T_ref_colmajor) deskew_check_pose(d->T_ref_colmajor, "T_ref_colmajor");
+  if (d->time_format != NGICP_TIME_F32_S && d->time_format != NGICP_TIME_F64_S && d->time_format != NGICP_TIME_U32_NS)
+    throw ArgError{NGICP_ERR_ARG, "time_format: unknown format"};
+  if (stride < 12 || stride % 4) throw ArgError{NGICP_ERR_ARG, "stride_bytes must be a multiple of 4 and >= 12"};
+  if (intensity_off >= 0 && ((size_t)intensity_off + 4 > stride || intensity_off % 4)) throw ArgError{NGICP_ERR_ARG, "intensity offset outside the point stride"};
+  if (n > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "cloud too large for int indices"};
+  const size_t tsize = d->time_format == NGICP_TIME_F64_S ? 8 : 4;  // a time is read with one aligned load of its own size
+  size_t record_end = intensity_off >= 0 ? std::max((size_t)12, (size_t)intensity_off + 4) : 12;
+  DeskewTimes tm{};
+  tm.format = d->time_format;
+  tm.unit = d->time_format == NGICP_TIME_U32_NS ? 1e-9 : 1.0;
+  tm.offset = d->time_offset;
+  if (!d->times) {
+    const long off = d->time_offset_bytes;
+    if (off < 0 || (size_t)off % tsize || (size_t)off + tsize > stride || stride % tsize)
+      throw ArgError{NGICP_ERR_ARG, "time_offset_bytes does not fit the point stride or the time format's size and alignment"};
+    record_end = std::max(record_end, (size_t)off + tsize);
+    tm.stride = stride;
+    tm.first = (size_t)off;
+  } else {
+    if (d->time_stride_bytes < tsize || d->time_stride_bytes % tsize)
+      throw ArgError{NGICP_ERR_ARG, "time_stride_bytes does not fit the time format's size and alignment"};
+    tm.stride = d->time_stride_bytes;
+    tm.first = 0;
+  }
+  const size_t raw_bytes = (n - 1) * stride + record_end;
+  h->raw.ensure(raw_bytes);
+  HIP_TRY(hipMemcpyAsync(h->raw.p, pts, raw_bytes, hipMemcpyHostToDevice, h->stream));
+  tm.base = h->raw.as<unsigned char>();
+  if (d->times) {
+    const size_t time_bytes = (n - 1) * tm.stride + tsize;
+    h->dsk_times.ensure(time_bytes);
+    HIP_TRY(hipMemcpyAsync(h->dsk_times.p, d->times, time_bytes, hipMemcpyHostToDevice, h->stream));
+    tm.base = h->dsk_times.as<unsigned char>();
+  }
+  std::vector<double>& in = h->dsk_host;
+  in.resize((size_t)M * 17 + 16);
+  std::copy(d->pose_times, d->pose_times + M, in.begin());
+  std::copy(d->poses_colmajor, d->poses_colmajor + (size_t)M * 16, in.begin() + M);
+  for (int e = 0; e < 16; ++e) in[(size_t)M * 17 + e] = d->T_ref_colmajor ? d->T_ref_colmajor[e] : (e % 5 == 0 ? 1.0 : 0.0);
+  h->dsk_in.ensure(in.size() * sizeof(double));
+  h->dsk_table.ensure(deskew_table_doubles(M) * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(h->dsk_in.p, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_deskew_prepare, dim3(1), dim3(kDeskewMaxPoses), 0, h->stream, h->dsk_in.as<double>(), M, h->dsk_table.as<double>());
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const size_t lds = deskew_table_doubles(M) * sizeof(double);
+  if (packed)
+    hipLaunchKernelGGL((k_deskew_unpack<true>), grid, block, lds, h->stream, h->raw.as<unsigned char>(), stride, intensity_off, tm, h->dsk_table.as<double>(), M, (int)n, out);
+  else
+    hipLaunchKernelGGL((k_deskew_unpack<false>), grid, block, lds, h->stream, h->raw.as<unsigned char>(), stride, intensity_off, tm, h->dsk_table.as<double>(), M, (int)n, out);
+  HIP_TRY(hipGetLastError());
 }
 }  // namespace
 
@@ -2015,6 +2089,45 @@ int ngicp_set_source_preprocessed(ngicp_t* h, uint64_t host_identity) {
     h->src_covs.clear();
   });
   return rc;
+}
+
+// ---- motion deskew: the per-point pose of a trajectory applied where the scan is unpacked (csrc/ngicp_deskew.h) ----
+int ngicp_deskew_cloud(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, const ngicp_deskew_t* d, float* xyz_out, size_t out_stride_bytes) {
+  return guarded(h, [&] {
+    if (n == 0) return;
+    if (!pts || !xyz_out) throw ArgError{NGICP_ERR_ARG, "null pointer"};
+    if (out_stride_bytes < 12 || out_stride_bytes % 4) throw ArgError{NGICP_ERR_ARG, "bad out_stride_bytes"};
+    if (n > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "cloud too large for int indices"};
+    h->out_xyz.ensure(n * 3 * sizeof(float));
+    deskew_upload_unpack(h, pts, n, stride_bytes, -1, d, true, h->out_xyz.as<float>());
+    download_xyz(h, n, xyz_out, out_stride_bytes);
+  });
+}
+
+int ngicp_preprocess_scan_deskewed(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, long intensity_offset_bytes, const ngicp_deskew_t* d, int remove_nan,
+                                   float crop_half_extent, float voxel_leaf, float* out_xyzi, size_t out_capacity, size_t* n_out) {
+  return guarded(h, [&] {
+    if (n_out) *n_out = 0;
+    h->filt_out = nullptr;
+    h->filt_n = 0;
+    if (n == 0) return;
+    if (!pts) throw ArgError{NGICP_ERR_ARG, "null cloud pointer"};
+    if (n > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "cloud too large for int indices"};
+    h->xyzi.ensure(n * sizeof(float4));
+    deskew_upload_unpack(h, pts, n, stride_bytes, intensity_offset_bytes, d, false, h->xyzi.as<float>());
+    char err[256] = {0};
+    const float4* out = nullptr;
+    int m = 0;
+    if (ngk_filter_cloud(h->stream, &h->fws, h->xyzi.as<float4>(), (int)n, remove_nan, crop_half_extent, voxel_leaf, &out, &m, err, sizeof(err)))
+      throw ArgError{NGICP_ERR_HIP, err};
+    h->filt_out = out;
+    h->filt_n = m;
+    if (n_out) *n_out = (size_t)m;
+    if (out_xyzi) {
+      if ((size_t)m > out_capacity) throw ArgError{NGICP_ERR_ARG, "output buffer too small for the filtered cloud"};
+      download_xyzi(h, out, (size_t)m, out_xyzi);
+    }
+  });
 }
 
 int ngicp_map_add(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, long intensity_offset_bytes) {

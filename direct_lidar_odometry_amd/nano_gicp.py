@@ -100,7 +100,20 @@ EXPORTS = [
     "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
     "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
     "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
+    "ngicp_deskew_cloud", "ngicp_preprocess_scan_deskewed",
 ]
+
+
+class Deskew(C.Structure):
+    """ngicp_deskew_t (include/ngicp.h, "motion deskew")."""
+    _fields_ = [("times", C.c_void_p), ("time_stride_bytes", C.c_size_t), ("time_offset_bytes", C.c_long), ("time_format", C.c_int),
+                ("time_offset", C.c_double), ("n_poses", C.c_size_t), ("pose_times", c_f64p), ("poses_colmajor", c_f64p),
+                ("T_ref_colmajor", c_f64p)]
+
+
+TIME_F32_S, TIME_F64_S, TIME_U32_NS = 0, 1, 2  # NGICP_TIME_*
+DESKEW_MAX_POSES = 256                          # NGICP_DESKEW_MAX_POSES
+_TIME_FORMAT_OF = {np.dtype(np.float32): TIME_F32_S, np.dtype(np.float64): TIME_F64_S, np.dtype(np.uint32): TIME_U32_NS}
 
 BATCH_MAX_LANES = 64  # NGICP_BATCH_MAX_LANES (include/ngicp.h): guesses per alignBatch call
 
@@ -179,6 +192,9 @@ def load_library() -> C.CDLL:
     L.ngicp_measure_copy_bandwidth.argtypes = [vp, C.c_size_t, C.c_int, c_f64p]
     L.ngicp_preprocess_scan.argtypes = [vp, c_f32p, C.c_size_t, C.c_size_t, C.c_long, C.c_int, C.c_float, C.c_float, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_set_source_preprocessed.argtypes = [vp, C.c_uint64]
+    L.ngicp_deskew_cloud.argtypes = [vp, c_f32p, C.c_size_t, C.c_size_t, C.POINTER(Deskew), c_f32p, C.c_size_t]
+    L.ngicp_preprocess_scan_deskewed.argtypes = [vp, c_f32p, C.c_size_t, C.c_size_t, C.c_long, C.POINTER(Deskew), C.c_int, C.c_float, C.c_float, c_f32p,
+                                                 C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_map_add.argtypes = [vp, c_f32p, C.c_size_t, C.c_size_t, C.c_long]
     L.ngicp_map_voxel_filter.argtypes = [vp, C.c_float, C.POINTER(C.c_size_t)]
     L.ngicp_map_size.argtypes = [vp, C.POINTER(C.c_size_t)]
@@ -797,6 +813,72 @@ class NanoGICP:
         m = C.c_size_t(0)
         self._ck(self._L.ngicp_preprocess_scan(self._h, _p(c, c_f32p), c.shape[0], c.strides[0], self._intensity_offset(c, intensity_col),
                                                1 if remove_nan else 0, float(crop_size), float(voxel_res), _p(out, c_f32p), out.shape[0], C.byref(m)))
+        out = out[:m.value].copy()
+        if set_as_source:
+            self._ck(self._L.ngicp_set_source_preprocessed(self._h, 0))
+            self._src = np.ascontiguousarray(out[:, :3])
+        return out
+
+    # ---- motion deskew (include/ngicp.h "motion deskew") ----
+    @staticmethod
+    def _deskew_desc(n, times, pose_times, poses, T_ref, time_format, time_offset):
+        """ngicp_deskew_t and the arrays it points into (to be kept alive over the call).  `times`: an array of n times (float32 or
+        float64 seconds, uint32 nanoseconds; any positive stride), or an int: the float32 column of the cloud's rows at which every
+        record holds its time (byte offset 4 * column; time_format says what lies there, float32 seconds by default)."""
+        d = Deskew()
+        keep = []
+        if isinstance(times, (int, np.integer)):
+            d.times, d.time_stride_bytes, d.time_offset_bytes = None, 0, 4 * int(times)
+            d.time_format = TIME_F32_S if time_format is None else int(time_format)
+        else:
+            t = np.asarray(times)
+            if t.dtype not in _TIME_FORMAT_OF:
+                t = t.astype(np.float64)
+            if t.ndim != 1 or t.shape[0] != n:
+                raise ValueError("times must be one time per point")
+            if n > 1 and t.strides[0] <= 0:
+                t = np.ascontiguousarray(t)
+            keep.append(t)
+            d.times, d.time_stride_bytes, d.time_offset_bytes = t.ctypes.data, (t.strides[0] if n > 1 else t.itemsize), 0
+            d.time_format = _TIME_FORMAT_OF[t.dtype] if time_format is None else int(time_format)
+        d.time_offset = float(time_offset)
+        pt = np.ascontiguousarray(pose_times, dtype=np.float64).reshape(-1)
+        ps = np.asarray(poses, dtype=np.float64)
+        if ps.ndim != 3 or ps.shape[1:] != (4, 4) or ps.shape[0] != pt.shape[0]:
+            raise ValueError("poses must have shape (len(pose_times), 4, 4)")
+        ps = np.ascontiguousarray(ps.transpose(0, 2, 1)).reshape(-1)
+        keep += [pt, ps]
+        d.n_poses, d.pose_times, d.poses_colmajor = pt.shape[0], _p(pt, c_f64p), _p(ps, c_f64p)
+        if T_ref is not None:
+            tr = _colmajor16(T_ref, np.float64)
+            keep.append(tr)
+            d.T_ref_colmajor = _p(tr, c_f64p)
+        return d, keep
+
+    def deskewCloud(self, cloud, times, pose_times, poses, T_ref=None, time_format=None, time_offset: float = 0.0) -> np.ndarray:
+        """Every point moved by the trajectory's pose at its own time into T_ref's frame (None: identity), on the GPU; returns (N, 3).
+        poses: (M, 4, 4) at pose_times (M, strictly ascending), geodesic in rotation and linear in translation between them, clamped at
+        both ends.  `times`: see _deskew_desc."""
+        c = _cloud(cloud)
+        d, keep = self._deskew_desc(c.shape[0], times, pose_times, poses, T_ref, time_format, time_offset)
+        out = np.empty((c.shape[0], 3), dtype=np.float32)
+        self._ck(self._L.ngicp_deskew_cloud(self._h, _p(c, c_f32p), c.shape[0], c.strides[0], C.byref(d), _p(out, c_f32p), 12))
+        del keep
+        return out
+
+    def preprocessScanDeskewed(self, cloud, times, pose_times, poses, T_ref=None, time_format=None, time_offset: float = 0.0, remove_nan: bool = True,
+                               crop_size: float = 0.0, voxel_res: float = 0.0, intensity_col=None, set_as_source: bool = False) -> np.ndarray:
+        """preprocessScan with the deskew (deskewCloud's arguments) applied where the scan is unpacked on the device: the deskewed scan
+        never exists on the host.  Returns (M, 4) {x, y, z, intensity}; set_as_source as in preprocessScan."""
+        c = np.asarray(cloud, dtype=np.float32)
+        if c.ndim != 2 or c.shape[1] < 3 or not c.flags.c_contiguous:
+            c = np.ascontiguousarray(c, dtype=np.float32)
+        d, keep = self._deskew_desc(c.shape[0], times, pose_times, poses, T_ref, time_format, time_offset)
+        out = np.empty((c.shape[0], 4), dtype=np.float32)
+        m = C.c_size_t(0)
+        self._ck(self._L.ngicp_preprocess_scan_deskewed(self._h, _p(c, c_f32p), c.shape[0], c.strides[0], self._intensity_offset(c, intensity_col), C.byref(d),
+                                                        1 if remove_nan else 0, float(crop_size), float(voxel_res), _p(out, c_f32p), out.shape[0], C.byref(m)))
+        del keep
         out = out[:m.value].copy()
         if set_as_source:
             self._ck(self._L.ngicp_set_source_preprocessed(self._h, 0))

@@ -14,6 +14,7 @@
 // With PCL and Eigen installed the class uses pcl::PointCloud / Eigen::Matrix4f; without them (this repo's
 // build container) it uses the layout-compatible stand-ins of pcl_compat.hpp.
 #pragma once
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -90,6 +91,54 @@ struct SpaciousnessFilter {
     return median_lpf;
   }
   void reset() { seeded = false; }
+};
+
+// Motion deskew (ngicp.h "motion deskew"; no counterpart in the reference, DLIO's headline addition): the pose trajectory over one
+// sweep, from an IMU or a velocity model, and where each point's time is found.  A value type: it owns the poses, and only
+// refers to a separate array of times.  In a DLIO-style callback:
+//     nano_gicp::DeskewTrajectory traj;
+//     for (auto& s : imu_states) traj.addPose(s.stamp - sweep_start, s.T_world_lidar);
+//     traj.setReference(imu_states.back().T_world_lidar);                      // output in the frame at the sweep's end
+//     traj.setTimesInRecord(offsetof(PointType, time), NGICP_TIME_F32_S);      // or setTimes(array.data(), n)
+//     gicp_s2s.preprocessScanDeskewed(scan, traj, true, crop, leaf, /*set_as_source=*/true);
+struct DeskewTrajectory {
+  std::vector<double> pose_times;      // strictly ascending, in the clock of the point times (after time_offset)
+  std::vector<double> poses_colmajor;  // 16 per pose
+  bool has_reference = false;
+  double T_ref_colmajor[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const void* times = nullptr;  // nullptr: inside each point record at time_offset_bytes
+  size_t time_stride_bytes = 0;
+  long time_offset_bytes = 0;
+  int time_format = NGICP_TIME_F32_S;
+  double time_offset = 0.0;  // added to every point time (seconds)
+
+  void clear() { pose_times.clear(); poses_colmajor.clear(); }
+  size_t size() const { return pose_times.size(); }
+  void addPose(double t, const types::Matrix4d& T) {
+    pose_times.push_back(t);
+    poses_colmajor.insert(poses_colmajor.end(), T.data(), T.data() + 16);
+  }
+  void setReference(const types::Matrix4d& T) {
+    has_reference = true;
+    for (int e = 0; e < 16; ++e) T_ref_colmajor[e] = T.data()[e];
+  }
+  void setTimes(const float* t, size_t stride_bytes = sizeof(float)) { times = t; time_stride_bytes = stride_bytes; time_format = NGICP_TIME_F32_S; }
+  void setTimes(const double* t, size_t stride_bytes = sizeof(double)) { times = t; time_stride_bytes = stride_bytes; time_format = NGICP_TIME_F64_S; }
+  void setTimesNanoseconds(const std::uint32_t* t, size_t stride_bytes = sizeof(std::uint32_t)) { times = t; time_stride_bytes = stride_bytes; time_format = NGICP_TIME_U32_NS; }
+  void setTimesInRecord(long offset_bytes, int format) { times = nullptr; time_stride_bytes = 0; time_offset_bytes = offset_bytes; time_format = format; }
+  ngicp_deskew_t describe() const {
+    ngicp_deskew_t d;
+    d.times = times;
+    d.time_stride_bytes = time_stride_bytes;
+    d.time_offset_bytes = time_offset_bytes;
+    d.time_format = time_format;
+    d.time_offset = time_offset;
+    d.n_poses = poses_colmajor.size() == pose_times.size() * 16 ? pose_times.size() : 0;
+    d.pose_times = pose_times.data();
+    d.poses_colmajor = poses_colmajor.data();
+    d.T_ref_colmajor = has_reference ? T_ref_colmajor : nullptr;
+    return d;
+  }
 };
 
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };  // gicp/gicp_settings.hpp:47
@@ -668,6 +717,43 @@ class NanoGICP {
       p.intensity = out[i * 4 + 3];
     }
     if (set_as_source) check(ngicp_set_source_preprocessed(h_, 0), "set_source_preprocessed");
+  }
+  // Motion deskew (ngicp.h "motion deskew"): every point of `cloud` moved by the trajectory's pose at its own time into the
+  // trajectory's reference frame, on the GPU; `out` is `cloud` with new x, y, z.  false (and a line on stderr) on a refused argument.
+  bool deskewCloud(const PointCloudSource& cloud, const DeskewTrajectory& traj, PointCloudSource& out) {
+    if (!h_) return false;
+    if (&out != &cloud) out = cloud;
+    if (cloud.empty()) return true;
+    const ngicp_deskew_t d = traj.describe();
+    std::vector<float> xyz(cloud.size() * 3);
+    if (!check(ngicp_deskew_cloud(h_, cloud.points[0].data, cloud.size(), sizeof(PointSource), &d, xyz.data(), 12), "deskewCloud")) return false;
+    for (size_t i = 0; i < out.size(); ++i) {
+      out.points[i].data[0] = xyz[i * 3 + 0];
+      out.points[i].data[1] = xyz[i * 3 + 1];
+      out.points[i].data[2] = xyz[i * 3 + 2];
+    }
+    return true;
+  }
+  // preprocessPoints with the deskew applied where the scan is unpacked on the device: the deskewed scan never exists on the host.
+  // With remove_nan, points whose time is not finite are dropped.  false on a refused argument: `cloud` is left as it was.
+  bool preprocessScanDeskewed(PointCloudSource& cloud, const DeskewTrajectory& traj, bool remove_nan, float crop_size, float voxel_res, bool set_as_source = false) {
+    if (!h_) return false;
+    if (cloud.empty()) return true;
+    const ngicp_deskew_t d = traj.describe();
+    std::vector<float> out(cloud.size() * 4);
+    size_t m = 0;
+    const long ioff = (long)((const char*)&cloud.points[0].intensity - (const char*)cloud.points[0].data);
+    if (!check(ngicp_preprocess_scan_deskewed(h_, cloud.points[0].data, cloud.size(), sizeof(PointSource), ioff, &d, remove_nan ? 1 : 0, crop_size, voxel_res,
+                                              out.data(), cloud.size(), &m), "preprocessScanDeskewed"))
+      return false;
+    cloud.resize(m);
+    for (size_t i = 0; i < m; ++i) {
+      PointSource& p = cloud.points[i];
+      p.data[0] = out[i * 4 + 0]; p.data[1] = out[i * 4 + 1]; p.data[2] = out[i * 4 + 2]; p.data[3] = 1.0f;
+      p.intensity = out[i * 4 + 3];
+    }
+    if (set_as_source) return check(ngicp_set_source_preprocessed(h_, 0), "set_source_preprocessed");
+    return true;
   }
   // dlo::MapNode (map.cc:100-131): `*dlo_map += *keyframe` and `voxelgrid.filter(*dlo_map)` on a device-resident map
   void mapAdd(const PointCloudSource& keyframe) {

@@ -598,6 +598,56 @@ int ngicp_preprocess_scan(ngicp_t* h, const float* pts, size_t n, size_t stride_
                           float voxel_leaf, float* out_xyzi_or_null, size_t out_capacity, size_t* n_out);
 int ngicp_set_source_preprocessed(ngicp_t* h, uint64_t host_identity);
 
+/* --- motion deskew (no counterpart in the reference) ------------------- */
+/* A spinning LiDAR collects a sweep over ~100 ms while the platform moves.  Given a time per point and a pose trajectory over the
+ * sweep (from an IMU or a velocity model: estimating it stays with the caller), every point is moved into the frame of ONE
+ * reference pose, on the device, where the scan is unpacked.  Restated in numpy float64 by tests/_deskew_model.py.
+ *   points      p_i, float32 xyz at byte 0 of a strided record.
+ *   times       s_i = double(raw_i) * unit + time_offset: two roundings in that order, no FMA.  unit = 1 for NGICP_TIME_F32_S and
+ *               NGICP_TIME_F64_S (seconds), 1e-9 for NGICP_TIME_U32_NS (nanoseconds).  raw_i lies inside the point record at
+ *               time_offset_bytes (times == NULL), or in the strided array `times`.  It is read with one load of its own size: the
+ *               offset, the stride it advances by and (inside the record) the point stride are multiples of 4 (8 for F64).
+ *   trajectory  n_poses poses T_k = (R_k, t_k), double, column-major 4x4 with last row (0, 0, 0, 1), at times tau_0 < ... <
+ *               tau_{M-1} in the clock of s_i; 2 <= n_poses <= NGICP_DESKEW_MAX_POSES.  T_ref: the pose whose frame the output is
+ *               expressed in (NULL: identity).
+ *   1. once per call  R'_k = R_ref^T R_k,  t'_k = R_ref^T (t_k - t_ref).
+ *   2. per segment k < M - 1:  phi_k = so3_log(R'_k^T R'_{k+1}) (csrc/ngicp_math.h).  Consecutive poses must be less than 3 rad
+ *      apart; beyond that the result is finite but unspecified.
+ *   3. bracket: k_i = the largest k with tau_k <= s_i, clamped to [0, M - 2]; alpha = (s_i - tau_k) / (tau_{k+1} - tau_k), clamped to
+ *      [0, 1].  No extrapolation: a time before tau_0 takes pose 0, a time at or after tau_{M-1} the last pose.
+ *   4. R(s) = R'_k * so3_exp_matrix(alpha * phi_k),  t(s) = t'_k + alpha * (t'_{k+1} - t'_k).
+ *   5. p'_i = R(s) p_i + t(s) in double, row by row as ((r0 * x + r1 * y) + r2 * z) + t, rounded once to float32.  Intensity is
+ *      carried through unchanged.  (An identity trajectory returns the input, except that -0.0 becomes +0.0.)
+ *   6. a point with a non-finite coordinate is copied unchanged; a finite point with a non-finite time gets x = y = z = NaN, so that
+ *      removeNaN drops it instead of leaving it skewed unnoticed.
+ * No result depends on n or on another point.
+ * ngicp_deskew_cloud: host cloud -> host, like ngicp_transform_cloud (xyz only); it changes nothing a getter returns and leaves a
+ * pending preprocessed cloud in place.
+ * ngicp_preprocess_scan_deskewed: ngicp_preprocess_scan with the deskew in the unpack step; the filters that follow and the result
+ * left on the device for ngicp_set_source_preprocessed are the same (every stage off: the deskewed scan becomes the source with no
+ * download).  On an error no preprocessed cloud is pending.
+ * NGICP_ERR_ARG, with ngicp_last_error naming the field: d == NULL; n_poses outside 2..256; pose_times not finite or not strictly
+ * ascending; a non-finite pose entry or a last row other than (0, 0, 0, 1) (T_ref included); an unknown time_format; a time offset
+ * or stride that does not fit the point stride or the format's size and alignment.  n == 0: nothing is done, 0 is returned. */
+#define NGICP_TIME_F32_S 0
+#define NGICP_TIME_F64_S 1
+#define NGICP_TIME_U32_NS 2
+#define NGICP_DESKEW_MAX_POSES 256
+typedef struct ngicp_deskew {
+  const void* times;            /* NULL: the time lies inside each point record at time_offset_bytes */
+  size_t time_stride_bytes;     /* of `times`; ignored when times is NULL */
+  long time_offset_bytes;       /* inside the point record, when times is NULL */
+  int time_format;              /* NGICP_TIME_* */
+  double time_offset;           /* added to every time after the unit conversion */
+  size_t n_poses;
+  const double* pose_times;     /* n_poses */
+  const double* poses_colmajor; /* n_poses x 16 */
+  const double* T_ref_colmajor; /* 16, or NULL = identity */
+} ngicp_deskew_t;
+int ngicp_deskew_cloud(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, const ngicp_deskew_t* d, float* xyz_out, size_t out_stride_bytes);
+int ngicp_preprocess_scan_deskewed(ngicp_t* h, const float* pts, size_t n, size_t stride_bytes, long intensity_offset_bytes, const ngicp_deskew_t* d, int remove_nan,
+                                   float crop_half_extent, float voxel_leaf, float* out_xyzi_or_null, size_t out_capacity, size_t* n_out);
+
 /* --- map accumulation + voxel filter ---------------------------------- */
 /* dlo::MapNode (src/dlo/map.cc:100-131): `*dlo_map += *keyframe` per keyframe (ngicp_map_add: the keyframe is appended to
  * a device-resident map), and on the publish timer `voxelgrid.filter(*dlo_map)` with a cubic leaf (ngicp_map_voxel_filter:
