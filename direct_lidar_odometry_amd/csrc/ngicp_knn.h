@@ -383,8 +383,11 @@ __global__ void __launch_bounds__(kKnnBlock) k_covariances(const float4* __restr
     } else if (reg == REG_MIN_EIG) {
       v0 = fmax(a0, 1e-3); v1 = fmax(a1, 1e-3); v2 = fmax(a2, 1e-3);
     } else {
+      // a rank-0 neighbourhood (k = 1, or k coincident points: m == 0) has no ratio to take; every value gets the floor, which is
+      // what MIN_EIG gives for the same input (the reference is unspecified there: Eigen's array max of a NaN, :346-347)
       const double m = fmax(a0, fmax(a1, a2));
-      v0 = fmax(a0 / m, 1e-3); v1 = fmax(a1 / m, 1e-3); v2 = fmax(a2 / m, 1e-3);
+      const bool ratio = m > 0.0;
+      v0 = ratio ? fmax(a0 / m, 1e-3) : 1e-3; v1 = ratio ? fmax(a1 / m, 1e-3) : 1e-3; v2 = ratio ? fmax(a2 / m, 1e-3) : 1e-3;
     }
     // U diag(v) V^T with U == V (columns of V are eigenvectors)
     out[0] = V[0] * v0 * V[0] + V[1] * v1 * V[1] + V[2] * v2 * V[2];

@@ -42,7 +42,8 @@ typedef struct ngicp ngicp_t;
 #define NGICP_ERR_STATE (-3)      /* call sequence error (e.g. align() without target) */
 #define NGICP_ERR_K_TOO_LARGE (-4)/* k > cloud size or k > 32: undefined in the reference, explicit error here */
 
-/* regularisation (include/nano_gicp/gicp/gicp_settings.hpp:47) */
+/* regularisation (include/nano_gicp/gicp/gicp_settings.hpp:47).  NORMALIZED_MIN_EIG of a rank-0 neighbourhood (k = 1, or k
+ * coincident points: every singular value is 0) is 1e-3 * I, as MIN_EIG gives; the reference leaves that case unspecified. */
 #define NGICP_REG_NONE 0
 #define NGICP_REG_MIN_EIG 1
 #define NGICP_REG_NORMALIZED_MIN_EIG 2

@@ -575,8 +575,11 @@ static int calc_covariances(const CloudView& cloud, const KdTree& tree, int k, i
       } else if (reg == REG_MIN_EIG) {
         for (int d = 0; d < 3; ++d) vals[d] = std::max(std::fabs(w[d]), 1e-3);
       } else {
+        // mx == 0 (a rank-0 neighbourhood: k = 1, or k coincident points): the reference is unspecified there (Eigen's array
+        // max of the NaN 0/0, impl/nano_gicp_impl.hpp:346-347).  The rule here is explicit: no ratio is taken, every value
+        // gets the floor 1e-3, which is what MIN_EIG gives for the same input.
         double mx = std::max(std::fabs(w[0]), std::max(std::fabs(w[1]), std::fabs(w[2])));
-        for (int d = 0; d < 3; ++d) vals[d] = std::max(std::fabs(w[d]) / mx, 1e-3);
+        for (int d = 0; d < 3; ++d) vals[d] = mx > 0.0 ? std::max(std::fabs(w[d]) / mx, 1e-3) : 1e-3;
       }
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) {
