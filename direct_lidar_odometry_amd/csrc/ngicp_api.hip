@@ -32,6 +32,7 @@
 #include "ngicp_voxel.h"
 #include "ngicp_voxel_batch.h"
 #include "ngicp_voxel_roll.h"
+#include "ngicp_voxel_rollrec.h"
 #include "ngicp_robust.h"
 
 using namespace ngk;
@@ -605,6 +606,8 @@ int ngicp_create(int device, ngicp_t** out) {
     HIP_TRY(hipEventCreate(&h->ev_vox_a));
     HIP_TRY(hipEventCreate(&h->ev_vox_b));
     HIP_TRY(hipEventCreate(&h->ev_vox_c));
+    HIP_TRY(hipEventCreate(&h->ev_rec_a));
+    HIP_TRY(hipEventCreate(&h->ev_rec_b));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_state), 2 * sizeof(LmState), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_final), sizeof(LmHot), hipHostMallocDefault));
     h->order_flag.ensure(64);
@@ -690,6 +693,8 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_vox_a) (void)hipEventDestroy(h->ev_vox_a);
   if (h->ev_vox_b) (void)hipEventDestroy(h->ev_vox_b);
   if (h->ev_vox_c) (void)hipEventDestroy(h->ev_vox_c);
+  if (h->ev_rec_a) (void)hipEventDestroy(h->ev_rec_a);
+  if (h->ev_rec_b) (void)hipEventDestroy(h->ev_rec_b);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -1342,6 +1347,7 @@ int ngicp_voxel_rolling_get(ngicp_t* h, size_t* n_vox, int* ijk_n3, double* sum_
 
 int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vox, size_t* capacity_vox, size_t* table_slots, double* last_insert_ms, double* last_evict_ms) {
   if (!h) return NGICP_ERR_ARG;
+  if (last_insert_ms) roll_resolve_time(const_cast<ngicp_t*>(h), true);  // (a record insert's commit is left in the stream: its time is read here)
   if (inserts) *inserts = h->roll.inserts;
   if (n_vox) *n_vox = h->roll.n_vox;
   if (capacity_vox) *capacity_vox = h->roll.cap;
@@ -1349,6 +1355,25 @@ int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vo
   if (last_insert_ms) *last_insert_ms = h->roll.last_insert_ms;
   if (last_evict_ms) *last_evict_ms = h->roll.last_evict_ms;
   return NGICP_OK;
+}
+
+// ---- the rolling map from voxel records (include/ngicp.h "rolling voxel map: records"; ngicp_voxel_rollrec.h) ----
+int ngicp_voxel_rolling_set(ngicp_t* h, size_t n_vox, const int* ijk_n3, const double* sum_n3, const double* covsum_n6, const int* count_n, const long long* stamp_n, long long inserts) {
+  return guarded(h, [&] { roll_set(h, n_vox, ijk_n3, sum_n3, covsum_n6, count_n, stamp_n, inserts); });
+}
+
+int ngicp_voxel_rolling_insert_voxels(ngicp_t* h, size_t n_rec, const double* sum_n3, const double* covsum_n6, const int* count_n, const float T_colmajor[16], size_t* n_new,
+                                      size_t* n_touched) {
+  return guarded(h, [&] { roll_insert_voxels(h, n_rec, sum_n3, covsum_n6, count_n, T_colmajor, n_new, n_touched); });
+}
+
+int ngicp_voxel_rolling_insert_map(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], size_t* n_new, size_t* n_touched) {
+  if (!from) return NGICP_ERR_ARG;
+  return guarded(h, [&] { roll_insert_map(h, from, T_colmajor, n_new, n_touched); });
+}
+
+int ngicp_voxel_rolling_transform(ngicp_t* h, const float T_colmajor[16], size_t* n_vox_after) {
+  return guarded(h, [&] { roll_transform(h, T_colmajor, n_vox_after); });
 }
 
 int ngicp_target_knn(ngicp_t* h, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {

@@ -417,6 +417,10 @@ struct ngicp {
     double last_insert_ms = 0.0, last_evict_ms = 0.0;  // device event times
   } roll;
   DevBuf roll_q, roll_sums, roll_hit, roll_tmp;  // an insert's transformed points, per-scan-voxel sums and lookup results; an eviction's compaction workspace
+  // the record routes (ngicp_voxel_rollrec.h): the uploaded arrays of a restore / a record insert, a move's per-voxel stamps
+  DevBuf roll_up, roll_seg_stamp;
+  hipEvent_t ev_rec_a = nullptr, ev_rec_b = nullptr;  // around a record insert, whose commit is left in the stream:
+  bool rec_time_pending = false;                      // its time is read when it is next asked for (roll_resolve_time)
   // motion deskew (csrc/ngicp_deskew.h): the separately uploaded times, the uploaded trajectory and the table k_deskew_prepare makes of it
   DevBuf dsk_times, dsk_in, dsk_table;
   std::vector<double> dsk_host;          // the trajectory as uploaded: [M times][M x 16 poses][16 T_ref] (outlives the asynchronous copy)

@@ -1,5 +1,6 @@
 // The rolling voxel map's host code (ngicp_voxel_roll.h; include/ngicp.h "rolling voxel map"): insert, evict, clear and
-// the growth of its arrays and table.  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose
+// the growth of its arrays and table; behind them the record routes (ngicp_voxel_rollrec.h): restore, insert of
+// records, handle-to-handle insert, move in place.  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose
 // size_voxel_work / voxel_segments number a scan's voxels).
 #pragma once
 
@@ -144,8 +145,207 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   ++r.inserts;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess) r.last_insert_ms = ms;
+  h->rec_time_pending = false;  // (a record insert's time that nobody asked for is superseded)
   if (n_new_out) *n_new_out = (size_t)n_new;
   if (n_touched_out) *n_touched_out = (size_t)n_seg;
+}
+
+// ---- the record routes (ngicp_voxel_rollrec.h; include/ngicp.h "rolling voxel map: records") ----
+// The device time of the last record insert or move: its commit was left in the stream, so the time is read when somebody asks
+// (ngicp_voxel_rolling_stats: wait = true) or, without waiting, before the events are recorded again - a commit still running then
+// loses its time, not the host's.
+void roll_resolve_time(ngicp* h, bool wait) {
+  if (!h->rec_time_pending) return;
+  h->rec_time_pending = false;
+  float ms = 0.f;
+  if ((wait ? hipEventSynchronize(h->ev_rec_b) : hipEventQuery(h->ev_rec_b)) != hipSuccess) {
+    (void)hipGetLastError();  // ("not ready" is no error of the insert that follows)
+    return;
+  }
+  if (hipEventElapsedTime(&ms, h->ev_rec_a, h->ev_rec_b) == hipSuccess) h->roll.last_insert_ms = ms;
+}
+
+RollPose roll_pose(const float T[16]) {
+  RollPose P;
+  std::memcpy(P.m, T, sizeof(P.m));
+  for (int row = 0; row < 3; ++row)
+    for (int col = 0; col < 3; ++col) P.R[row * 3 + col] = (double)T[col * 4 + row];
+  return P;
+}
+
+// Insert n records at the float pose T (include/ngicp.h: "insert of records").  in / stamps_in are device arrays that stay valid until
+// the second synchronisation (the caller holds them); stamps_in != nullptr is the move in place: the map is rebuilt from its own
+// former records, every destination voxel is new and carries the largest stamp of its records, and the counter stays.
+// Two host synchronisations, both BEFORE the first write to the map: the destination voxel count with the refusal flag of the keys
+// (what sizes nothing yet), then the number of new voxels with the overflow flag of the lookup, which ran on the table as it stood.
+// Only then do the arrays and the table grow - by the exact count - and the commit is left in the stream.
+void roll_insert_records(ngicp* h, const RollRecs& in, const long long* stamps_in, int n, const float T[16], const char* entry, size_t* n_new_out, size_t* n_touched_out) {
+  ngicp::RollMap& r = h->roll;
+  const bool move = stamps_in != nullptr;
+  const RollPose P = roll_pose(T);
+  const float inv_res = 1.0f / (float)h->voxel_res;
+  roll_resolve_time(h, false);
+  size_voxel_work(h, (size_t)n);
+  h->roll_sums.ensure((size_t)n * kVoxRec * sizeof(double));
+  h->roll_hit.ensure((size_t)n * sizeof(int));
+  if (move) h->roll_seg_stamp.ensure((size_t)n * sizeof(long long));
+  HIP_TRY(hipEventRecord(h->ev_rec_a, h->stream));
+  HIP_TRY(hipMemsetAsync(h->vox_flag.p, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(k_rollrec_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, in, n, P, inv_res, h->vox_keys.as<unsigned long long>(), h->vox_vals.as<int>(),
+                     h->vox_flag.as<int>());
+  const VoxelSegments sg = voxel_segments(h, n);
+  int n_seg = 0, flag = 0;
+  HIP_TRY(hipMemcpyAsync(&n_seg, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&flag, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (flag & kRecBadCount) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a record's count is below 1; nothing was written"};
+  if (flag & kRecNoVoxel)
+    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a record's moved mean lies 2^20 voxels or more from the origin on some axis (or is not finite); nothing was written"};
+  if (n_seg <= 0 || n_seg > n) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent voxel count"};
+  const unsigned blocks = (unsigned)((n_seg + 255) / 256);
+  const int ntiles = (n_seg + kScanTile - 1) / kScanTile;
+  int* is_new = h->vox_scan.as<int>();  // (as roll_insert: the head and prefix arrays are free again; keys, order and seg_start are not)
+  int* rank = is_new + n;
+  const bool probe = !move && r.slots && r.n_vox;  // (an empty map, or the move's empty destination: every voxel is new)
+  long long* seg_stamp = move ? h->roll_seg_stamp.as<long long>() : nullptr;
+  hipLaunchKernelGGL(k_rollrec_lookup, dim3(blocks), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_seg, in, stamps_in, P,
+                     probe ? (const ulonglong2*)r.table.as<ulonglong2>() : (const ulonglong2*)nullptr, (unsigned int)(r.slots ? r.slots - 1 : 0), (const double*)r.sums.as<double>(),
+                     h->roll_sums.as<double>(), h->roll_hit.as<int>(), is_new, seg_stamp, h->vox_flag.as<int>());
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)is_new, n_seg, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)is_new, n_seg, (const int*)h->tile_sums.as<int>(), rank);
+  int n_new = 0;
+  HIP_TRY(hipMemcpyAsync(&n_new, rank + n_seg, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&flag, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  if (flag & kRecOverflow) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a voxel's count would pass 2^31 - 1; nothing was written"};
+  if (n_new < 0 || n_new > n_seg || (move && n_new != n_seg)) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent count of new voxels"};
+  const size_t base = move ? 0 : r.n_vox;
+  if (base + (size_t)n_new > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": too many voxels for int indices"};
+  // ---- from here on the map is written (the lookup has finished: a move's own records, and another handle's, are not read again) ----
+  h->hook_valid = 0;
+  if (move) r.n_vox = 0;  // nothing of the former arrays is kept: the destination sums are in the workspace
+  roll_reserve(h, base + (size_t)n_new);
+  if (!roll_reserve_table(h, base + (size_t)n_new) && move) roll_refill_table(h);  // (n_vox == 0: the table cleared)
+  hipLaunchKernelGGL(k_rollrec_commit, dim3(blocks), dim3(256), 0, h->stream, sg.keys, sg.seg_start, n_seg, (const double*)h->roll_sums.as<double>(), (const int*)h->roll_hit.as<int>(),
+                     (const int*)rank, (int)base, r.inserts + 1, (const long long*)seg_stamp, r.sums.as<double>(), r.rec.as<double>(), r.vkeys.as<unsigned long long>(),
+                     r.stamps.as<long long>(), r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1));
+  HIP_TRY(hipEventRecord(h->ev_rec_b, h->stream));
+  HIP_TRY(hipGetLastError());
+  h->rec_time_pending = true;
+  r.n_vox = base + (size_t)n_new;
+  if (!move) ++r.inserts;
+  if (n_new_out) *n_new_out = (size_t)n_new;
+  if (n_touched_out) *n_touched_out = (size_t)n_seg;
+}
+
+void roll_insert_voxels(ngicp* h, size_t n_rec, const double* sum_n3, const double* covsum_n6, const int* count_n, const float T[16], size_t* n_new_out, size_t* n_touched_out) {
+  const char* entry = "ngicp_voxel_rolling_insert_voxels";
+  roll_require_on(h, entry);
+  if (!sum_n3 || !covsum_n6 || !count_n || !T) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null pointer"};
+  if (n_rec == 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": no records"};
+  if (n_rec > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": too many records for int indices"};
+  const size_t off_c = n_rec * 3 * sizeof(double), off_n = off_c + n_rec * 6 * sizeof(double);
+  h->roll_up.ensure(off_n + n_rec * sizeof(int));
+  unsigned char* up = h->roll_up.as<unsigned char>();
+  // (pageable host arrays: they are the caller's until the first synchronisation of the insert, which comes before this returns)
+  HIP_TRY(hipMemcpyAsync(up, sum_n3, off_c, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(up + off_c, covsum_n6, off_n - off_c, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(up + off_n, count_n, n_rec * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const RollRecs in{nullptr, reinterpret_cast<const double*>(up), reinterpret_cast<const double*>(up + off_c), reinterpret_cast<const int*>(up + off_n)};
+  try {
+    roll_insert_records(h, in, nullptr, (int)n_rec, T, entry, n_new_out, n_touched_out);
+  } catch (...) {
+    (void)hipStreamSynchronize(h->stream);  // an upload may still be pending: it must not outlive the caller's arrays
+    throw;
+  }
+}
+
+void roll_insert_map(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, size_t* n_touched_out) {
+  const char* entry = "ngicp_voxel_rolling_insert_map";
+  roll_require_on(h, entry);
+  if (!T) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null transform"};
+  if (from == h) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a map cannot be inserted into itself (ngicp_voxel_rolling_transform moves it)"};
+  if (h->device != from->device) throw ArgError{NGICP_ERR_ARG, std::string(entry) + " across devices is not supported"};
+  const size_t n = from->roll.n_vox;
+  if (n == 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the other handle's rolling map is empty"};
+  // the producer's stream may still be writing its map (a commit is left in the stream): this handle's stream waits, on the device.
+  // Its arrays are read up to the second synchronisation of the insert, which comes before this returns.
+  HIP_TRY(hipEventRecord(h->ev_fence, from->stream));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_fence, 0));
+  const RollRecs in{(const double*)from->roll.sums.as<double>(), nullptr, nullptr, nullptr};
+  roll_insert_records(h, in, nullptr, (int)n, T, entry, n_new_out, n_touched_out);
+}
+
+// The move in place.  An empty map stays empty.
+void roll_transform(ngicp* h, const float T[16], size_t* n_vox_out) {
+  const char* entry = "ngicp_voxel_rolling_transform";
+  roll_require_on(h, entry);
+  if (!T) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null transform"};
+  ngicp::RollMap& r = h->roll;
+  if (r.n_vox) {
+    const RollRecs in{(const double*)r.sums.as<double>(), nullptr, nullptr, nullptr};
+    roll_insert_records(h, in, (const long long*)r.stamps.as<long long>(), (int)r.n_vox, T, entry, nullptr, nullptr);
+  }
+  if (n_vox_out) *n_vox_out = r.n_vox;
+}
+
+// The restore.  Everything that can refuse is checked on the host before the map is touched.  One host synchronisation (the uploads
+// read the caller's arrays).
+void roll_set(ngicp* h, size_t n, const int* ijk, const double* sum_n3, const double* covsum_n6, const int* count_n, const long long* stamp_n, long long inserts) {
+  const char* entry = "ngicp_voxel_rolling_set";
+  roll_require_on(h, entry);
+  if (inserts < 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a negative insert counter"};
+  if (n && (!ijk || !sum_n3 || !covsum_n6 || !count_n || !stamp_n)) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null pointer"};
+  if (n > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": too many voxels for int indices"};
+  std::vector<std::pair<unsigned long long, int>> keyed(n);
+  for (size_t v = 0; v < n; ++v) {
+    const int ix = ijk[3 * v], iy = ijk[3 * v + 1], iz = ijk[3 * v + 2];
+    const auto in_range = [](int i) { return i > -kVoxBias && i < kVoxBias; };
+    if (!in_range(ix) || !in_range(iy) || !in_range(iz)) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": row " + std::to_string(v) + ": an index of 2^20 or more in magnitude"};
+    if (count_n[v] < 1) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": row " + std::to_string(v) + ": a count below 1"};
+    if (stamp_n[v] < 1 || stamp_n[v] > inserts) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": row " + std::to_string(v) + ": a stamp outside 1..inserts"};
+    keyed[v] = {((unsigned long long)(iz + kVoxBias) << 42) | ((unsigned long long)(iy + kVoxBias) << 21) | (unsigned long long)(ix + kVoxBias), (int)v};
+  }
+  std::sort(keyed.begin(), keyed.end());
+  for (size_t j = 1; j < n; ++j)
+    if (keyed[j].first == keyed[j - 1].first)
+      throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": rows " + std::to_string(keyed[j - 1].second) + " and " + std::to_string(keyed[j].second) + " name the same voxel"};
+  keyed = {};
+  // ---- from here on the map is written ----
+  ngicp::RollMap& r = h->roll;
+  h->hook_valid = 0;
+  r.n_vox = 0;  // (nothing of the former map is kept when an array grows)
+  r.inserts = inserts;
+  if (n == 0) {
+    if (r.slots) roll_refill_table(h);
+    return;
+  }
+  const size_t off_c = n * 3 * sizeof(double), off_n = off_c + n * 6 * sizeof(double), off_i = off_n + n * sizeof(int);
+  h->roll_up.ensure(off_i + n * 3 * sizeof(int));
+  roll_reserve(h, n);
+  unsigned char* up = h->roll_up.as<unsigned char>();
+  try {
+    HIP_TRY(hipMemcpyAsync(up, sum_n3, off_c, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(up + off_c, covsum_n6, off_n - off_c, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(up + off_n, count_n, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(up + off_i, ijk, n * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(r.stamps.p, stamp_n, n * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_rollrec_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, reinterpret_cast<const int*>(up + off_i), reinterpret_cast<const double*>(up),
+                       reinterpret_cast<const double*>(up + off_c), reinterpret_cast<const int*>(up + off_n), (int)n, r.sums.as<double>(), r.rec.as<double>(),
+                       r.vkeys.as<unsigned long long>());
+    r.n_vox = n;
+    if (!roll_reserve_table(h, n)) roll_refill_table(h);  // the key table, filled as after an eviction
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+  } catch (...) {
+    (void)hipStreamSynchronize(h->stream);  // an upload may still be pending: it must not outlive the caller's arrays
+    r.n_vox = 0;                            // a device failure half way: an empty map, not a half-written one
+    if (r.slots) (void)hipMemsetAsync(r.table.p, 0xff, r.slots * sizeof(ulonglong2), h->stream);
+    throw;
+  }
 }
 
 // Evict: flags, the scan, a stable compaction into the workspace, copies back, the table rebuilt.  One host synchronisation (the

@@ -98,6 +98,7 @@ EXPORTS = [
     "ngicp_set_voxel_submap_merge", "ngicp_get_voxel_submap_merge", "ngicp_voxelmap_merge_stats", "ngicp_keyframe_voxelmap_get",
     "ngicp_set_voxel_rolling", "ngicp_get_voxel_rolling", "ngicp_voxel_rolling_insert", "ngicp_voxel_rolling_evict", "ngicp_voxel_rolling_clear",
     "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
+    "ngicp_voxel_rolling_set", "ngicp_voxel_rolling_insert_voxels", "ngicp_voxel_rolling_insert_map", "ngicp_voxel_rolling_transform",
     "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
     "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
     "ngicp_deskew_cloud", "ngicp_preprocess_scan_deskewed",
@@ -221,6 +222,10 @@ def load_library() -> C.CDLL:
     L.ngicp_voxel_rolling_clear.argtypes = [vp]
     L.ngicp_voxel_rolling_get.argtypes = [vp, c_szp, c_i32p, c_f64p, c_f64p, c_i32p, c_i64p]
     L.ngicp_voxel_rolling_stats.argtypes = [vp, c_i64p, c_szp, c_szp, c_szp, c_f64p, c_f64p]
+    L.ngicp_voxel_rolling_set.argtypes = [vp, C.c_size_t, c_i32p, c_f64p, c_f64p, c_i32p, c_i64p, C.c_longlong]
+    L.ngicp_voxel_rolling_insert_voxels.argtypes = [vp, C.c_size_t, c_f64p, c_f64p, c_i32p, c_f32p, c_szp, c_szp]
+    L.ngicp_voxel_rolling_insert_map.argtypes = [vp, vp, c_f32p, c_szp, c_szp]
+    L.ngicp_voxel_rolling_transform.argtypes = [vp, c_f32p, c_szp]
     L.ngicp_set_robust_kernel.argtypes = [vp, C.c_int, C.c_double]
     L.ngicp_get_robust_kernel.argtypes = [vp, c_i32p, c_f64p]
     L.ngicp_robust_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, C.c_size_t, c_i32p]
@@ -431,6 +436,57 @@ class NanoGICP:
         ti, te = C.c_double(0), C.c_double(0)
         self._ck(self._L.ngicp_voxel_rolling_stats(self._h, C.byref(ins), C.byref(nv), C.byref(cap), C.byref(sl), C.byref(ti), C.byref(te)))
         return dict(inserts=ins.value, n_vox=nv.value, capacity_vox=cap.value, table_slots=sl.value, last_insert_ms=ti.value, last_evict_ms=te.value)
+
+    # ---- the rolling map from voxel records (include/ngicp.h "rolling voxel map: records") ----
+    @staticmethod
+    def _records(S, Cm, count):
+        """(S (n, 3), C (n, 3, 3) or (n, 6), count (n,)) as the contiguous arrays of the C ABI"""
+        s = np.ascontiguousarray(S, dtype=np.float64).reshape(-1, 3)
+        c = np.asarray(Cm, dtype=np.float64)
+        c6 = np.ascontiguousarray(c.reshape(-1, 9)[:, [0, 1, 2, 4, 5, 8]] if c.ndim == 3 else c.reshape(-1, 6))
+        cnt = np.asarray(count)
+        if cnt.size and (cnt.min() < -2**31 or cnt.max() > 2**31 - 1):
+            raise ValueError("a count outside the int range")
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32).reshape(-1)
+        if not (len(s) == len(c6) == len(cnt)):
+            raise ValueError(f"{len(s)} sums, {len(c6)} covariance sums and {len(cnt)} counts")
+        return s, c6, cnt
+
+    def setRollingVoxelMap(self, ijk, S, C_, count, stamp, inserts: int):
+        """The rolling map becomes exactly the given state (what rollingVoxelMap() and voxelRollingStats()['inserts'] return): voxel v
+        has key ijk[v], sums S[v], C[v], count[v] and stamp[v], numbered in array order; the insert counter becomes `inserts`.  A bad
+        argument (an index of 2^20 or more, a count below 1, a stamp outside 1..inserts, two equal ijk rows) raises and changes nothing."""
+        s, c6, cnt = self._records(S, C_, count)
+        k = np.ascontiguousarray(ijk, dtype=np.int32).reshape(-1, 3)
+        st = np.ascontiguousarray(stamp, dtype=np.int64).reshape(-1)
+        if not (len(k) == len(st) == len(s)):
+            raise ValueError(f"{len(k)} ijk rows, {len(st)} stamps and {len(s)} sums")
+        self._ck(self._L.ngicp_voxel_rolling_set(self._h, len(s), _p(k, c_i32p), _p(s, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p),
+                                                 _p(st, C.POINTER(C.c_longlong)), int(inserts)))
+
+    def insertVoxelsIntoVoxelMap(self, S, C_, count, T) -> tuple:
+        """Add voxel records (sums S (n, 3), covariance sums C (n, 3, 3) or (n, 6), counts) to the rolling map at the float pose T: every
+        record lands, whole, in the voxel of its moved mean.  -> (voxels created, destination voxels).  A refused insert raises and
+        changes nothing."""
+        s, c6, cnt = self._records(S, C_, count)
+        t = _colmajor16(T, np.float32); n_new, n_touched = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_insert_voxels(self._h, len(s), _p(s, c_f64p), _p(c6, c_f64p), _p(cnt, c_i32p), _p(t, c_f32p),
+                                                           C.byref(n_new), C.byref(n_touched)))
+        return n_new.value, n_touched.value
+
+    def insertVoxelMapFrom(self, other: "NanoGICP", T) -> tuple:
+        """insertVoxelsIntoVoxelMap of the other handle's rolling map, read on the device (it never passes through the host).  The other
+        handle need neither have the rolling setting on nor this handle's resolution; it is left unchanged."""
+        t = _colmajor16(T, np.float32); n_new, n_touched = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_insert_map(self._h, other._h, _p(t, c_f32p), C.byref(n_new), C.byref(n_touched)))
+        return n_new.value, n_touched.value
+
+    def transformVoxelMap(self, T) -> int:
+        """Move the rolling map by the float pose T in place: its former records inserted into an empty map.  The insert counter stays
+        and a voxel keeps the largest stamp of the records that landed in it.  -> voxels after the move."""
+        t = _colmajor16(T, np.float32); n = C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_transform(self._h, _p(t, c_f32p), C.byref(n)))
+        return n.value
 
     def setRobustKernel(self, kind, width: float = 1.0):
         """A robust kernel on every term of the cost (include/ngicp.h "robust kernel"): HUBER, CAUCHY or GEMAN_MCCLURE of the given width

@@ -606,6 +606,43 @@ class NanoGICP {
     if (h_) check(ngicp_voxel_rolling_stats(h_, &s.inserts, &s.n_vox, &s.capacity_vox, &s.table_slots, &s.last_insert_ms, &s.last_evict_ms), "voxelRollingStats");
     return s;
   }
+  // ---- the rolling map from voxel records (include/ngicp.h "rolling voxel map: records"): restore, merge, move ----
+  // The map becomes exactly `m` (what rollingVoxelMap() returned, here or in another session, on a handle of the same resolution) and
+  // the insert counter `inserts` (voxelRollingStats().inserts).  false: refused, nothing changed.
+  bool setRollingVoxelMap(const RollingVoxelMap& m, long long inserts) {
+    const size_t n = m.size();
+    if (m.ijk.size() != 3 * n || m.sum.size() != 3 * n || m.covsum.size() != 6 * n || m.stamp.size() != n) {
+      std::fprintf(stderr, "[NanoGICP] setRollingVoxelMap: arrays of different lengths\n");
+      return false;
+    }
+    return h_ && check(ngicp_voxel_rolling_set(h_, n, m.ijk.data(), m.sum.data(), m.covsum.data(), m.count.data(), m.stamp.data(), inserts), "setRollingVoxelMap");
+  }
+  // Add the records of `m` (its ijk and stamps are not read) at the float pose T: every record lands, whole, in the voxel of its moved
+  // mean.  Taking a map to another resolution is this at identity after setVoxelResolution - not the map the points would have built.
+  VoxelMapInsert insertVoxelsIntoVoxelMap(const RollingVoxelMap& m, const Matrix4& T) {
+    VoxelMapInsert r;
+    const size_t n = m.size();
+    if (m.sum.size() != 3 * n || m.covsum.size() != 6 * n) {
+      std::fprintf(stderr, "[NanoGICP] insertVoxelsIntoVoxelMap: arrays of different lengths\n");
+      return r;
+    }
+    r.ok = h_ && check(ngicp_voxel_rolling_insert_voxels(h_, n, m.sum.data(), m.covsum.data(), m.count.data(), T.data(), &r.n_new, &r.n_touched), "insertVoxelsIntoVoxelMap");
+    return r;
+  }
+  // The same with the records of `other`'s rolling map, read on the device; `other` (not *this) is left unchanged.
+  VoxelMapInsert insertVoxelMapFrom(NanoGICP& other, const Matrix4& T) {
+    VoxelMapInsert r;
+    r.ok = h_ && check(ngicp_voxel_rolling_insert_map(h_, other.h_, T.data(), &r.n_new, &r.n_touched), "insertVoxelMapFrom");
+    return r;
+  }
+  // Move the map by T in place (after a loop closure, say): the insert counter stays, a voxel keeps the largest stamp of the records
+  // that landed in it.  Returns the voxels after the move; `ok` false when it was refused (the map is as it was).
+  size_t transformVoxelMap(const Matrix4& T, bool* ok = nullptr) {
+    size_t n = 0;
+    const bool good = h_ && check(ngicp_voxel_rolling_transform(h_, T.data(), &n), "transformVoxelMap");
+    if (ok) *ok = good;
+    return n;
+  }
 
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
   // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN

@@ -326,6 +326,59 @@ int ngicp_voxel_rolling_evict(ngicp_t* h, const float centre[3], double max_dist
 int ngicp_voxel_rolling_clear(ngicp_t* h);
 int ngicp_voxel_rolling_get(ngicp_t* h, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n, long long* stamp_n);
 int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vox, size_t* capacity_vox, size_t* table_slots, double* last_insert_ms, double* last_evict_ms);
+/* --- rolling voxel map: records - restore, merge and move a map from its voxel sums (csrc/ngicp_voxel_rollrec.h) ----
+ * A RECORD is what ngicp_voxel_rolling_get returns per voxel: S (3 doubles), C (6 doubles: xx, xy, xz, yy, yz, zz), n (int, at least 1)
+ * and a stamp.  The state of the map is per-voxel sums, so it can be taken back, added to another map and moved without the points.
+ * All four entries return NGICP_ERR_STATE unless the rolling setting is on and res > 0, and - when they succeed - drop the
+ * correspondences and the hooks' state as the scan insert does.  None of them reads or changes the target slot, the last alignment's
+ * results or ngicp_voxelmap_builds.
+ *   restore: _set              the map becomes exactly the given state: voxel v has key ijk[v], sums S[v], C[v], n[v] and stamp stamp[v];
+ *                              the numbering is the array order; the insert counter becomes `inserts`.  S and C are taken as they are.
+ *                              The records the passes read are written by one division per entry, the key table is filled as after an
+ *                              eviction.  n_vox == 0 empties the map and sets the counter.  NGICP_ERR_ARG, and then nothing changes (map,
+ *                              numbering, counter, stamps, table): a null array with n_vox > 0, |i| >= 2^20 on any axis, a count below 1,
+ *                              a stamp outside 1..inserts, inserts < 0, two equal ijk rows (the message names both rows), more voxels
+ *                              than int indices allow.  Round trip: _get plus the `inserts` of _stats, _set on any handle with the same
+ *                              resolution, _get: the same bytes in every array.
+ *   insert of records at the   per record r, in ascending input index: m = S_r / (double)n_r (three divisions), p = (float)m per axis,
+ *   float pose T               q = T p in the order of the scan insert's transform; the destination voxel is the voxel of q by the mode's
+ *                              rule at h's resolution.  Per destination voxel, over its records in ascending input index, every sum
+ *                              started at 0.0: A = sum S_r, Cc = sum C_r (one addition per entry and record), N = sum n_r in integers;
+ *                              s_k = ((R[k][0]*A_0 + R[k][1]*A_1) + R[k][2]*A_2) + (double)N * (double)t_k, nothing fused;
+ *                              c = R Cc R^T, ONE rotation per destination voxel, evaluated as the scan insert's; R the row-major double
+ *                              image of T's float 3x3 block, t its float translation.  The commit is the scan insert's: an existing
+ *                              voxel gets one addition per entry, a new one starts from (s, c, N); new voxels are numbered in ascending
+ *                              (iz, iy, ix) behind the existing ones; the stamp is this insert's number and the counter advances by one;
+ *                              the records of the touched voxels are rewritten by one division per entry.
+ *                              NGICP_ERR_ARG, nothing written (all of it is found before the first write to the map; capacity and table
+ *                              stay as they were too): a record whose moved mean has no voxel (2^20 voxels or more from the origin, or
+ *                              not finite), a count below 1, a destination voxel whose count would pass 2^31 - 1, no records, null arrays.
+ *   A WHOLE SOURCE VOXEL       lands in the voxel of its moved mean.  That is the definition, with its consequences: several records
+ *                              may merge into one voxel; a map moved by T and then by T^-1 is not the original in general; a map taken
+ *                              to a coarser (or finer) resolution this way is not the map the points would have built.  With T the
+ *                              identity, q == p and both the rotation and the added N * 0 are exact: where every record's float mean
+ *                              lies in that record's own voxel, inserting a map into an empty map of the same resolution reproduces
+ *                              S, C and n bit for bit.
+ *   _insert_voxels             takes the records from host arrays (n_rec of them).
+ *   _insert_map                takes them from `from`'s rolling map on the device, in its numbering, without a pass through the host;
+ *                              h's stream waits for `from`'s on the device.  `from` need neither have the rolling setting on nor h's
+ *                              resolution: only its sums are read, and it is left unchanged.  NGICP_ERR_ARG: from == h, handles on
+ *                              different devices, an empty `from`.
+ *   move in place: _transform  the map becomes what the insert above gives for its own former records, in their former numbering,
+ *                              inserted into an empty map.  The insert counter stays.  A destination voxel's stamp is the largest stamp
+ *                              of the records that landed in it: ages survive a move, and evict(min_stamp) keeps working.  A refusal
+ *                              leaves the map as it was.  An empty map is a no-op that returns 0.  *n_vox_after: the voxels left.
+ * *n_new / *n_touched as for the scan insert: voxels created, destination voxels (created or added to).
+ * Host synchronisations: two per insert or move (the destination voxel count with the refusal flags; the number of new voxels with the
+ * overflow flag), both before the map is written; the commit is left in the handle's stream.  ngicp_voxel_rolling_stats'
+ * last_insert_ms also reports the last record insert or move; asking for it waits for that commit.  _set: one.
+ * Device memory on top of the map's: an insert of n records uses the voxel builds' sort buffers for n keys, 84 bytes per record of
+ * workspace (80 destination sums, 4 lookup result), 8 more per record for a move, and 76 per uploaded record (_insert_voxels; 88 for _set). */
+int ngicp_voxel_rolling_set(ngicp_t* h, size_t n_vox, const int* ijk_n3, const double* sum_n3, const double* covsum_n6, const int* count_n, const long long* stamp_n, long long inserts);
+int ngicp_voxel_rolling_insert_voxels(ngicp_t* h, size_t n_rec, const double* sum_n3, const double* covsum_n6, const int* count_n, const float T_colmajor[16], size_t* n_new_or_null,
+                                      size_t* n_touched_or_null);
+int ngicp_voxel_rolling_insert_map(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], size_t* n_new_or_null, size_t* n_touched_or_null);
+int ngicp_voxel_rolling_transform(ngicp_t* h, const float T_colmajor[16], size_t* n_vox_after_or_null);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
