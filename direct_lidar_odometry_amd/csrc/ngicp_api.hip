@@ -32,7 +32,6 @@
 #include "ngicp_voxel.h"
 #include "ngicp_voxel_batch.h"
 #include "ngicp_voxel_roll.h"
-#include "ngicp_voxel_rollrec.h"
 #include "ngicp_robust.h"
 
 using namespace ngk;
@@ -783,8 +782,7 @@ int ngicp_share_source_index(ngicp_t* dst, ngicp_t* src) {
     const bool same = (dst->src.identity != 0 && dst->src.identity == src->src.identity) || (dst->src.host == src->src.host && dst->src.n == src->src.n);
     if (same) {
       // dst's stream waits (on the device) for the index build src has enqueued: no host synchronisation per scan
-      HIP_TRY(hipEventRecord(dst->ev_fence, src->stream));
-      HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_fence, 0));
+      stream_wait_for(dst, src);
       dst->src.dev = src->src.dev;
     }
   });
@@ -819,8 +817,7 @@ int ngicp_copy_source_covs(ngicp_t* dst, ngicp_t* src) {
       return;
     }
     if (dst->device == src->device) {
-      HIP_TRY(hipEventRecord(dst->ev_fence, src->stream));  // the covariance kernel / reorder src has enqueued
-      HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_fence, 0));
+      stream_wait_for(dst, src);  // the covariance kernel / reorder src has enqueued
       dst->src_covs = src->src_covs;  // shares the immutable device buffer
     } else {
       throw ArgError{NGICP_ERR_ARG, "copy_source_covs across devices is not supported; use get/set"};
@@ -1357,7 +1354,7 @@ int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vo
   return NGICP_OK;
 }
 
-// ---- the rolling map from voxel records (include/ngicp.h "rolling voxel map: records"; ngicp_voxel_rollrec.h) ----
+// ---- the rolling map from voxel records (include/ngicp.h "rolling voxel map: records"; ngicp_voxel_roll.h) ----
 int ngicp_voxel_rolling_set(ngicp_t* h, size_t n_vox, const int* ijk_n3, const double* sum_n3, const double* covsum_n6, const int* count_n, const long long* stamp_n, long long inserts) {
   return guarded(h, [&] { roll_set(h, n_vox, ijk_n3, sum_n3, covsum_n6, count_n, stamp_n, inserts); });
 }

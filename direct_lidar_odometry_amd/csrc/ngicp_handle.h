@@ -275,7 +275,7 @@ struct ngicp {
   hipStream_t stream = nullptr;
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   hipEvent_t ev_cov_a = nullptr, ev_cov_b = nullptr;  // around the last covariance kernel; read lazily (ngicp_get_stats)
-  hipEvent_t ev_fence = nullptr;                       // fence_engine_streams()
+  hipEvent_t ev_fence = nullptr;                       // stream_wait_for()
   bool cov_timing_pending = false;
   std::string err;
   Params p;
@@ -417,7 +417,7 @@ struct ngicp {
     double last_insert_ms = 0.0, last_evict_ms = 0.0;  // device event times
   } roll;
   DevBuf roll_q, roll_sums, roll_hit, roll_tmp;  // an insert's transformed points, per-scan-voxel sums and lookup results; an eviction's compaction workspace
-  // the record routes (ngicp_voxel_rollrec.h): the uploaded arrays of a restore / a record insert, a move's per-voxel stamps
+  // the record routes: the uploaded arrays of a restore / a record insert, a move's per-voxel stamps
   DevBuf roll_up, roll_seg_stamp;
   hipEvent_t ev_rec_a = nullptr, ev_rec_b = nullptr;  // around a record insert, whose commit is left in the stream:
   bool rec_time_pending = false;                      // its time is read when it is next asked for (roll_resolve_time)
@@ -428,14 +428,17 @@ struct ngicp {
 
 namespace {
 
+// h's stream waits, on the device, for what `other`'s stream (same device) holds now; the host does not wait
+void stream_wait_for(ngicp* h, ngicp* other) {
+  HIP_TRY(hipEventRecord(h->ev_fence, other->stream));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_fence, 0));
+}
+
 void fence_engine_streams(ngicp* h) {
   HandleRegistry& r = registry();
   std::lock_guard<std::mutex> lock(r.m);
-  for (ngicp* o : r.live) {
-    if (o == h || o->device != h->device) continue;  // (work on h's own stream is ordered before anything h enqueues next)
-    HIP_TRY(hipEventRecord(h->ev_fence, o->stream));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_fence, 0));
-  }
+  for (ngicp* o : r.live)
+    if (o != h && o->device == h->device) stream_wait_for(h, o);  // (work on h's own stream is ordered before anything h enqueues next)
 }
 
 template <class F>

@@ -1,13 +1,12 @@
-// The rolling voxel map's host code (ngicp_voxel_roll.h; include/ngicp.h "rolling voxel map"): insert, evict, clear and
-// the growth of its arrays and table; behind them the record routes (ngicp_voxel_rollrec.h): restore, insert of
-// records, handle-to-handle insert, move in place.  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose
-// size_voxel_work / voxel_segments number a scan's voxels).
+// The rolling voxel map's host code (ngicp_voxel_roll.h; include/ngicp.h "rolling voxel map"): insert, evict, clear and the growth of its
+// arrays and table; behind them the record routes: restore, insert of records, handle-to-handle insert,
+// move in place.  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose size_voxel_work /
+// voxel_segments / read_count / exclusive_scan_flags number a scan's voxels).
 #pragma once
 
 namespace {
 
 constexpr size_t kRollMinCap = 1024;  // voxels the per-voxel arrays start with
-constexpr size_t kRollMinSlots = 64;  // (the target map's smallest table)
 
 // A buffer of the rolling map to `bytes`, its first `live` bytes kept: DevBuf::ensure frees, so a new allocation, a device-to-device copy
 // and only then the old one's release.  The caller's stream is idle or holds only work that the copy is ordered behind.
@@ -55,8 +54,7 @@ void roll_refill_table(ngicp* h) {
 bool roll_reserve_table(ngicp* h, size_t need) {
   ngicp::RollMap& r = h->roll;
   if (r.slots && r.slots >= 2 * need) return false;
-  size_t slots = std::max(r.slots, kRollMinSlots);
-  while (slots < 2 * need) slots <<= 1;
+  const size_t slots = voxel_table_slots(need, r.slots);
   r.table.ensure(slots * sizeof(ulonglong2));  // (its contents are rebuilt, not kept)
   r.slots = slots;
   roll_refill_table(h);
@@ -75,6 +73,23 @@ void roll_require_on(const ngicp* h, const char* entry) {
   if (!h->voxel_roll) throw ArgError{NGICP_ERR_STATE, std::string(entry) + ": the rolling setting is off (ngicp_set_voxel_rolling)"};
 }
 
+RollPose roll_pose(const float T[16]) {
+  RollPose P;
+  std::memcpy(P.m, T, sizeof(P.m));
+  for (int row = 0; row < 3; ++row)
+    for (int col = 0; col < 3; ++col) P.R[row * 3 + col] = (double)T[col * 4 + row];
+  return P;
+}
+
+// The commit of an insert's n_seg scan / destination voxels (sums in roll_sums, lookup results in roll_hit, ranks of the new ones in
+// `rank`) onto the map from voxel `base` on; the stamp is the next insert's number, or seg_stamp[u] (the move in place).
+void roll_launch_commit(ngicp* h, const VoxelSegments& sg, int n_seg, const int* rank, size_t base, const long long* seg_stamp) {
+  ngicp::RollMap& r = h->roll;
+  hipLaunchKernelGGL(k_roll_commit, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.seg_start, n_seg, (const double*)h->roll_sums.as<double>(),
+                     (const int*)h->roll_hit.as<int>(), rank, (int)base, r.inserts + 1, seg_stamp, r.sums.as<double>(), r.rec.as<double>(), r.vkeys.as<unsigned long long>(),
+                     r.stamps.as<long long>(), r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1));
+}
+
 // Insert `from`'s source cloud at the float pose T.  Two host synchronisations: the scan's voxel count with the `bad` flag (the refusal,
 // and what sizes the arrays and the table), and the number of new voxels behind the commit.  An insert that grows an array waits for
 // that array's copy as well.
@@ -85,19 +100,13 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   // the covariances the producer holds for its source; computed now if absent, with the producer's k / regularisation (ngicp_keyframe_add)
   if (from->src_covs.n != from->src.dev->n) compute_covs(from, from->src, from->src_covs, "source");
   const double* covs = covs_for(from, from->src_covs, from->src.dev);  // in the cloud's own sorted order
-  if (from != h) {  // the producer's stream may still be writing them: this handle's stream waits, on the device
-    HIP_TRY(hipEventRecord(h->ev_fence, from->stream));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_fence, 0));
-  }
+  if (from != h) stream_wait_for(h, from);  // the producer's stream may still be writing them
   const std::shared_ptr<DeviceCloud> cloud = from->src.dev;  // held until the last kernel that reads it has been waited for
   const std::shared_ptr<DevBuf> cov_hold = from->src_covs.data;
   ngicp::RollMap& r = h->roll;
   const int n = (int)cloud->n;
   if (n <= 0) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_rolling_insert: empty source cloud"};
-  RollPose P;
-  std::memcpy(P.m, T, sizeof(P.m));
-  for (int row = 0; row < 3; ++row)
-    for (int col = 0; col < 3; ++col) P.R[row * 3 + col] = (double)T[col * 4 + row];
+  const RollPose P = roll_pose(T);
   const float inv_res = 1.0f / (float)h->voxel_res;
   size_voxel_work(h, (size_t)n);
   h->roll_q.ensure((size_t)n * sizeof(float4));
@@ -108,11 +117,7 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   hipLaunchKernelGGL(k_roll_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, cloud->pts(), n, P, inv_res, h->roll_q.as<float4>(),
                      h->vox_keys.as<unsigned long long>(), h->vox_vals.as<int>(), h->vox_flag.as<int>());
   const VoxelSegments sg = voxel_segments(h, n);
-  int n_seg = 0, bad = 0;
-  HIP_TRY(hipMemcpyAsync(&n_seg, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const auto [n_seg, bad] = read_count(h, sg.n_seg_dev, true);
   // the refusal comes before anything of the map is written: map, counter and stamps stay as they were
   if (bad)
     throw ArgError{NGICP_ERR_ARG, "rolling voxel map: a transformed point lies 2^20 voxels or more from the origin on some axis (or is not finite); nothing was inserted"};
@@ -122,24 +127,15 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   if (r.n_vox + (size_t)n_seg > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "rolling voxel map: too many voxels for int indices"};
   roll_reserve(h, r.n_vox + (size_t)n_seg);
   roll_reserve_table(h, r.n_vox + (size_t)n_seg);
-  const unsigned blocks = (unsigned)((n_seg + 255) / 256);
-  const int ntiles = (n_seg + kScanTile - 1) / kScanTile;
   int* is_new = h->vox_scan.as<int>();  // (voxel_segments' head and prefix arrays are free again; keys, order and seg_start are not)
   int* rank = is_new + n;               // n_seg + 1 + kCellPad <= n + 1 + kCellPad entries
-  hipLaunchKernelGGL(k_roll_lookup, dim3(blocks), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_seg, (const float4*)h->roll_q.as<float4>(), covs, P,
-                     (const ulonglong2*)r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1), h->roll_sums.as<double>(), h->roll_hit.as<int>(), is_new);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)is_new, n_seg, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)is_new, n_seg, (const int*)h->tile_sums.as<int>(), rank);
-  hipLaunchKernelGGL(k_roll_commit, dim3(blocks), dim3(256), 0, h->stream, sg.keys, sg.seg_start, n_seg, (const double*)h->roll_sums.as<double>(), (const int*)h->roll_hit.as<int>(),
-                     (const int*)rank, (int)r.n_vox, r.inserts + 1, r.sums.as<double>(), r.rec.as<double>(), r.vkeys.as<unsigned long long>(), r.stamps.as<long long>(),
-                     r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1));
+  hipLaunchKernelGGL(k_roll_lookup, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_seg, (const float4*)h->roll_q.as<float4>(), covs,
+                     P, (const ulonglong2*)r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1), h->roll_sums.as<double>(), h->roll_hit.as<int>(), is_new);
+  exclusive_scan_flags(h, is_new, n_seg, rank);
+  roll_launch_commit(h, sg, n_seg, rank, r.n_vox, nullptr);
   HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
-  int n_new = 0;
-  HIP_TRY(hipMemcpyAsync(&n_new, rank + n_seg, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   h->hook_valid = 0;  // (from here on the map is being written)
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const int n_new = read_count(h, rank + n_seg).count;
   if (n_new < 0 || n_new > n_seg) throw ArgError{NGICP_ERR_HIP, "rolling voxel map insert: inconsistent count of new voxels"};
   r.n_vox += (size_t)n_new;
   ++r.inserts;
@@ -150,7 +146,7 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   if (n_touched_out) *n_touched_out = (size_t)n_seg;
 }
 
-// ---- the record routes (ngicp_voxel_rollrec.h; include/ngicp.h "rolling voxel map: records") ----
+// ---- the record routes (include/ngicp.h "rolling voxel map: records") ----
 // The device time of the last record insert or move: its commit was left in the stream, so the time is read when somebody asks
 // (ngicp_voxel_rolling_stats: wait = true) or, without waiting, before the events are recorded again - a commit still running then
 // loses its time, not the host's.
@@ -163,14 +159,6 @@ void roll_resolve_time(ngicp* h, bool wait) {
     return;
   }
   if (hipEventElapsedTime(&ms, h->ev_rec_a, h->ev_rec_b) == hipSuccess) h->roll.last_insert_ms = ms;
-}
-
-RollPose roll_pose(const float T[16]) {
-  RollPose P;
-  std::memcpy(P.m, T, sizeof(P.m));
-  for (int row = 0; row < 3; ++row)
-    for (int col = 0; col < 3; ++col) P.R[row * 3 + col] = (double)T[col * 4 + row];
-  return P;
 }
 
 // Insert n records at the float pose T (include/ngicp.h: "insert of records").  in / stamps_in are device arrays that stay valid until
@@ -194,33 +182,21 @@ void roll_insert_records(ngicp* h, const RollRecs& in, const long long* stamps_i
   hipLaunchKernelGGL(k_rollrec_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, in, n, P, inv_res, h->vox_keys.as<unsigned long long>(), h->vox_vals.as<int>(),
                      h->vox_flag.as<int>());
   const VoxelSegments sg = voxel_segments(h, n);
-  int n_seg = 0, flag = 0;
-  HIP_TRY(hipMemcpyAsync(&n_seg, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&flag, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const auto [n_seg, flag] = read_count(h, sg.n_seg_dev, true);
   if (flag & kRecBadCount) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a record's count is below 1; nothing was written"};
   if (flag & kRecNoVoxel)
     throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a record's moved mean lies 2^20 voxels or more from the origin on some axis (or is not finite); nothing was written"};
   if (n_seg <= 0 || n_seg > n) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent voxel count"};
-  const unsigned blocks = (unsigned)((n_seg + 255) / 256);
-  const int ntiles = (n_seg + kScanTile - 1) / kScanTile;
   int* is_new = h->vox_scan.as<int>();  // (as roll_insert: the head and prefix arrays are free again; keys, order and seg_start are not)
   int* rank = is_new + n;
   const bool probe = !move && r.slots && r.n_vox;  // (an empty map, or the move's empty destination: every voxel is new)
   long long* seg_stamp = move ? h->roll_seg_stamp.as<long long>() : nullptr;
-  hipLaunchKernelGGL(k_rollrec_lookup, dim3(blocks), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_seg, in, stamps_in, P,
+  hipLaunchKernelGGL(k_rollrec_lookup, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_seg, in, stamps_in, P,
                      probe ? (const ulonglong2*)r.table.as<ulonglong2>() : (const ulonglong2*)nullptr, (unsigned int)(r.slots ? r.slots - 1 : 0), (const double*)r.sums.as<double>(),
                      h->roll_sums.as<double>(), h->roll_hit.as<int>(), is_new, seg_stamp, h->vox_flag.as<int>());
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)is_new, n_seg, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)is_new, n_seg, (const int*)h->tile_sums.as<int>(), rank);
-  int n_new = 0;
-  HIP_TRY(hipMemcpyAsync(&n_new, rank + n_seg, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&flag, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
-  if (flag & kRecOverflow) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a voxel's count would pass 2^31 - 1; nothing was written"};
+  exclusive_scan_flags(h, is_new, n_seg, rank);
+  const auto [n_new, lookup_flag] = read_count(h, rank + n_seg, true);
+  if (lookup_flag & kRecOverflow) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": a voxel's count would pass 2^31 - 1; nothing was written"};
   if (n_new < 0 || n_new > n_seg || (move && n_new != n_seg)) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent count of new voxels"};
   const size_t base = move ? 0 : r.n_vox;
   if (base + (size_t)n_new > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": too many voxels for int indices"};
@@ -229,9 +205,7 @@ void roll_insert_records(ngicp* h, const RollRecs& in, const long long* stamps_i
   if (move) r.n_vox = 0;  // nothing of the former arrays is kept: the destination sums are in the workspace
   roll_reserve(h, base + (size_t)n_new);
   if (!roll_reserve_table(h, base + (size_t)n_new) && move) roll_refill_table(h);  // (n_vox == 0: the table cleared)
-  hipLaunchKernelGGL(k_rollrec_commit, dim3(blocks), dim3(256), 0, h->stream, sg.keys, sg.seg_start, n_seg, (const double*)h->roll_sums.as<double>(), (const int*)h->roll_hit.as<int>(),
-                     (const int*)rank, (int)base, r.inserts + 1, (const long long*)seg_stamp, r.sums.as<double>(), r.rec.as<double>(), r.vkeys.as<unsigned long long>(),
-                     r.stamps.as<long long>(), r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1));
+  roll_launch_commit(h, sg, n_seg, rank, base, seg_stamp);
   HIP_TRY(hipEventRecord(h->ev_rec_b, h->stream));
   HIP_TRY(hipGetLastError());
   h->rec_time_pending = true;
@@ -241,21 +215,27 @@ void roll_insert_records(ngicp* h, const RollRecs& in, const long long* stamps_i
   if (n_touched_out) *n_touched_out = (size_t)n_seg;
 }
 
+// The three record arrays of the C ABI into roll_up, one behind the other, with `extra_bytes` of room behind them (*extra: where).  The
+// copies read pageable host arrays: they are the caller's until the next synchronisation, which the caller of this guarantees.
+RollRecs roll_upload_records(ngicp* h, size_t n, const double* sum_n3, const double* covsum_n6, const int* count_n, size_t extra_bytes = 0, unsigned char** extra = nullptr) {
+  const size_t off_c = n * 3 * sizeof(double), off_n = off_c + n * 6 * sizeof(double), off_x = off_n + n * sizeof(int);
+  h->roll_up.ensure(off_x + extra_bytes);
+  unsigned char* up = h->roll_up.as<unsigned char>();
+  HIP_TRY(hipMemcpyAsync(up, sum_n3, off_c, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(up + off_c, covsum_n6, off_n - off_c, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(up + off_n, count_n, off_x - off_n, hipMemcpyHostToDevice, h->stream));
+  if (extra) *extra = up + off_x;
+  return RollRecs{nullptr, reinterpret_cast<const double*>(up), reinterpret_cast<const double*>(up + off_c), reinterpret_cast<const int*>(up + off_n)};
+}
+
 void roll_insert_voxels(ngicp* h, size_t n_rec, const double* sum_n3, const double* covsum_n6, const int* count_n, const float T[16], size_t* n_new_out, size_t* n_touched_out) {
   const char* entry = "ngicp_voxel_rolling_insert_voxels";
   roll_require_on(h, entry);
   if (!sum_n3 || !covsum_n6 || !count_n || !T) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null pointer"};
   if (n_rec == 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": no records"};
   if (n_rec > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": too many records for int indices"};
-  const size_t off_c = n_rec * 3 * sizeof(double), off_n = off_c + n_rec * 6 * sizeof(double);
-  h->roll_up.ensure(off_n + n_rec * sizeof(int));
-  unsigned char* up = h->roll_up.as<unsigned char>();
-  // (pageable host arrays: they are the caller's until the first synchronisation of the insert, which comes before this returns)
-  HIP_TRY(hipMemcpyAsync(up, sum_n3, off_c, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(up + off_c, covsum_n6, off_n - off_c, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(up + off_n, count_n, n_rec * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  const RollRecs in{nullptr, reinterpret_cast<const double*>(up), reinterpret_cast<const double*>(up + off_c), reinterpret_cast<const int*>(up + off_n)};
-  try {
+  try {  // (the first synchronisation of the insert comes before this returns)
+    const RollRecs in = roll_upload_records(h, n_rec, sum_n3, covsum_n6, count_n);
     roll_insert_records(h, in, nullptr, (int)n_rec, T, entry, n_new_out, n_touched_out);
   } catch (...) {
     (void)hipStreamSynchronize(h->stream);  // an upload may still be pending: it must not outlive the caller's arrays
@@ -273,8 +253,7 @@ void roll_insert_map(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out
   if (n == 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the other handle's rolling map is empty"};
   // the producer's stream may still be writing its map (a commit is left in the stream): this handle's stream waits, on the device.
   // Its arrays are read up to the second synchronisation of the insert, which comes before this returns.
-  HIP_TRY(hipEventRecord(h->ev_fence, from->stream));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_fence, 0));
+  stream_wait_for(h, from);
   const RollRecs in{(const double*)from->roll.sums.as<double>(), nullptr, nullptr, nullptr};
   roll_insert_records(h, in, nullptr, (int)n, T, entry, n_new_out, n_touched_out);
 }
@@ -323,19 +302,14 @@ void roll_set(ngicp* h, size_t n, const int* ijk, const double* sum_n3, const do
     if (r.slots) roll_refill_table(h);
     return;
   }
-  const size_t off_c = n * 3 * sizeof(double), off_n = off_c + n * 6 * sizeof(double), off_i = off_n + n * sizeof(int);
-  h->roll_up.ensure(off_i + n * 3 * sizeof(int));
   roll_reserve(h, n);
-  unsigned char* up = h->roll_up.as<unsigned char>();
   try {
-    HIP_TRY(hipMemcpyAsync(up, sum_n3, off_c, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(up + off_c, covsum_n6, off_n - off_c, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(up + off_n, count_n, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(up + off_i, ijk, n * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    unsigned char* ijk_dev = nullptr;
+    const RollRecs up = roll_upload_records(h, n, sum_n3, covsum_n6, count_n, n * 3 * sizeof(int), &ijk_dev);
+    HIP_TRY(hipMemcpyAsync(ijk_dev, ijk, n * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(r.stamps.p, stamp_n, n * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_rollrec_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, reinterpret_cast<const int*>(up + off_i), reinterpret_cast<const double*>(up),
-                       reinterpret_cast<const double*>(up + off_c), reinterpret_cast<const int*>(up + off_n), (int)n, r.sums.as<double>(), r.rec.as<double>(),
-                       r.vkeys.as<unsigned long long>());
+    hipLaunchKernelGGL(k_rollrec_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, reinterpret_cast<const int*>(ijk_dev), up.S, up.C, up.cnt, (int)n,
+                       r.sums.as<double>(), r.rec.as<double>(), r.vkeys.as<unsigned long long>());
     r.n_vox = n;
     if (!roll_reserve_table(h, n)) roll_refill_table(h);  // the key table, filled as after an eviction
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -363,7 +337,6 @@ void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_
   const size_t rec_bytes = (size_t)n * kVoxRec * sizeof(double);
   h->roll_tmp.ensure(2 * rec_bytes + (size_t)n * 16);
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  const int ntiles = (n + kScanTile - 1) / kScanTile;
   int* keep = h->vox_scan.as<int>();
   int* rank = keep + n;  // n + 1 + kCellPad entries
   double* sums_o = h->roll_tmp.as<double>();
@@ -373,15 +346,10 @@ void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_
   HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
   hipLaunchKernelGGL(k_roll_evict_flags, dim3(blocks), dim3(256), 0, h->stream, (const unsigned long long*)r.vkeys.as<unsigned long long>(), (const long long*)r.stamps.as<long long>(), n,
                      h->voxel_res, (double)centre[0], (double)centre[1], (double)centre[2], max_dist, min_stamp, keep);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)keep, n, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)keep, n, (const int*)h->tile_sums.as<int>(), rank);
+  exclusive_scan_flags(h, keep, n, rank);
   hipLaunchKernelGGL(k_roll_compact, dim3(blocks), dim3(256), 0, h->stream, (const int*)keep, (const int*)rank, n, (const double*)r.sums.as<double>(), (const double*)r.rec.as<double>(),
                      (const unsigned long long*)r.vkeys.as<unsigned long long>(), (const long long*)r.stamps.as<long long>(), sums_o, rec_o, vkeys_o, stamps_o);
-  int n_keep = 0;
-  HIP_TRY(hipMemcpyAsync(&n_keep, rank + n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const int n_keep = read_count(h, rank + n).count;
   if (n_keep < 0 || n_keep > n) throw ArgError{NGICP_ERR_HIP, "rolling voxel map evict: inconsistent count of survivors"};
   if (n_keep < n) {
     const size_t k = (size_t)n_keep;

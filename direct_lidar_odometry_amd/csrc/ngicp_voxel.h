@@ -30,7 +30,7 @@
 //   vgicp_pass_body / vgicp_pass_n_body<K>   what the two kernels do once they hold the state's pose and flags, as inlined functions:
 //                                 k_vgicp_pass_batch<K> (ngicp_voxel_batch.h) runs the same bodies on a lane's record.
 //   shared pieces, each defined once   voxel_cell / voxel_pack (-> voxel_key), voxel_probe_from (-> voxel_lookup, and the neighbourhoods'
-//                                 probe continuation), voxel_segment_sums and voxel_table_insert (the map's fill kernels), voxel_pass_begin
+//                                 probe continuation), voxel_segment_sums, voxel_table_insert and voxel_record_from_sums (every map's fill kernels), voxel_pass_begin
 //                                 (the single kernels' head), voxel_block_row (a pass block's row); through ngicp_pass.h: load_pose (ngicp_lm.h),
 //                                 transform_point_rowmajor_f (ngicp_search.h), lin_terms / err_term (ngicp_terms.h: the exact pass's K3 and its error leg).
 //   merged voxel map              (a setting, off by default) the map of a submap from sums its keyframes carry:
@@ -131,6 +131,14 @@ __device__ __forceinline__ void voxel_table_insert(ulonglong2* __restrict__ tabl
   }
 }
 
+// the record of a voxel from its ten sums {S 3, C 6, n}: one division per entry, the count kept
+__device__ __forceinline__ void voxel_record_from_sums(const double (&S)[kVoxRec], double* __restrict__ r) {
+  const double cnt = S[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) r[k] = S[k] / cnt;
+  r[9] = cnt;
+}
+
 // keys[o] / vals[o] for ORIGINAL target index o (the sort is stable: a voxel's points stay in ascending original index); vals = the
 // point's position in the cell-sorted cloud, where its coordinates and covariance are.  *bad != 0: a point without a voxel.
 __global__ void __launch_bounds__(256) k_voxel_map_keys(const float4* __restrict__ pts, int n, float inv_res, unsigned long long* __restrict__ keys, int* __restrict__ vals,
@@ -168,13 +176,8 @@ __global__ void __launch_bounds__(256) k_voxel_map_fill(const unsigned long long
   const int s = seg_start[v], e = seg_start[v + 1];
   double m[3], c[6];
   voxel_segment_sums(order, s, e, pts, covs, m, c);
-  const double cnt = (double)(e - s);
-  double* r = rec + (size_t)v * kVoxRec;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r[k] = m[k] / cnt;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) r[3 + k] = c[k] / cnt;
-  r[9] = cnt;
+  const double S[kVoxRec] = {m[0], m[1], m[2], c[0], c[1], c[2], c[3], c[4], c[5], (double)(e - s)};
+  voxel_record_from_sums(S, rec + (size_t)v * kVoxRec);
   const unsigned long long key = keys[s];
   vkeys[v] = key;
   voxel_table_insert(table, mask, key, v);
@@ -239,11 +242,7 @@ __global__ void __launch_bounds__(256) k_voxel_merge_fill(const unsigned long lo
       for (int k = 0; k < kVoxRec; ++k) S[k] = S[k] + r[k];
     }
   }
-  const double cnt = S[9];
-  double* out = rec + (size_t)v * kVoxRec;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) out[k] = S[k] / cnt;
-  out[9] = cnt;
+  voxel_record_from_sums(S, rec + (size_t)v * kVoxRec);
   const unsigned long long key = keys[s];
   vkeys[v] = key;
   voxel_table_insert(table, mask, key, v);

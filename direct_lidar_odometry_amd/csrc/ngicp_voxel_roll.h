@@ -1,24 +1,33 @@
-// The rolling voxel map (include/ngicp.h "rolling voxel map"): a voxel map that lives across frames.  Scans are added to
-// it at a pose, old voxels are dropped from it, and the voxelized passes (ngicp_voxel.h) align against it unchanged: they read
-// {table, mask, rec, n_vox} and do not care who filled them.  The project's own definition; no fidelity to an outside library is claimed.
+// The rolling voxel map (include/ngicp.h "rolling voxel map" and "rolling voxel map: records"): a voxel map that
+// lives across frames.  Scans are added to it at a pose, voxel RECORDS (what ngicp_voxel_rolling_get returns per voxel, {S 3, C 6, n},
+// plus a stamp) are restored into it, added to it at a pose or moved in place, old voxels are dropped from it, and the voxelized passes
+// (ngicp_voxel.h) align against it unchanged: they read {table, mask, rec, n_vox} and do not care who filled them.  The project's own
+// definition; no fidelity to an outside library is claimed.
 //
-//   state per voxel v             sums[v] = {S 3, C 6 (xx, xy, xz, yy, yz, zz), n} in double, stamp[v] = the number of the last insert that
-//                                 added a point, vkeys[v] = the voxel's key, and rec[v] = {S / n, C / n, n}: the kVoxRec record the passes
-//                                 read.  Voxels are numbered in order of first insertion.
-//   insert of a scan at pose T    k_roll_keys       one thread per scan point: q = transform_point_f(T, a) kept in qpts (sorted position), the
-//                                                   key of q and the sorted position by ORIGINAL index; *bad when q has no voxel
-//                                 voxel_segments    (ngicp_voxelmap.h) stable sort, heads, scan, starts - over the scan's points only
-//                                 k_roll_lookup     one thread per scan voxel: voxel_segment_sums over qpts, ONE rotate_sym of the covariance
-//                                                   sum, one read-only voxel_lookup: the existing number or -1, and the flag "new"
-//                                 (the three-kernel exclusive scan over the flags: a new voxel's rank, in ascending key)
-//                                 k_roll_commit     one thread per scan voxel: an existing voxel gets one addition per entry, a new one is
-//                                                   appended at n_vox + rank and entered into the table; the stamp; the record by one division
-//                                 Lookup and commit are separate launches: no probe races an insertion.  Distinct threads own distinct
-//                                 voxels: nothing depends on the order in which threads arrive.  Nothing walks the existing map.
-//   table                         ngicp_voxel.h's, at most half full.  k_roll_table_fill enters the keys [0, n) into a cleared table: the
-//                                 rebuild at twice the size before a commit that would cross the limit, and after an eviction.
-//   evict                         k_roll_evict_flags (keep = 0 / 1 per voxel), the same scan, k_roll_compact into a workspace (stable: the
-//                                 survivors keep their order), copies back, table rebuild.
+//   state per voxel v    sums[v] = {S 3, C 6 (xx, xy, xz, yy, yz, zz), n} in double, stamp[v] = the number of the last insert that added to it,
+//                        vkeys[v] = the voxel's key, and rec[v] = {S / n, C / n, n}: the kVoxRec record the passes read
+//                        (voxel_record_from_sums).  Voxels are numbered in order of first insertion.
+//   step                 insert of a scan at pose T (ngicp_voxel_rolling_insert)     insert of records at pose T (_insert_voxels / _insert_map / _transform)
+//   keys                 k_roll_keys: one thread per scan point, q = transform_point_f  k_rollrec_keys: one thread per record, m = S / n (three divisions),
+//                        (T, a) kept in qpts (sorted position), the key of q and the     p = (float)m, q = transform_point_f(T, p), the key of q;
+//                        sorted position by ORIGINAL index; *bad when q has no voxel     keys[r] / vals[r] = r; flag bits kRecNoVoxel, kRecBadCount
+//   numbering            voxel_segments (ngicp_voxelmap.h): stable sort, heads, scan, starts - over the scan's points or the records only
+//   lookup               k_roll_lookup: one thread per scan voxel,                      k_rollrec_lookup: one thread per destination voxel, A = sum S_r,
+//                        voxel_segment_sums over qpts, ONE rotate_sym of the             Cc = sum C_r from 0.0 in ascending input index, N = sum n_r in
+//                        covariance sum                                                  integers, the segment's largest stamp (the move), s = R A + N t,
+//                                                                                        ONE rotate_sym; flag bit kRecOverflow past 2^31 - 1
+//                        both end in roll_store_lookup: the ten sums stored, one read-only voxel_lookup, the existing number or -1, the flag "new"
+//   ranks                exclusive_scan_flags (ngicp_voxelmap.h) over the flags: a new voxel's rank, in ascending key
+//   commit               k_roll_commit: one thread per scan / destination voxel: an existing voxel gets one addition per entry, a new one is
+//                        appended at n_vox + rank and entered into the table; the stamp (the insert's number, or per destination voxel for the
+//                        move); the record by one division
+//   restore              k_rollrec_fill: one thread per voxel, the key from ijk, the sums as given, the record (k_roll_table_fill follows)
+//   table                ngicp_voxel.h's, at most half full.  k_roll_table_fill enters the keys [0, n) into a cleared table: the rebuild at
+//                        twice the size before a commit that would cross the limit, after an eviction and after a restore.
+//   evict                k_roll_evict_flags (keep = 0 / 1 per voxel), the same scan, k_roll_compact into a workspace (stable: the survivors
+//                        keep their order), copies back, table rebuild.
+// Lookup and commit are separate launches: no probe races an insertion.  Distinct threads own distinct voxels and nothing is added
+// atomically: nothing depends on the order in which threads arrive.  Nothing walks the existing map.
 #pragma once
 #include "ngicp_cloudops.h"
 #include "ngicp_voxel.h"
@@ -46,6 +55,25 @@ __global__ void __launch_bounds__(256) k_roll_keys(const float4* __restrict__ pt
   vals[o] = s;
 }
 
+// The ending both lookups share: a scan / destination voxel's sums {s 3, rc 6, n} stored, the map's number of its key (or -1; a null
+// table holds no voxel) into *hit, *is_new = 1 when the map does not have it.  The table is only read.  Returns the number.
+__device__ __forceinline__ int roll_store_lookup(const double (&s)[3], const double (&rc)[6], double n, const ulonglong2* __restrict__ table, unsigned int mask,
+                                                 unsigned long long key, double* __restrict__ o, int* __restrict__ hit, int* __restrict__ is_new) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[k] = s[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[3 + k] = rc[k];
+  o[9] = n;
+  int v = -1;
+  if (table) {
+    unsigned int probes = 0;
+    v = voxel_lookup(table, mask, key, probes);
+  }
+  *hit = v;
+  *is_new = v < 0 ? 1 : 0;
+  return v;
+}
+
 // One thread per scan voxel u: its sums {s 3, rotate_sym(R, sum C) 6, n} into scan_sums[u], the map's number of its key (or -1) into
 // hit[u], is_new[u] = 1 when the map does not have it.  The table is only read.
 __global__ void __launch_bounds__(256) k_roll_lookup(const unsigned long long* __restrict__ keys, const int* __restrict__ order, const int* __restrict__ seg_start, int n_seg,
@@ -57,32 +85,16 @@ __global__ void __launch_bounds__(256) k_roll_lookup(const unsigned long long* _
   double m[3], c[6], rc[6];
   voxel_segment_sums(order, s, e, qpts, covs, m, c);
   rotate_sym(T.R, c, rc);
-  double* o = scan_sums + (size_t)u * kVoxRec;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) o[k] = m[k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[3 + k] = rc[k];
-  o[9] = (double)(e - s);
-  unsigned int probes = 0;
-  const int v = voxel_lookup(table, mask, keys[s], probes);
-  hit[u] = v;
-  is_new[u] = v < 0 ? 1 : 0;
+  roll_store_lookup(m, rc, (double)(e - s), table, mask, keys[s], scan_sums + (size_t)u * kVoxRec, hit + u, is_new + u);
 }
 
-// the record of a voxel from its sums: one division per entry
-__device__ __forceinline__ void roll_write_record(const double (&S)[kVoxRec], double* __restrict__ r) {
-  const double cnt = S[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) r[k] = S[k] / cnt;
-  r[9] = cnt;
-}
-
-// One thread per scan voxel u.  An existing voxel: sums = sums + scan sums (one addition per entry, the count among them: exact).  A new
-// one: voxel n_vox + rank[u] starts from the scan's sums, gets its key and its table entry.  Both: the stamp and the record.
+// One thread per scan / destination voxel u.  An existing voxel: sums = sums + scan sums (one addition per entry, the count among them:
+// exact).  A new one: voxel n_vox + rank[u] starts from the scan's sums, gets its key and its table entry.  Both: the record, and the
+// stamp - seg_stamp[u] when that array is given (the move in place), else `stamp`.
 __global__ void __launch_bounds__(256) k_roll_commit(const unsigned long long* __restrict__ keys, const int* __restrict__ seg_start, int n_seg,
                                                       const double* __restrict__ scan_sums, const int* __restrict__ hit, const int* __restrict__ rank, int n_vox, long long stamp,
-                                                      double* __restrict__ sums, double* __restrict__ rec, unsigned long long* __restrict__ vkeys, long long* __restrict__ stamps,
-                                                      ulonglong2* __restrict__ table, unsigned int mask) {
+                                                      const long long* __restrict__ seg_stamp, double* __restrict__ sums, double* __restrict__ rec,
+                                                      unsigned long long* __restrict__ vkeys, long long* __restrict__ stamps, ulonglong2* __restrict__ table, unsigned int mask) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= n_seg) return;
   const double* a = scan_sums + (size_t)u * kVoxRec;
@@ -103,8 +115,8 @@ __global__ void __launch_bounds__(256) k_roll_commit(const unsigned long long* _
   double* d = sums + (size_t)v * kVoxRec;
 #pragma unroll
   for (int k = 0; k < kVoxRec; ++k) d[k] = S[k];
-  stamps[v] = stamp;
-  roll_write_record(S, rec + (size_t)v * kVoxRec);
+  stamps[v] = seg_stamp ? seg_stamp[u] : stamp;
+  voxel_record_from_sums(S, rec + (size_t)v * kVoxRec);
 }
 
 // {vkeys[v], v} for v in [0, n) into a cleared table
@@ -145,6 +157,111 @@ __global__ void __launch_bounds__(256) k_roll_compact(const int* __restrict__ ke
   for (int k = 0; k < kVoxRec; ++k) rec_o[(size_t)w * kVoxRec + k] = rec[(size_t)v * kVoxRec + k];
   vkeys_o[w] = vkeys[v];
   stamps_o[w] = stamps[v];
+}
+
+// ---- the record routes ----
+constexpr int kRecNoVoxel = 1, kRecBadCount = 2, kRecOverflow = 4;  // bits of the refusal flag
+
+// Where the records of an insert are: the map's own layout [n][kVoxRec] (another handle's sums, or this map's), or the three arrays
+// of the C ABI as uploaded (packed == nullptr).
+struct RollRecs {
+  const double* packed;
+  const double* S;   // [n][3]
+  const double* C;   // [n][6]
+  const int* cnt;    // [n]
+};
+
+__device__ __forceinline__ void rollrec_load(const RollRecs& in, int r, double (&S)[3], double (&Cv)[6], double& cnt) {
+  if (in.packed) {
+    const double* p = in.packed + (size_t)r * kVoxRec;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) S[k] = p[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Cv[k] = p[3 + k];
+    cnt = p[9];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) S[k] = in.S[(size_t)r * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Cv[k] = in.C[(size_t)r * 6 + k];
+    cnt = (double)in.cnt[r];
+  }
+}
+
+// keys[r] / vals[r] = r for record r: the key of the voxel its moved float mean lies in
+__global__ void __launch_bounds__(256) k_rollrec_keys(RollRecs in, int n, RollPose T, float inv_res, unsigned long long* __restrict__ keys, int* __restrict__ vals,
+                                                       int* __restrict__ flag) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const double* S = in.packed ? in.packed + (size_t)r * kVoxRec : in.S + (size_t)r * 3;  // (the covariance sum is not read here)
+  const double cnt = in.packed ? S[9] : (double)in.cnt[r];
+  int f = 0;
+  if (!(cnt >= 1.0)) f |= kRecBadCount;
+  const float px = (float)(S[0] / cnt), py = (float)(S[1] / cnt), pz = (float)(S[2] / cnt);
+  const float3 q = transform_point_f(T.m, px, py, pz);
+  unsigned long long key = 0;
+  if (!voxel_key(q.x, q.y, q.z, inv_res, key)) f |= kRecNoVoxel;
+  if (f) atomicOr(flag, f);
+  keys[r] = key;
+  vals[r] = r;
+}
+
+// One thread per destination voxel u: {s 3, rotate_sym(R, sum C) 6, N} into dst_sums[u], the map's number of its key (or -1) into hit[u],
+// is_new[u], and (stamps_in != nullptr) the largest stamp of its records into seg_stamp[u].  `table` may be null (no map yet, or the move
+// in place, which inserts into an empty map): every voxel is new.  The map is only read.
+__global__ void __launch_bounds__(256) k_rollrec_lookup(const unsigned long long* __restrict__ keys, const int* __restrict__ order, const int* __restrict__ seg_start, int n_seg,
+                                                         RollRecs in, const long long* __restrict__ stamps_in, RollPose T, const ulonglong2* __restrict__ table, unsigned int mask,
+                                                         const double* __restrict__ map_sums, double* __restrict__ dst_sums, int* __restrict__ hit, int* __restrict__ is_new,
+                                                         long long* __restrict__ seg_stamp, int* __restrict__ flag) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= n_seg) return;
+  const int s = seg_start[u], e = seg_start[u + 1];
+  double A[3], Cc[6], rc[6];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) A[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) Cc[k] = 0.0;
+  long long N = 0, newest = 0;
+  for (int j = s; j < e; ++j) {
+    const int r = order[j];
+    double S[3], Cv[6], cnt;
+    rollrec_load(in, r, S, Cv, cnt);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) A[k] += S[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) Cc[k] += Cv[k];
+    N += (long long)cnt;  // (counts are integers below 2^31; at most 2^31 records: no overflow)
+    if (stamps_in) {
+      const long long t = stamps_in[r];
+      newest = t > newest ? t : newest;
+    }
+  }
+  rotate_sym(T.R, Cc, rc);
+  double sv[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) sv[k] = ((T.R[k * 3 + 0] * A[0] + T.R[k * 3 + 1] * A[1]) + T.R[k * 3 + 2] * A[2]) + (double)N * (double)T.m[12 + k];
+  const int v = roll_store_lookup(sv, rc, (double)N, table, mask, keys[s], dst_sums + (size_t)u * kVoxRec, hit + u, is_new + u);
+  const long long total = N + (v >= 0 ? (long long)map_sums[(size_t)v * kVoxRec + 9] : 0ll);
+  if (total > 2147483647ll) atomicOr(flag, kRecOverflow);
+  if (seg_stamp) seg_stamp[u] = newest;
+}
+
+// The restore: voxel v from row v of the uploaded arrays.  (The stamps are copied straight into the map's array.)
+__global__ void __launch_bounds__(256) k_rollrec_fill(const int* __restrict__ ijk, const double* __restrict__ S3, const double* __restrict__ C6, const int* __restrict__ cnt, int n,
+                                                       double* __restrict__ sums, double* __restrict__ rec, unsigned long long* __restrict__ vkeys) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  double S[kVoxRec];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) S[k] = S3[(size_t)v * 3 + k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) S[3 + k] = C6[(size_t)v * 6 + k];
+  S[9] = (double)cnt[v];
+  double* d = sums + (size_t)v * kVoxRec;
+#pragma unroll
+  for (int k = 0; k < kVoxRec; ++k) d[k] = S[k];
+  voxel_record_from_sums(S, rec + (size_t)v * kVoxRec);
+  vkeys[v] = voxel_pack(ijk[3 * v + 0], ijk[3 * v + 1], ijk[3 * v + 2]);
 }
 
 }  // namespace ngk

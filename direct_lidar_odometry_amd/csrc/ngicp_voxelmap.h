@@ -14,6 +14,36 @@ void size_voxel_work(ngicp* h, size_t n) {
   h->tile_sums.ensure(((n + kScanTile - 1) / kScanTile) * sizeof(int));
 }
 
+// rank[0 .. n] = the exclusive prefix sums of the n int flags (rank[n]: their total), three launches on the handle's stream with tile_sums,
+// which size_voxel_work sized for n.  Nothing is synchronised.
+void exclusive_scan_flags(ngicp* h, const int* flags, int n, int* rank) {
+  const int ntiles = (n + kScanTile - 1) / kScanTile;
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, flags, n, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, flags, n, (const int*)h->tile_sums.as<int>(), rank);
+}
+
+// A count the stream leaves on the device (a numbering's segments, a scan's total) and, if asked for, the flag word vox_flag, read
+// back: one host synchronisation.  What the two values refuse is the caller's business.
+struct CountAndFlag {
+  int count, flag;
+};
+CountAndFlag read_count(ngicp* h, const int* count_dev, bool with_flag = false) {
+  CountAndFlag r{0, 0};
+  HIP_TRY(hipMemcpyAsync(&r.count, count_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (with_flag) HIP_TRY(hipMemcpyAsync(&r.flag, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  return r;
+}
+
+// the slots of a table that stays at most half full with `need` voxels: a power of two, at least 64 and at least `current`
+size_t voxel_table_slots(size_t need, size_t current = 0) {
+  size_t slots = std::max(current, (size_t)64);
+  while (slots < 2 * need) slots <<= 1;
+  return slots;
+}
+
 // What a build's numbering step leaves on the device: the keys sorted (stable), the values beside them, where every run of equal keys
 // starts (n_seg + 1 entries) and the number of runs.
 struct VoxelSegments {
@@ -27,7 +57,6 @@ struct VoxelSegments {
 // of a target's points, a keyframe's part and the merge of parts.  Nothing is synchronised.
 VoxelSegments voxel_segments(ngicp* h, int n) {
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  const int ntiles = (n + kScanTile - 1) / kScanTile;
   unsigned long long* keys_a = h->vox_keys.as<unsigned long long>();
   unsigned long long* keys_b = keys_a + n;
   int* vals_a = h->vox_vals.as<int>();
@@ -41,9 +70,7 @@ VoxelSegments voxel_segments(ngicp* h, int n) {
   const unsigned long long* keys = in_a ? keys_a : keys_b;
   const int* order = in_a ? vals_a : vals_b;
   hipLaunchKernelGGL(k_voxel_map_heads, dim3(blocks), dim3(256), 0, h->stream, keys, n, head);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)head, n, h->tile_sums.as<int>(), (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(kScanBlock), 0, h->stream, h->tile_sums.as<int>(), ntiles, (const unsigned long long*)nullptr, (unsigned long long*)nullptr);
-  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(kScanBlock), 0, h->stream, (const int*)head, n, (const int*)h->tile_sums.as<int>(), vox_of);
+  exclusive_scan_flags(h, head, n, vox_of);
   hipLaunchKernelGGL(k_voxel_map_starts, dim3(blocks), dim3(256), 0, h->stream, (const int*)head, (const int*)vox_of, n, seg_start);
   return VoxelSegments{keys, order, seg_start, vox_of + n};
 }
@@ -61,8 +88,7 @@ VoxelSegments voxel_segments_of_cloud(ngicp* h, const DeviceCloud& dc) {
 
 // sizes the map's own buffers for n_vox voxels, clears the table and returns its slot count (the stream is idle: the count was just read)
 size_t size_voxel_map(ngicp* h, ngicp::VoxelMap& m, int n_vox) {
-  size_t slots = 64;
-  while (slots < 2 * (size_t)n_vox) slots <<= 1;
+  const size_t slots = voxel_table_slots((size_t)n_vox);
   m.rec.ensure((size_t)n_vox * kVoxRec * sizeof(double));
   m.vkeys.ensure((size_t)n_vox * sizeof(unsigned long long));
   m.table.ensure(slots * sizeof(ulonglong2));
@@ -79,11 +105,7 @@ void build_voxel_map_from_points(ngicp* h, const double* covs) {
   size_voxel_work(h, (size_t)n);
   HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
   const VoxelSegments sg = voxel_segments_of_cloud(h, T);
-  int n_vox = 0, bad = 0;
-  HIP_TRY(hipMemcpyAsync(&n_vox, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const auto [n_vox, bad] = read_count(h, sg.n_seg_dev, true);
   if (bad) throw ArgError{NGICP_ERR_ARG, "voxelized target: a point lies 2^20 voxels or more from the origin on some axis (or is not finite); use a coarser resolution"};
   if (n_vox <= 0 || n_vox > n) throw ArgError{NGICP_ERR_HIP, "voxel map build: inconsistent voxel count"};
   const size_t slots = size_voxel_map(h, m, n_vox);
@@ -107,11 +129,7 @@ void build_keyframe_part(ngicp* h, int id) {
   ngicp::Keyframe& kf = h->keyframes[(size_t)id];
   const int n = (int)kf.cloud->n;
   const VoxelSegments sg = voxel_segments_of_cloud(h, *kf.cloud);
-  int n_vox = 0, bad = 0;
-  HIP_TRY(hipMemcpyAsync(&n_vox, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const auto [n_vox, bad] = read_count(h, sg.n_seg_dev, true);
   if (bad)
     throw ArgError{NGICP_ERR_ARG, "voxel part of keyframe " + std::to_string(id) +
                                       ": a point lies 2^20 voxels or more from the origin on some axis (or is not finite); use a coarser resolution"};
@@ -183,10 +201,7 @@ void build_voxel_map_merged(ngicp* h) {
     (void)hipStreamSynchronize(h->stream);  // the upload of `tab` may still be pending: it must not outlive the vector
     throw;
   }
-  int n_vox = 0;
-  HIP_TRY(hipMemcpyAsync(&n_vox, sg.n_seg_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipGetLastError());
+  const int n_vox = read_count(h, sg.n_seg_dev).count;
   if (n_vox <= 0 || n_vox > G) throw ArgError{NGICP_ERR_HIP, "merged voxel map build: inconsistent voxel count"};
   const size_t slots = size_voxel_map(h, m, n_vox);
   hipLaunchKernelGGL(k_voxel_merge_fill, dim3((unsigned)((n_vox + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_vox,

@@ -326,7 +326,7 @@ int ngicp_voxel_rolling_evict(ngicp_t* h, const float centre[3], double max_dist
 int ngicp_voxel_rolling_clear(ngicp_t* h);
 int ngicp_voxel_rolling_get(ngicp_t* h, size_t* n_vox, int* ijk_n3, double* sum_n3, double* covsum_n6, int* count_n, long long* stamp_n);
 int ngicp_voxel_rolling_stats(const ngicp_t* h, long long* inserts, size_t* n_vox, size_t* capacity_vox, size_t* table_slots, double* last_insert_ms, double* last_evict_ms);
-/* --- rolling voxel map: records - restore, merge and move a map from its voxel sums (csrc/ngicp_voxel_rollrec.h) ----
+/* --- rolling voxel map: records - restore, merge and move a map from its voxel sums (csrc/ngicp_voxel_roll.h) -------
  * A RECORD is what ngicp_voxel_rolling_get returns per voxel: S (3 doubles), C (6 doubles: xx, xy, xz, yy, yz, zz), n (int, at least 1)
  * and a stamp.  The state of the map is per-voxel sums, so it can be taken back, added to another map and moved without the points.
  * All four entries return NGICP_ERR_STATE unless the rolling setting is on and res > 0, and - when they succeed - drop the

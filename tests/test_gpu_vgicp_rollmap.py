@@ -1,5 +1,5 @@
 """The rolling voxel map's record routes on the GPU (ngicp_voxel_rolling_set / _insert_voxels / _insert_map / _transform; k_rollrec_keys /
-k_rollrec_lookup / k_rollrec_commit / k_rollrec_fill in csrc/ngicp_voxel_rollrec.h) against the numpy model of their definition
+k_rollrec_lookup / k_roll_commit / k_rollrec_fill in csrc/ngicp_voxel_roll.h) against the numpy model of their definition
 (tests/_vgicp_rollmap_model.py, which proves itself in test_vgicp_rollmap_model_cpu.py).
 
 Everything is compared with np.array_equal: the library is built with -ffp-contract=off and the definition fixes the order of every
