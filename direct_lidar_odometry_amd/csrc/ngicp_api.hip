@@ -607,6 +607,8 @@ int ngicp_create(int device, ngicp_t** out) {
     HIP_TRY(hipEventCreate(&h->ev_vox_c));
     HIP_TRY(hipEventCreate(&h->ev_rec_a));
     HIP_TRY(hipEventCreate(&h->ev_rec_b));
+    HIP_TRY(hipEventCreate(&h->ev_vfit_a));
+    HIP_TRY(hipEventCreate(&h->ev_vfit_b));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_state), 2 * sizeof(LmState), hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin_final), sizeof(LmHot), hipHostMallocDefault));
     h->order_flag.ensure(64);
@@ -694,6 +696,8 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_vox_c) (void)hipEventDestroy(h->ev_vox_c);
   if (h->ev_rec_a) (void)hipEventDestroy(h->ev_rec_a);
   if (h->ev_rec_b) (void)hipEventDestroy(h->ev_rec_b);
+  if (h->ev_vfit_a) (void)hipEventDestroy(h->ev_vfit_a);
+  if (h->ev_vfit_b) (void)hipEventDestroy(h->ev_vfit_b);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -1965,6 +1969,7 @@ int ngicp_measure_copy_bandwidth(ngicp_t* h, size_t bytes, int reps, double* gbp
 
 // ---- scan preprocessing and map accumulation + voxel filter ----
 #include "ngicp_deskew.h"  // (here, after every other kernel: the code object up to this point is laid out as it was without it)
+#include "ngicp_voxel_fitness.h"  // (and this one behind it, for the same reason)
 
 namespace {
 // host cloud (strided xyz [+ intensity]) -> device float4 {x, y, z, intensity} at dst[0..n)
@@ -2209,6 +2214,119 @@ int ngicp_map_get(ngicp_t* h, float* out_xyzi, size_t out_capacity) {
 
 int ngicp_map_clear(ngicp_t* h) {
   return guarded(h, [&] { h->map_n = 0; });
+}
+
+}  // extern "C"
+
+// ---- voxel fitness: poses scored against the voxel map the handle aligns against (csrc/ngicp_voxel_fitness.h) ----
+namespace {
+
+template <bool POINTS>
+void launch_voxel_fitness(ngicp* h, const VoxelFitnessArgs& a, int nb, size_t poses) {
+  const dim3 grid((unsigned)nb, (unsigned)poses), block(kVoxFitBlock);
+  switch (h->voxel_nbr) {
+    case NGICP_VOX_DIRECT1: hipLaunchKernelGGL((k_voxel_fitness<1, POINTS>), grid, block, 0, h->stream, a); break;
+    case NGICP_VOX_DIRECT7: hipLaunchKernelGGL((k_voxel_fitness<7, POINTS>), grid, block, 0, h->stream, a); break;
+    default: hipLaunchKernelGGL((k_voxel_fitness<27, POINTS>), grid, block, 0, h->stream, a); break;
+  }
+}
+
+// n poses -> out[n]; with per-point outputs (n == 1) also m, d, v of every source point.  Everything the caller passed is checked before
+// anything is enqueued; then the source, the map (at most one build) and the source's covariances are readied in align's order.  Reads
+// and writes nothing of the hooks' state, of the last align's results and stats or of the batch workspace.
+void voxel_fitness_impl(ngicp* h, const std::string& e, size_t n, const float* T_colmajor, double max_m, ngicp_voxel_fitness_t* out, double* pt_m, double* pt_d, int* pt_v,
+                        size_t capacity) {
+  const bool points = pt_m || pt_d || pt_v;
+  if (!(h->voxel_res > 0.0)) throw ArgError{NGICP_ERR_STATE, e + ": the voxelized mode is off (ngicp_set_voxel_resolution)"};
+  if (n == 0) throw ArgError{NGICP_ERR_ARG, e + ": n is 0"};
+  if (!T_colmajor) throw ArgError{NGICP_ERR_ARG, e + ": null transforms"};
+  if (!(max_m >= 0.0)) throw ArgError{NGICP_ERR_ARG, e + ": max_mahalanobis must be >= 0 and not NaN"};
+  if (points ? !(pt_m && pt_d && pt_v) : !out) throw ArgError{NGICP_ERR_ARG, e + ": null output"};
+  if (points && capacity < h->src.n) throw ArgError{NGICP_ERR_ARG, e + ": the outputs hold fewer than n_src entries"};
+  ensure_slot_ready(h, h->src, "source");
+  const VoxelMapView vm = ensure_voxel_map(h);
+  if (h->src_covs.n != h->src.dev->n) compute_covs(h, h->src, h->src_covs, "source");
+  DeviceCloud& S = *h->src.dev;
+  const int np = (int)S.n;
+  const int nb = std::max(1, (np + kVoxFitBlock - 1) / kVoxFitBlock);
+  const size_t chunk = std::min(n, (size_t)kVoxelFitnessChunk);
+  h->vfit_T.ensure(chunk * 16 * sizeof(float));
+  h->vfit_part.ensure(chunk * (size_t)nb * kVoxFitSums * sizeof(double));
+  h->vfit_out.ensure(chunk * kVoxFitSums * sizeof(double));
+  VoxelFitnessArgs a{};
+  a.src = S.pts();
+  a.cov_src = covs_for(h, h->src_covs, h->src.dev);
+  a.n_src = np;
+  a.table = vm.table;
+  a.mask = vm.mask;
+  a.rec = vm.rec;
+  a.inv_res = 1.0f / (float)h->voxel_res;
+  a.T_colmajor = h->vfit_T.as<float>();
+  a.max_m = max_m;
+  a.partials = h->vfit_part.as<double>();
+  if (points) {
+    h->vfit_pts.ensure((size_t)np * (2 * sizeof(double) + sizeof(int)));
+    a.pt_m = h->vfit_pts.as<double>();
+    a.pt_d = a.pt_m + np;
+    a.pt_v = reinterpret_cast<int*>(a.pt_d + np);
+  }
+  std::vector<double> r(n * kVoxFitSums);
+  double kernel_ms = 0.0;
+  for (size_t at = 0; at < n; at += chunk) {
+    const size_t m = std::min(chunk, n - at);
+    HIP_TRY(hipMemcpyAsync(h->vfit_T.p, T_colmajor + at * 16, m * 16 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->ev_vfit_a, h->stream));
+    if (points) launch_voxel_fitness<true>(h, a, nb, m);
+    else launch_voxel_fitness<false>(h, a, nb, m);
+    hipLaunchKernelGGL((k_voxel_fitness_final<kVoxFitSums>), dim3((unsigned)m), dim3(kVoxFitFinalBlock), 0, h->stream, (const double*)h->vfit_part.as<double>(), nb, h->vfit_out.as<double>());
+    HIP_TRY(hipEventRecord(h->ev_vfit_b, h->stream));
+    HIP_TRY(hipMemcpyAsync(r.data() + at * kVoxFitSums, h->vfit_out.p, m * kVoxFitSums * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, h->ev_vfit_a, h->ev_vfit_b));
+    kernel_ms += ms;
+  }
+  if (points && np) {
+    HIP_TRY(hipMemcpyAsync(pt_m, a.pt_m, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(pt_d, a.pt_d, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(pt_v, a.pt_v, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  HIP_TRY(hipGetLastError());
+  h->vfit_kernel_ms = kernel_ms;
+  for (size_t i = 0; out && i < n; ++i) {
+    const double* s = r.data() + i * kVoxFitSums;
+    const bool any = s[2] > 0.0;
+    out[i].mahalanobis = any ? s[0] / s[2] : std::numeric_limits<double>::max();
+    out[i].sqdist = any ? s[1] / s[2] : std::numeric_limits<double>::max();
+    out[i].n_inliers = (size_t)s[2];
+    out[i].n_matched = (size_t)s[3];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngicp_voxel_fitness(ngicp_t* h, const float T_colmajor[16], double max_mahalanobis, ngicp_voxel_fitness_t* out) {
+  return guarded(h, [&] { voxel_fitness_impl(h, "ngicp_voxel_fitness", 1, T_colmajor ? T_colmajor : h->final_T, max_mahalanobis, out, nullptr, nullptr, nullptr, 0); });
+}
+
+int ngicp_voxel_fitness_batch(ngicp_t* h, size_t n, const float* T_colmajor, double max_mahalanobis, ngicp_voxel_fitness_t* out) {
+  return guarded(h, [&] { voxel_fitness_impl(h, "ngicp_voxel_fitness_batch", n, T_colmajor, max_mahalanobis, out, nullptr, nullptr, nullptr, 0); });
+}
+
+int ngicp_voxel_fitness_points(ngicp_t* h, const float T_colmajor[16], double* m_out, double* sqd_out, int* voxel_out, size_t capacity) {
+  return guarded(h, [&] {
+    if (!m_out || !sqd_out || !voxel_out) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_fitness_points: null output"};
+    voxel_fitness_impl(h, "ngicp_voxel_fitness_points", 1, T_colmajor ? T_colmajor : h->final_T, std::numeric_limits<double>::max(), nullptr, m_out, sqd_out, voxel_out, capacity);
+  });
+}
+
+int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms) {
+  if (!h || !ms) return NGICP_ERR_ARG;
+  *ms = h->vfit_kernel_ms;
+  return NGICP_OK;
 }
 
 }  // extern "C"

@@ -424,6 +424,11 @@ struct ngicp {
   // motion deskew (csrc/ngicp_deskew.h): the separately uploaded times, the uploaded trajectory and the table k_deskew_prepare makes of it
   DevBuf dsk_times, dsk_in, dsk_table;
   std::vector<double> dsk_host;          // the trajectory as uploaded: [M times][M x 16 poses][16 T_ref] (outlives the asynchronous copy)
+  // voxel fitness (csrc/ngicp_voxel_fitness.h): a query's own workspace, grow-only - nothing of an alignment lives here
+  DevBuf vfit_T, vfit_part, vfit_out;    // a chunk's poses [chunk][16], block partials [chunk][blocks][4], sums [chunk][4]
+  DevBuf vfit_pts;                       // ngicp_voxel_fitness_points: [n_src] m, [n_src] d, [n_src] v
+  hipEvent_t ev_vfit_a = nullptr, ev_vfit_b = nullptr;  // around a chunk's two kernels (its own pair: ngicp_stats is left alone)
+  double vfit_kernel_ms = 0.0;           // device time of the last call's kernels, all chunks (ngicp_voxel_fitness_kernel_ms)
 };
 
 namespace {

@@ -102,7 +102,13 @@ EXPORTS = [
     "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
     "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
     "ngicp_deskew_cloud", "ngicp_preprocess_scan_deskewed",
+    "ngicp_voxel_fitness", "ngicp_voxel_fitness_batch", "ngicp_voxel_fitness_points", "ngicp_voxel_fitness_kernel_ms",
 ]
+
+
+class VoxelFitness(C.Structure):
+    """ngicp_voxel_fitness_t (include/ngicp.h, "voxel fitness")."""
+    _fields_ = [("mahalanobis", C.c_double), ("sqdist", C.c_double), ("n_inliers", C.c_size_t), ("n_matched", C.c_size_t)]
 
 
 class Deskew(C.Structure):
@@ -232,6 +238,10 @@ def load_library() -> C.CDLL:
     L.ngicp_set_pose_prior.argtypes = [vp, c_f64p, c_f64p]
     L.ngicp_get_pose_prior.argtypes = [vp, c_i32p, c_f64p, c_f64p]
     L.ngicp_pose_prior_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]
+    L.ngicp_voxel_fitness.argtypes = [vp, c_f32p, C.c_double, C.POINTER(VoxelFitness)]
+    L.ngicp_voxel_fitness_batch.argtypes = [vp, C.c_size_t, c_f32p, C.c_double, C.POINTER(VoxelFitness)]
+    L.ngicp_voxel_fitness_points.argtypes = [vp, c_f32p, c_f64p, c_f64p, c_i32p, C.c_size_t]
+    L.ngicp_voxel_fitness_kernel_ms.argtypes = [vp, c_f64p]
     _lib = L
     return L
 
@@ -681,6 +691,49 @@ class NanoGICP:
         self._ck(self._L.ngicp_fitness_score_batch(self._h, B, _p(tc, c_f32p) if B else None, float(max_range), _p(scores, c_f64p) if B else None,
                                                    cnt.ctypes.data_as(C.POINTER(C.c_size_t))))
         return scores, cnt.astype(np.int64)
+
+    # ---- voxel fitness (include/ngicp.h "voxel fitness"): poses scored against the voxel map this handle aligns against ----
+    _VFIT_DTYPE = np.dtype([("mahalanobis", np.float64), ("sqdist", np.float64), ("n_inliers", np.uint64), ("n_matched", np.uint64)])
+
+    def voxelFitness(self, max_mahalanobis: float = sys.float_info.max, T=None) -> dict:
+        """-> {"mahalanobis", "sqdist", "n_inliers", "n_matched"} of the pose T (None: the last align's final transformation) against the
+        voxel map in force - the target's, the merged one or the rolling one; no target cloud is needed on a rolling map.  Per source
+        point the best slot's e^T (cov_v + R C_a R^T)^-1 e (no n_v factor) and squared distance to the voxel mean; a point is an inlier
+        iff that term is <= max_mahalanobis; the two scores are means over the inliers (DBL_MAX without any); n_matched / n_src is the
+        overlap."""
+        t = None if T is None else _colmajor16(T, np.float32)
+        r = VoxelFitness()
+        self._ck(self._L.ngicp_voxel_fitness(self._h, None if t is None else _p(t, c_f32p), float(max_mahalanobis), C.byref(r)))
+        return {"mahalanobis": r.mahalanobis, "sqdist": r.sqdist, "n_inliers": int(r.n_inliers), "n_matched": int(r.n_matched)}
+
+    def voxelFitnessBatch(self, Ts, max_mahalanobis: float = sys.float_info.max):
+        """voxelFitness() for every pose of Ts (B, 4, 4), B poses per launch -> (mahalanobis (B,) float64, sqdist (B,) float64,
+        n_inliers (B,) int64, n_matched (B,) int64), bit for bit what B calls of voxelFitness(max_mahalanobis, T) give."""
+        t = np.asarray(Ts)
+        if t.ndim != 3 or t.shape[1:] != (4, 4):
+            raise NgicpError(-2, "voxelFitnessBatch: Ts must be (B, 4, 4)")
+        B = t.shape[0]
+        tc = np.ascontiguousarray(np.transpose(t, (0, 2, 1)), dtype=np.float32).reshape(B, 16)
+        out = np.zeros(B, dtype=self._VFIT_DTYPE)
+        self._ck(self._L.ngicp_voxel_fitness_batch(self._h, B, _p(tc, c_f32p) if B else None, float(max_mahalanobis),
+                                                   out.ctypes.data_as(C.POINTER(VoxelFitness)) if B else None))
+        return (out["mahalanobis"].copy(), out["sqdist"].copy(), out["n_inliers"].astype(np.int64), out["n_matched"].astype(np.int64))
+
+    def voxel_fitness_points(self, T=None):
+        """-> (m (n,) float64, sqd (n,) float64, voxel (n,) int32) in original source order: every point's value at the pose T (None: the
+        final transformation) - the winning slot's term, squared distance and voxel number; -1 / -1 / -1 where the map has no voxel for
+        the point (unmatched), +inf / +inf / -1 where it has one but no term is finite."""
+        t = None if T is None else _colmajor16(T, np.float32)
+        n = 0 if self._src is None else self._src.shape[0]  # (no source: the engine says so)
+        m = np.empty(max(n, 1)); d = np.empty(max(n, 1)); v = np.empty(max(n, 1), dtype=np.int32)
+        self._ck(self._L.ngicp_voxel_fitness_points(self._h, None if t is None else _p(t, c_f32p), _p(m, c_f64p), _p(d, c_f64p), _p(v, c_i32p), n))
+        return m[:n], d[:n], v[:n]
+
+    def voxelFitnessKernelMs(self) -> float:
+        """device time of the kernels of the last voxelFitness / voxelFitnessBatch / voxel_fitness_points call (stats() is left alone)"""
+        ms = C.c_double(0)
+        self._ck(self._L.ngicp_voxel_fitness_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def getFinalTransformation(self): return self.final_transformation_
     def hasConverged(self) -> bool: return self.converged_

@@ -704,6 +704,49 @@ class NanoGICP {
     return scores;
   }
 
+  // ---- voxel fitness (include/ngicp.h "voxel fitness"): a pose scored against the voxel map the voxelized entries align against - the
+  //      target's, the merged one or the rolling one.  getFitnessScore(s) need a target cloud and its exact index; these need neither, so
+  //      they are what scores a pose on a rolling map.  Per source point the best neighbourhood slot's e^T (cov_v + R C_a R^T)^-1 e (no
+  //      voxel-count factor) and squared distance to the voxel mean; a point is an inlier iff that term is <= max_mahalanobis; both
+  //      scores are means over the inliers, DBL_MAX without any; n_matched / (source size) is the overlap.  ok false (and a line on
+  //      stderr): the voxel mode is off, the rolling map is empty or there is no source.  Recipe: INTEGRATION.md.
+  struct VoxelFitness {
+    bool ok = false;
+    double mahalanobis = std::numeric_limits<double>::max(), sqdist = std::numeric_limits<double>::max();
+    size_t n_inliers = 0, n_matched = 0;
+  };
+  // the final transformation of the last align()
+  VoxelFitness getVoxelFitness(double max_mahalanobis = std::numeric_limits<double>::max()) {
+    VoxelFitness f;
+    ngicp_voxel_fitness_t r;
+    if (h_ && check(ngicp_voxel_fitness(h_, final_transformation_.data(), max_mahalanobis, &r), "getVoxelFitness")) f = fromRecord(r);
+    return f;
+  }
+  // every transform in the same launches; entry i is bit for bit what the single call gives for transforms[i]
+  std::vector<VoxelFitness> getVoxelFitnessScores(const std::vector<Matrix4>& transforms, double max_mahalanobis = std::numeric_limits<double>::max()) {
+    std::vector<VoxelFitness> out(transforms.size());
+    if (!h_ || transforms.empty()) return out;
+    std::vector<float> T(transforms.size() * 16);
+    std::vector<ngicp_voxel_fitness_t> r(transforms.size());
+    for (size_t i = 0; i < transforms.size(); ++i) std::memcpy(&T[i * 16], transforms[i].data(), 16 * sizeof(float));
+    if (check(ngicp_voxel_fitness_batch(h_, transforms.size(), T.data(), max_mahalanobis, r.data()), "getVoxelFitnessScores"))
+      for (size_t i = 0; i < r.size(); ++i) out[i] = fromRecord(r[i]);
+    return out;
+  }
+  // every source point's value at T, in the source cloud's order: the winning slot's term, squared distance and voxel number; -1 / -1 / -1
+  // where the map has no voxel for the point.  Cleared (false) on an error.
+  bool voxelFitnessPoints(const Matrix4& T, std::vector<double>& m, std::vector<double>& sqd, std::vector<int>& voxel) {
+    const size_t n = input_ ? input_->size() : 0;
+    m.assign(n, -1.0);
+    sqd.assign(n, -1.0);
+    voxel.assign(n, -1);
+    if (h_ && check(ngicp_voxel_fitness_points(h_, T.data(), m.data(), sqd.data(), voxel.data(), n), "voxelFitnessPoints")) return true;
+    m.clear();
+    sqd.clear();
+    voxel.clear();
+    return false;
+  }
+
   // ---- extensions with no reference counterpart (include/ngicp.h "keyframe store", "rigid transform"): the keyframes and the
   //      submap stay on the GPU.  In DLO they replace odom.cc:1174 (`keyframe_normals.push_back(gicp_s2s.getSourceCovariances())`)
   //      and odom.cc:830-833 (`setInputTarget(submap_cloud); setTargetCovariances(submap_normals)`); see INTEGRATION.md ----
@@ -851,6 +894,15 @@ class NanoGICP {
   }
   template <class CloudPtr> static const float* xyz(const CloudPtr& c) { return c->size() ? c->points[0].data : nullptr; }
   template <class CloudPtr> static uint64_t id(const CloudPtr& c) { return (uint64_t)(uintptr_t)c.get(); }
+  static VoxelFitness fromRecord(const ngicp_voxel_fitness_t& r) {
+    VoxelFitness f;
+    f.ok = true;
+    f.mahalanobis = r.mahalanobis;
+    f.sqdist = r.sqdist;
+    f.n_inliers = r.n_inliers;
+    f.n_matched = r.n_matched;
+    return f;
+  }
   static void set_identity(Matrix4& m) { for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m(r, c) = r == c ? 1.f : 0.f; }
 
   ngicp_t* h_ = nullptr;

@@ -512,6 +512,49 @@ int ngicp_batch_get_lm_trace(ngicp_t* h, size_t lane, double* rows8_or_null, siz
  * the lowest score. */
 int ngicp_fitness_score_batch(ngicp_t* h, size_t n, const float* T_n16_colmajor, double max_range, double* scores_n, size_t* n_inliers_n_or_null);
 
+/* --- voxel fitness: poses scored against the voxel map the handle aligns against (no counterpart in the reference;
+ *     csrc/ngicp_voxel_fitness.h) -----------------------------------------------------------------------------------
+ * ngicp_fitness_score needs a target cloud and its exact index; a handle on a rolling voxel map has neither.  These entries score a
+ * pose against the voxel map itself - the target's, the merged one, or the rolling one - and say how much of the source it explains.
+ * The definition is the project's own:
+ *   inputs     a float 4x4 pose T (column-major; NULL where allowed: the final transformation of the last align); the source with its
+ *              covariances, computed if missing exactly as ngicp_align does; the voxel map as ngicp_align would use it (built if stale,
+ *              at most once per call; the rolling map while that setting is on, an empty one being NGICP_ERR_STATE); the resolution and
+ *              the neighbourhood K (1, 7 or 27) in force.
+ *   the point  q = the float pose times the source point a in the passes' order, ((c0 x + c1 y) + c2 z) + c3 per row, nothing fused;
+ *              its cell is floorf(q * inv_res) as everywhere in the voxelized mode.
+ *   the slots  slot s = 0..K-1 is voxel c + off[s] under the passes' rule (see "voxelized GICP"): the centre and the neighbour in range
+ *              on the integers, the voxel occupied.  A point without an occupied slot is UNMATCHED.
+ *   a term     of an occupied slot, in FP64 with nothing fused, R and t being the float entries of T widened to double:
+ *              e = mean_v - (R a + t), M = (cov_v + R C_a R^T)^-1 (the passes' routines in the passes' order of operations),
+ *              m_s = e^T M e - the pass's term WITHOUT the factor n_v - and d_s = (ex ex + ey ey) + ez ez.
+ *   the value  of a point: best = +inf; in ascending slot, slot s wins when m_s < best (ties go to the lower slot, a NaN never wins);
+ *              (m, d, v) are those of the winning slot, v its voxel number (ngicp_voxelmap_get / ngicp_voxel_rolling_get order).  A
+ *              matched point without a winner (every term non-finite) has m = d = +inf, v = -1: matched, never an inlier.
+ *   counting   a point is an INLIER iff m <= max_mahalanobis (pass DBL_MAX for no gate; NaN or negative: NGICP_ERR_ARG).  Per pose:
+ *              n_matched, n_inliers, mahalanobis = (sum of m over the inliers) / n_inliers, sqdist = (sum of d) / n_inliers, both
+ *              DBL_MAX when there is no inlier.  n_matched / n_src is the overlap.
+ * The sums are fixed-order FP64 reductions (a lane's value, the wave's butterflies, the block's waves in order, the blocks strided per
+ * thread of one block and reduced the same way): bitwise reproducible, pose i of a batch is bit for bit the single call, and nothing
+ * depends on n or on how the poses are cut into launches.  The robust kernel, the pose prior and max_correspondence_distance are not
+ * consulted, and nothing is refused because they are set.  The calls leave the hooks' state (ngicp_compute_error, the correspondences),
+ * the results, trace and stats of the last ngicp_align and the lanes and traces of the last batch call untouched.
+ * Errors: voxel mode off NGICP_ERR_STATE; no source as ngicp_align; empty rolling map NGICP_ERR_STATE; n == 0, a null pointer, a short
+ * capacity or a bad gate NGICP_ERR_ARG.  Everything passed in is checked before anything is enqueued. */
+typedef struct ngicp_voxel_fitness {
+  double mahalanobis, sqdist;
+  size_t n_inliers, n_matched;
+} ngicp_voxel_fitness_t;
+int ngicp_voxel_fitness(ngicp_t* h, const float T_colmajor_or_null[16], double max_mahalanobis, ngicp_voxel_fitness_t* out);
+/* n poses (n x 16 floats, column-major; any n: a launch takes at most 4096) -> out[n] */
+int ngicp_voxel_fitness_batch(ngicp_t* h, size_t n, const float* T_n16_colmajor, double max_mahalanobis, ngicp_voxel_fitness_t* out_n);
+/* The per-point values of one pose in ORIGINAL source order, capacity >= n_src entries each: unmatched points come out as
+ * m = -1, d = -1, v = -1 (the convention of ngicp_robust_terms).  No gate applies. */
+int ngicp_voxel_fitness_points(ngicp_t* h, const float T_colmajor_or_null[16], double* m_out, double* sqd_out, int* voxel_out, size_t capacity);
+/* device time (HIP events on the handle's stream) of the kernels of the last call of any of the three, all launches together;
+ * kept here and not in ngicp_stats, which these calls leave alone */
+int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms);
+
 /* The small FP64 routines of the engine evaluated on the device, one problem per thread (unit-test hook): which = 0 so3_exp
  * (gicp/so3.hpp:99-118 followed by Quaternion::toRotationMatrix; in: 3 doubles, out: R row-major 9), 1 the 6x6 LDLT solve that
  * stands in for Eigen::LDLT (impl/lsq_registration_impl.hpp:147-148,172-173; in: A row-major 36 + rhs 6, out: 6), 2 the
