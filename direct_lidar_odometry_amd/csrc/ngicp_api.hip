@@ -698,6 +698,8 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_rec_b) (void)hipEventDestroy(h->ev_rec_b);
   if (h->ev_vfit_a) (void)hipEventDestroy(h->ev_vfit_a);
   if (h->ev_vfit_b) (void)hipEventDestroy(h->ev_vfit_b);
+  if (h->sc.ev_a) (void)hipEventDestroy(h->sc.ev_a);
+  if (h->sc.ev_b) (void)hipEventDestroy(h->sc.ev_b);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -2330,3 +2332,6 @@ int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms) {
 }
 
 }  // extern "C"
+
+// ---- scan context place recognition: descriptors, their database, matching (csrc/ngicp_scan_context.h) ----
+#include "ngicp_scan_context.h"  // (kernels and entries; behind everything else, so that the code object up to here is laid out as it was)

@@ -429,6 +429,19 @@ struct ngicp {
   DevBuf vfit_pts;                       // ngicp_voxel_fitness_points: [n_src] m, [n_src] d, [n_src] v
   hipEvent_t ev_vfit_a = nullptr, ev_vfit_b = nullptr;  // around a chunk's two kernels (its own pair: ngicp_stats is left alone)
   double vfit_kernel_ms = 0.0;           // device time of the last call's kernels, all chunks (ngicp_voxel_fitness_kernel_ms)
+  // scan context (csrc/ngicp_scan_context.h): parameters, tables, the descriptor database and a query's own workspace
+  struct ScanContext {
+    int R = 20, S = 60;                  // rings, sectors
+    float L = 80.0f, z0 = 2.0f;          // max_radius, z_offset
+    std::vector<float> tab;              // the host tables (sc_make_tables), valid while tab_valid; tab_dev holds them while tab_on_device
+    bool tab_valid = false, tab_on_device = false;
+    DevBuf tab_dev;
+    size_t count = 0, cap = 0;           // entries, capacity of the two arrays in entries (doubling; recounted when a parameter change alters the entry size)
+    DevBuf db_desc, db_norm;             // [cap][R][S] floats, [cap][S] column norms
+    DevBuf q_desc, q_norm, res;          // a query's descriptor and norms; [n] distances, [n] shifts and the top-k record of the last query
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;  // around a call's kernels (created on first use; its own pair: ngicp_stats is left alone)
+    double kernel_ms = 0.0;              // ngicp_scan_context_kernel_ms
+  } sc;
 };
 
 namespace {

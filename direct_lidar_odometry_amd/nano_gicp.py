@@ -103,6 +103,9 @@ EXPORTS = [
     "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
     "ngicp_deskew_cloud", "ngicp_preprocess_scan_deskewed",
     "ngicp_voxel_fitness", "ngicp_voxel_fitness_batch", "ngicp_voxel_fitness_points", "ngicp_voxel_fitness_kernel_ms",
+    "ngicp_scan_context_set_params", "ngicp_scan_context_get_params", "ngicp_scan_context_tables", "ngicp_scan_context_compute",
+    "ngicp_scan_context_add", "ngicp_scan_context_add_descriptor", "ngicp_scan_context_count", "ngicp_scan_context_get", "ngicp_scan_context_clear",
+    "ngicp_scan_context_distances", "ngicp_scan_context_match", "ngicp_scan_context_kernel_ms",
 ]
 
 
@@ -242,6 +245,18 @@ def load_library() -> C.CDLL:
     L.ngicp_voxel_fitness_batch.argtypes = [vp, C.c_size_t, c_f32p, C.c_double, C.POINTER(VoxelFitness)]
     L.ngicp_voxel_fitness_points.argtypes = [vp, c_f32p, c_f64p, c_f64p, c_i32p, C.c_size_t]
     L.ngicp_voxel_fitness_kernel_ms.argtypes = [vp, c_f64p]
+    L.ngicp_scan_context_set_params.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float]
+    L.ngicp_scan_context_get_params.argtypes = [vp, c_i32p, c_i32p, c_f32p, c_f32p]
+    L.ngicp_scan_context_tables.argtypes = [vp, c_f32p, c_f32p]
+    L.ngicp_scan_context_compute.argtypes = [vp, C.c_int, c_f32p]
+    L.ngicp_scan_context_add.argtypes = [vp, C.c_int, c_i32p]
+    L.ngicp_scan_context_add_descriptor.argtypes = [vp, c_f32p, c_i32p]
+    L.ngicp_scan_context_count.argtypes = [vp, c_szp]
+    L.ngicp_scan_context_get.argtypes = [vp, C.c_int, c_f32p]
+    L.ngicp_scan_context_clear.argtypes = [vp]
+    L.ngicp_scan_context_distances.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, c_f64p, c_i32p]
+    L.ngicp_scan_context_match.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, C.c_int, c_i32p, c_f64p, c_i32p, c_szp]
+    L.ngicp_scan_context_kernel_ms.argtypes = [vp, c_f64p]
     _lib = L
     return L
 
@@ -733,6 +748,124 @@ class NanoGICP:
         """device time of the kernels of the last voxelFitness / voxelFitnessBatch / voxel_fitness_points call (stats() is left alone)"""
         ms = C.c_double(0)
         self._ck(self._L.ngicp_voxel_fitness_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # ---- scan context (include/ngicp.h "scan context"): which earlier keyframe a scan revisits, and at what yaw ----
+    SCAN_CONTEXT_MAX_TOP_K = 64
+
+    def _sc_which(self, which) -> int:
+        """a slot as a number (0 source, 1 target, 2 the preprocessed scan) or by rangeSelect's names"""
+        if isinstance(which, str):
+            return self._range_which(which)
+        if isinstance(which, (int, np.integer)) and not isinstance(which, bool):
+            return int(which)  # (a number outside 0..2: the engine says so)
+        raise NgicpError(-2, f"which must be a slot number or one of {sorted(self._RANGE_WHICH)}, not {which!r}")
+
+    def _sc_query(self, query):
+        """-> (which, descriptor pointer or None, the array kept alive): a slot number / name, or an (R, S) descriptor"""
+        if isinstance(query, (str, int, np.integer)) and not isinstance(query, bool):
+            return self._sc_which(query), None, None
+        R, S, _, _ = self.getScanContextParams()
+        d = np.ascontiguousarray(query, dtype=np.float32)
+        if d.shape != (R, S):
+            raise NgicpError(-2, f"a scan context descriptor must be ({R}, {S}), not {d.shape}")
+        return -1, _p(d, c_f32p), d
+
+    def setScanContextParams(self, n_rings: int = 20, n_sectors: int = 60, max_radius: float = 80.0, z_offset: float = 2.0):
+        """rings 1..64, sectors even 2..64, max_radius > 0, z_offset finite.  A change clears the descriptor database."""
+        self._ck(self._L.ngicp_scan_context_set_params(self._h, int(n_rings), int(n_sectors), float(max_radius), float(z_offset)))
+
+    def getScanContextParams(self):
+        """-> (n_rings, n_sectors, max_radius, z_offset)"""
+        R, S, L, z0 = C.c_int(0), C.c_int(0), C.c_float(0), C.c_float(0)
+        self._ck(self._L.ngicp_scan_context_get_params(self._h, C.byref(R), C.byref(S), C.byref(L), C.byref(z0)))
+        return R.value, S.value, np.float32(L.value), np.float32(z0.value)
+
+    def scanContextTables(self):
+        """-> (E2 (R + 1,) float32: the squared ring edges; b (S / 2, 2) float32: the sector boundary directions) as the engine uses them"""
+        R, S, _, _ = self.getScanContextParams()
+        E2 = np.empty(R + 1, dtype=np.float32); b = np.empty(S, dtype=np.float32)
+        self._ck(self._L.ngicp_scan_context_tables(self._h, _p(E2, c_f32p), _p(b, c_f32p)))
+        return E2, b.reshape(S // 2, 2)
+
+    def computeScanContext(self, which=0) -> np.ndarray:
+        """-> the (R, S) float32 descriptor of a slot's cloud (0 source, 1 target, 2 the preprocessed scan), built on the device"""
+        R, S, _, _ = self.getScanContextParams()
+        d = np.empty((R, S), dtype=np.float32)
+        self._ck(self._L.ngicp_scan_context_compute(self._h, self._sc_which(which), _p(d, c_f32p)))
+        return d
+
+    def addScanContext(self, which=0) -> int:
+        """append the descriptor of a slot's cloud to the database without leaving the device -> its id (dense, in insertion order)"""
+        i = C.c_int(-1)
+        self._ck(self._L.ngicp_scan_context_add(self._h, self._sc_which(which), C.byref(i)))
+        return i.value
+
+    def addScanContextDescriptor(self, desc) -> int:
+        """append a host descriptor (R, S), finite and >= 0 -> its id"""
+        _, p, keep = self._sc_query(np.asarray(desc))
+        i = C.c_int(-1)
+        self._ck(self._L.ngicp_scan_context_add_descriptor(self._h, p, C.byref(i)))
+        return i.value
+
+    def numScanContexts(self) -> int:
+        n = C.c_size_t(0)
+        self._ck(self._L.ngicp_scan_context_count(self._h, C.byref(n)))
+        return n.value
+
+    def scanContext(self, id: int) -> np.ndarray:
+        R, S, _, _ = self.getScanContextParams()
+        d = np.empty((R, S), dtype=np.float32)
+        self._ck(self._L.ngicp_scan_context_get(self._h, int(id), _p(d, c_f32p)))
+        return d
+
+    def clearScanContexts(self):
+        self._ck(self._L.ngicp_scan_context_clear(self._h))
+
+    def _sc_range(self, begin, end):
+        end = self.numScanContexts() if end is None else int(end)
+        begin = int(begin)
+        if begin < 0 or end < 0:
+            raise NgicpError(-2, "a scan context id range must not be negative")
+        return begin, end
+
+    def scanContextDistances(self, query, begin: int = 0, end=None):
+        """-> (dist (n,) float64, shift (n,) int32) of the query - a slot number or an (R, S) descriptor - to the entries [begin, end) (end
+        None: every entry from begin), each the minimum over all S column shifts and the smallest shift that attains it."""
+        which, p, keep = self._sc_query(query)
+        begin, end = self._sc_range(begin, end)
+        n = max(end - begin, 0)
+        dist = np.empty(max(n, 1)); shift = np.empty(max(n, 1), dtype=np.int32)
+        self._ck(self._L.ngicp_scan_context_distances(self._h, which, p, begin, end, _p(dist, c_f64p), _p(shift, c_i32p)))
+        return dist[:n], shift[:n]
+
+    def matchScanContext(self, query, begin: int = 0, end=None, top_k: int = 1):
+        """-> (ids (m,) int32, dist (m,) float64, shift (m,) int32): the first m = min(top_k, end - begin) entries of [begin, end) in
+        ascending (distance, id) order, selected on the device.  top_k 1..64."""
+        which, p, keep = self._sc_query(query)
+        begin, end = self._sc_range(begin, end)
+        k = int(top_k)
+        cap = min(max(k, 1), self.SCAN_CONTEXT_MAX_TOP_K)
+        ids = np.empty(cap, dtype=np.int32); dist = np.empty(cap); shift = np.empty(cap, dtype=np.int32)
+        m = C.c_size_t(0)
+        self._ck(self._L.ngicp_scan_context_match(self._h, which, p, begin, end, k, _p(ids, c_i32p), _p(dist, c_f64p), _p(shift, c_i32p), C.byref(m)))
+        return ids[:m.value].copy(), dist[:m.value].copy(), shift[:m.value].copy()
+
+    def scanContextGuess(self, shift: int) -> np.ndarray:
+        """-> the 4x4 float32 rotation about z by shift * 2 pi / n_sectors: the guess that carries the query scan into the matched entry's
+        frame when both were taken at about the same place (for align / alignBatch)."""
+        _, S, _, _ = self.getScanContextParams()
+        a = float(shift) * (2.0 * np.pi / S)
+        T = np.eye(4, dtype=np.float32)
+        T[0, 0] = T[1, 1] = np.float32(np.cos(a))
+        T[1, 0] = np.float32(np.sin(a))
+        T[0, 1] = -T[1, 0]
+        return T
+
+    def scanContextKernelMs(self) -> float:
+        """device time of the kernels of the last scan context call (stats() is left alone)"""
+        ms = C.c_double(0)
+        self._ck(self._L.ngicp_scan_context_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
     def getFinalTransformation(self): return self.final_transformation_

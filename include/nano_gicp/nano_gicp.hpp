@@ -14,6 +14,7 @@
 // With PCL and Eigen installed the class uses pcl::PointCloud / Eigen::Matrix4f; without them (this repo's
 // build container) it uses the layout-compatible stand-ins of pcl_compat.hpp.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -747,6 +748,99 @@ class NanoGICP {
     return false;
   }
 
+  // ---- scan context (include/ngicp.h "scan context"): which earlier keyframe a scan revisits, and at what yaw.  A polar height
+  //      descriptor of a cloud that is already on the device (which: 0 = the input source, 1 = the target, 2 = the scan preprocessPoints
+  //      left there), a device-resident database of descriptors with dense ids in insertion order, and an exhaustive match over every
+  //      column shift.  On an error: a line on stderr and false / -1 / an empty vector.  Recipe: INTEGRATION.md.
+  struct ScanContextParams {
+    int n_rings = 20, n_sectors = 60;
+    float max_radius = 80.0f, z_offset = 2.0f;
+  };
+  struct ScanContextMatch {
+    int id;
+    double distance;
+    int shift;
+  };
+  // a change clears the database; a refused value changes nothing
+  bool setScanContextParams(int n_rings, int n_sectors, float max_radius, float z_offset) {
+    return h_ && check(ngicp_scan_context_set_params(h_, n_rings, n_sectors, max_radius, z_offset), "setScanContextParams");
+  }
+  ScanContextParams getScanContextParams() const {
+    ScanContextParams p;
+    if (h_) check(ngicp_scan_context_get_params(h_, &p.n_rings, &p.n_sectors, &p.max_radius, &p.z_offset), "getScanContextParams");
+    return p;
+  }
+  // the engine's tables: the squared ring edges (n_rings + 1) and the sector boundary directions (n_sectors floats, x and y interleaved)
+  bool scanContextTables(std::vector<float>& ring_edges_squared, std::vector<float>& boundary_directions) {
+    const ScanContextParams p = getScanContextParams();
+    ring_edges_squared.assign((size_t)p.n_rings + 1, 0.f);
+    boundary_directions.assign((size_t)p.n_sectors, 0.f);
+    return h_ && check(ngicp_scan_context_tables(h_, ring_edges_squared.data(), boundary_directions.data()), "scanContextTables");
+  }
+  // n_rings x n_sectors floats, row-major by ring
+  std::vector<float> computeScanContext(int which = 0) {
+    const ScanContextParams p = getScanContextParams();
+    std::vector<float> d((size_t)p.n_rings * p.n_sectors);
+    if (!h_ || !check(ngicp_scan_context_compute(h_, which, d.data()), "computeScanContext")) d.clear();
+    return d;
+  }
+  int addScanContext(int which = 0) {
+    int id = -1;
+    if (h_) check(ngicp_scan_context_add(h_, which, &id), "addScanContext");
+    return id;
+  }
+  int addScanContextDescriptor(const std::vector<float>& desc) {
+    const ScanContextParams p = getScanContextParams();
+    int id = -1;
+    if (desc.size() != (size_t)p.n_rings * p.n_sectors) {
+      std::fprintf(stderr, "[NanoGICP] addScanContextDescriptor: the descriptor must hold n_rings x n_sectors floats\n");
+      return id;
+    }
+    if (h_) check(ngicp_scan_context_add_descriptor(h_, desc.data(), &id), "addScanContextDescriptor");
+    return id;
+  }
+  size_t numScanContexts() const {
+    size_t n = 0;
+    if (h_) ngicp_scan_context_count(h_, &n);
+    return n;
+  }
+  std::vector<float> scanContext(int id) {
+    const ScanContextParams p = getScanContextParams();
+    std::vector<float> d((size_t)p.n_rings * p.n_sectors);
+    if (!h_ || !check(ngicp_scan_context_get(h_, id, d.data()), "scanContext")) d.clear();
+    return d;
+  }
+  void clearScanContexts() {
+    if (h_) check(ngicp_scan_context_clear(h_), "clearScanContexts");
+  }
+  // distance and shift of the slot's cloud / of a host descriptor to every entry of [begin, end): entry g describes id begin + g (its id
+  // is filled in); in id order, not ranked
+  std::vector<ScanContextMatch> scanContextDistances(int which, size_t begin, size_t end) { return scanContextDistancesOf(which, nullptr, begin, end); }
+  std::vector<ScanContextMatch> scanContextDistances(const std::vector<float>& desc, size_t begin, size_t end) {
+    return descriptorFits(desc, "scanContextDistances") ? scanContextDistancesOf(-1, desc.data(), begin, end) : std::vector<ScanContextMatch>();
+  }
+  // the first min(top_k, end - begin) entries of [begin, end) ascending by (distance, id), selected on the device; top_k 1..64
+  std::vector<ScanContextMatch> matchScanContext(int which, size_t begin, size_t end, int top_k = 1) { return matchScanContextOf(which, nullptr, begin, end, top_k); }
+  std::vector<ScanContextMatch> matchScanContext(const std::vector<float>& desc, size_t begin, size_t end, int top_k = 1) {
+    return descriptorFits(desc, "matchScanContext") ? matchScanContextOf(-1, desc.data(), begin, end, top_k) : std::vector<ScanContextMatch>();
+  }
+  // the rotation about z by shift * 2 pi / n_sectors: the guess that carries the query scan into the matched entry's frame when both
+  // were taken at about the same place - for align() or, with its neighbours, alignBatch()
+  Matrix4 scanContextGuess(int shift) const {
+    const double a = (double)shift * (6.283185307179586476925286766559 / (double)getScanContextParams().n_sectors);
+    Matrix4 T;
+    set_identity(T);
+    T(0, 0) = T(1, 1) = (float)std::cos(a);
+    T(1, 0) = (float)std::sin(a);
+    T(0, 1) = -T(1, 0);
+    return T;
+  }
+  double scanContextKernelMs() const {
+    double ms = 0.0;
+    if (h_) ngicp_scan_context_kernel_ms(h_, &ms);
+    return ms;
+  }
+
   // ---- extensions with no reference counterpart (include/ngicp.h "keyframe store", "rigid transform"): the keyframes and the
   //      submap stay on the GPU.  In DLO they replace odom.cc:1174 (`keyframe_normals.push_back(gicp_s2s.getSourceCovariances())`)
   //      and odom.cc:830-833 (`setInputTarget(submap_cloud); setTargetCovariances(submap_normals)`); see INTEGRATION.md ----
@@ -902,6 +996,32 @@ class NanoGICP {
     f.n_inliers = r.n_inliers;
     f.n_matched = r.n_matched;
     return f;
+  }
+  bool descriptorFits(const std::vector<float>& desc, const char* what) const {
+    const ScanContextParams p = getScanContextParams();
+    if (desc.size() == (size_t)p.n_rings * p.n_sectors) return true;
+    std::fprintf(stderr, "[NanoGICP] %s: the descriptor must hold n_rings x n_sectors floats\n", what);
+    return false;
+  }
+  std::vector<ScanContextMatch> scanContextDistancesOf(int which, const float* desc, size_t begin, size_t end) {
+    std::vector<ScanContextMatch> out;
+    if (!h_) return out;
+    const size_t n = end > begin ? end - begin : 0;
+    std::vector<double> dist(n + 1);
+    std::vector<int> shift(n + 1);
+    if (!check(ngicp_scan_context_distances(h_, which, desc, begin, end, dist.data(), shift.data()), "scanContextDistances")) return out;
+    for (size_t g = 0; g < n; ++g) out.push_back(ScanContextMatch{(int)(begin + g), dist[g], shift[g]});
+    return out;
+  }
+  std::vector<ScanContextMatch> matchScanContextOf(int which, const float* desc, size_t begin, size_t end, int top_k) {
+    std::vector<ScanContextMatch> out;
+    if (!h_) return out;
+    int ids[64], shift[64];
+    double dist[64];
+    size_t n = 0;
+    if (!check(ngicp_scan_context_match(h_, which, desc, begin, end, top_k, ids, dist, shift, &n), "matchScanContext")) return out;
+    for (size_t g = 0; g < n; ++g) out.push_back(ScanContextMatch{ids[g], dist[g], shift[g]});
+    return out;
   }
   static void set_identity(Matrix4& m) { for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) m(r, c) = r == c ? 1.f : 0.f; }
 

@@ -555,6 +555,60 @@ int ngicp_voxel_fitness_points(ngicp_t* h, const float T_colmajor_or_null[16], d
  * kept here and not in ngicp_stats, which these calls leave alone */
 int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms);
 
+/* --- scan context: which earlier keyframe does this scan revisit, and at what yaw (no counterpart in the reference;
+ *     csrc/ngicp_scan_context.h) ------------------------------------------------------------------------------------
+ * A polar height descriptor of a scan in the manner of Scan Context (Kim & Kim, IROS 2018), a device-resident database of such
+ * descriptors (one per keyframe) and an exhaustive match of a query against a range of the database over every column shift.  The
+ * definition is this project's own, written so that a host restates it bit for bit (tests/_scan_context_model.py); no fidelity to any
+ * outside implementation is claimed.  There is no pruning stage (no ring key, no tree): every candidate is matched at every shift.
+ *   parameters  n_rings R in 1..64, n_sectors S even in 2..64, max_radius L > 0 finite, z_offset z0 finite; defaults 20, 60, 80.0f, 2.0f.
+ *   tables      built on the host once per parameter change: ring edges e_k = (float)((double)L * k / R) and E2_k = e_k * e_k in float,
+ *               k = 0..R; sector boundary directions b_k = ((float)cos(2 pi k / S), (float)sin(2 pi k / S)), k = 0..S/2-1, computed in
+ *               double.  ngicp_scan_context_tables returns both (E2: R + 1 floats; b: S floats, x and y interleaved).
+ *   a point     (x, y, z) float.  A non-finite coordinate: skipped.  r2 = x*x + y*y (two rounded products, one addition, nothing
+ *               fused); skipped unless r2 < E2_R.  ring = the number of k in 1..R-1 with r2 >= E2_k.  low = y < 0 || (y == 0 && x < 0);
+ *               (xs, ys) = low ? (-x, -y) : (x, y).  sector = the number of k in 1..S/2-1 with b_k.x * ys - b_k.y * xs >= 0 (two rounded
+ *               products, one subtraction), plus S/2 if low - a COUNT, not a search: it stays defined where rounding breaks monotonicity
+ *               near a boundary.  v = z + z0 in float.
+ *   descriptor  D[R][S] floats, row-major by ring; every cell starts at 0.0f; D[ring][sector] = max(D[ring][sector], v).  A maximum does
+ *               not depend on order: the descriptor is deterministic.  Cells are >= 0.
+ *   norms       n_j = sqrt(sum_r (double)D[r][j] * (double)D[r][j]), r ascending from 0.0, the root correctly rounded.
+ *   distance    of query Q to candidate C at shift k (0 <= k < S), all in double: with j' = (j + k) mod S, column j counts iff
+ *               nq_j > 0 && nc_j' > 0; its term is (sum_r (double)Q[r][j] * (double)C[r][j']) / (nq_j * nc_j'), r ascending from 0.0;
+ *               d_k = 1.0 - (sum of the counted terms, j ascending from 0.0) / (double)m for m counted columns, 1.0 when m = 0.
+ *               dist(Q, C) = min_k d_k and shift = the smallest k that attains it (a scan with k ascending under strict <).
+ *   the shift   column j of the query lies on column j + k of the candidate: if the query scan was taken at the candidate's place with
+ *               the sensor yawed by psi, k is about psi / (2 pi / S), and the guess that carries the query scan into the candidate's
+ *               frame is a rotation about z by k * 2 pi / S.
+ *   ranking     candidates ascending by (distance, id).
+ * which: as ngicp_range_select defines it (0 source, 1 target, 2 the preprocessed scan; non-finite rows left in it are skipped), with its
+ * state errors.  A query is EITHER a slot (which 0..2 and desc_or_null NULL) OR a host descriptor (which -1 and R * S floats).  Host
+ * descriptors must be finite and >= 0, else NGICP_ERR_ARG.  Ids are dense in insertion order, like keyframe ids.
+ * Everything passed in is checked before anything is enqueued; a refused call changes nothing.  None of these entries changes what any
+ * existing getter returns: scratch of their own; hooks, results, stats and batch traces are left alone. */
+/* A refused value is NGICP_ERR_ARG and changes nothing; an accepted CHANGE clears the database (as a change of resolution clears the
+ * rolling map); setting the values in force is a no-op. */
+int ngicp_scan_context_set_params(ngicp_t* h, int n_rings, int n_sectors, float max_radius, float z_offset);
+int ngicp_scan_context_get_params(const ngicp_t* h, int* n_rings, int* n_sectors, float* max_radius, float* z_offset);
+int ngicp_scan_context_tables(ngicp_t* h, float* E2_out_R_plus_1, float* b_out_S);
+/* the descriptor of a slot's cloud, R * S floats to the host; a cloud whose points are all skipped gives the all-zero descriptor */
+int ngicp_scan_context_compute(ngicp_t* h, int which, float* desc_out);
+/* compute the descriptor and append it, with its column norms, without leaving the device / append a host descriptor */
+int ngicp_scan_context_add(ngicp_t* h, int which, int* id);
+int ngicp_scan_context_add_descriptor(ngicp_t* h, const float* desc, int* id);
+int ngicp_scan_context_count(const ngicp_t* h, size_t* n);
+int ngicp_scan_context_get(ngicp_t* h, int id, float* desc_out);
+int ngicp_scan_context_clear(ngicp_t* h);
+/* distance and shift of the query to every entry of [id_begin, id_end): id_end - id_begin values each, one launch, one read-back.
+ * id_end > count or id_begin > id_end is NGICP_ERR_ARG; an empty range writes nothing and succeeds. */
+int ngicp_scan_context_distances(ngicp_t* h, int which_or_minus1, const float* desc_or_null, size_t id_begin, size_t id_end, double* dist_out, int* shift_out);
+/* the first min(top_k, id_end - id_begin) entries of the ranking, selected on the device (top_k in 1..64; the outputs hold top_k
+ * entries); *n_out = their number, 0 for an empty range */
+int ngicp_scan_context_match(ngicp_t* h, int which_or_minus1, const float* desc_or_null, size_t id_begin, size_t id_end, int top_k, int* ids_out, double* dist_out,
+                             int* shift_out, size_t* n_out);
+/* device time of the kernels of the last compute / add / distances / match call (as ngicp_voxel_fitness_kernel_ms) */
+int ngicp_scan_context_kernel_ms(const ngicp_t* h, double* ms);
+
 /* The small FP64 routines of the engine evaluated on the device, one problem per thread (unit-test hook): which = 0 so3_exp
  * (gicp/so3.hpp:99-118 followed by Quaternion::toRotationMatrix; in: 3 doubles, out: R row-major 9), 1 the 6x6 LDLT solve that
  * stands in for Eigen::LDLT (impl/lsq_registration_impl.hpp:147-148,172-173; in: A row-major 36 + rhs 6, out: 6), 2 the
