@@ -700,6 +700,8 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->ev_vfit_b) (void)hipEventDestroy(h->ev_vfit_b);
   if (h->sc.ev_a) (void)hipEventDestroy(h->sc.ev_a);
   if (h->sc.ev_b) (void)hipEventDestroy(h->sc.ev_b);
+  for (hipEvent_t e : h->ps.ev)
+    if (e) (void)hipEventDestroy(e);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -2335,3 +2337,6 @@ int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms) {
 
 // ---- scan context place recognition: descriptors, their database, matching (csrc/ngicp_scan_context.h) ----
 #include "ngicp_scan_context.h"  // (kernels and entries; behind everything else, so that the code object up to here is laid out as it was)
+
+// ---- voxel pose search: a lattice of poses scored by occupied-voxel hits, the best few returned (csrc/ngicp_pose_search.h) ----
+#include "ngicp_pose_search.h"  // (kernels and entries; behind everything else, for the same reason)

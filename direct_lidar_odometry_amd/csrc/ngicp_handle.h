@@ -413,6 +413,7 @@ struct ngicp {
   struct RollMap {
     size_t n_vox = 0, cap = 0, slots = 0;  // voxels, capacity of the per-voxel arrays (doubling), hash table slots (>= 2 * n_vox, a power of two)
     long long inserts = 0;                 // accepted inserts since the last clear: the stamp of the last one
+    long long gen = 0;                     // bumped wherever the map is written (insert, evict, clear, restore, move): what a kept result was computed against
     DevBuf sums, rec, vkeys, stamps, table;  // [cap][kVoxRec] {S 3, C 6, n}, [cap][kVoxRec] records, [cap] keys, [cap] stamps, [slots] {key, voxel number}
     double last_insert_ms = 0.0, last_evict_ms = 0.0;  // device event times
   } roll;
@@ -442,6 +443,16 @@ struct ngicp {
     hipEvent_t ev_a = nullptr, ev_b = nullptr;  // around a call's kernels (created on first use; its own pair: ngicp_stats is left alone)
     double kernel_ms = 0.0;              // ngicp_scan_context_kernel_ms
   } sc;
+  // voxel pose search (csrc/ngicp_pose_search.h): a query's own workspace, grow-only
+  struct PoseSearch {
+    DevBuf T, box, grid, score, cand;    // the base poses [B][16]; the two cell boxes (12 ints); the occupancy bit grid; the score volume [B][|S|]; the top-k levels' keys
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the box kernels and around everything behind their read-back (created on first use)
+    double kernel_ms = 0.0;              // ngicp_voxel_pose_search_kernel_ms
+    bool valid = false;                  // `score` holds the volume of a finished search of `entries` ints ...
+    size_t entries = 0;
+    bool stamp_rolling = false;          // ... computed against this map: the rolling one at generation stamp_gen, or build number stamp_gen of the target's
+    long long stamp_gen = 0;
+  } ps;
 };
 
 namespace {

@@ -66,6 +66,7 @@ void roll_clear(ngicp* h) {
   h->roll.inserts = 0;
   if (h->roll.slots) roll_refill_table(h);  // (memory stays with the handle)
   h->hook_valid = 0;
+  ++h->roll.gen;
 }
 
 void roll_require_on(const ngicp* h, const char* entry) {
@@ -134,7 +135,8 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   exclusive_scan_flags(h, is_new, n_seg, rank);
   roll_launch_commit(h, sg, n_seg, rank, r.n_vox, nullptr);
   HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
-  h->hook_valid = 0;  // (from here on the map is being written)
+  h->hook_valid = 0;
+  ++h->roll.gen;  // (from here on the map is being written)
   const int n_new = read_count(h, rank + n_seg).count;
   if (n_new < 0 || n_new > n_seg) throw ArgError{NGICP_ERR_HIP, "rolling voxel map insert: inconsistent count of new voxels"};
   r.n_vox += (size_t)n_new;
@@ -202,6 +204,7 @@ void roll_insert_records(ngicp* h, const RollRecs& in, const long long* stamps_i
   if (base + (size_t)n_new > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": too many voxels for int indices"};
   // ---- from here on the map is written (the lookup has finished: a move's own records, and another handle's, are not read again) ----
   h->hook_valid = 0;
+  ++h->roll.gen;
   if (move) r.n_vox = 0;  // nothing of the former arrays is kept: the destination sums are in the workspace
   roll_reserve(h, base + (size_t)n_new);
   if (!roll_reserve_table(h, base + (size_t)n_new) && move) roll_refill_table(h);  // (n_vox == 0: the table cleared)
@@ -296,6 +299,7 @@ void roll_set(ngicp* h, size_t n, const int* ijk, const double* sum_n3, const do
   // ---- from here on the map is written ----
   ngicp::RollMap& r = h->roll;
   h->hook_valid = 0;
+  ++h->roll.gen;
   r.n_vox = 0;  // (nothing of the former map is kept when an array grows)
   r.inserts = inserts;
   if (n == 0) {
@@ -330,6 +334,7 @@ void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_
   if (std::isnan(max_dist)) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_rolling_evict: max_dist is not a number"};
   ngicp::RollMap& r = h->roll;
   h->hook_valid = 0;
+  ++h->roll.gen;
   if (n_removed_out) *n_removed_out = 0;
   const int n = (int)r.n_vox;
   if (n == 0) return;

@@ -233,6 +233,13 @@ VoxelMapView voxel_map_view(const ngicp* h) {
   return VoxelMapView{m.table.as<ulonglong2>(), m.mask, m.rec.as<double>(), m.vkeys.as<unsigned long long>(), m.n_vox};
 }
 
+// Would ensure_voxel_map return the target's map as it stands (no upload, no covariances, no build)?  Not meant for the rolling map.
+bool voxel_map_current(const ngicp* h) {
+  const ngicp::VoxelMap& m = h->vmap;
+  if (!h->tgt.dev || h->tgt_covs.n != h->tgt.dev->n) return false;
+  return m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && m.merged == (merged_route_applies(h) ? 1 : 0);
+}
+
 // The voxel map of the current target, its covariances (computed if missing, as for align) and the resolution: built at the first use
 // after any of the three changed, or after the route it would be built by did (ngicp_set_voxel_submap_merge).  With the rolling setting
 // on: the rolling map as inserts and evictions left it (nothing is built, the target and the merged setting are not consulted); an
@@ -247,7 +254,7 @@ VoxelMapView ensure_voxel_map(ngicp* h) {
   const double* covs = covs_for(h, h->tgt_covs, h->tgt.dev);
   ngicp::VoxelMap& m = h->vmap;
   const int merged = merged_route_applies(h) ? 1 : 0;
-  if (m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && m.merged == merged) return voxel_map_view(h);
+  if (voxel_map_current(h)) return voxel_map_view(h);
   m.invalidate();
   if (merged) build_voxel_map_merged(h);
   else build_voxel_map_from_points(h, covs);

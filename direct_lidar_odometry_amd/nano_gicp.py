@@ -106,6 +106,7 @@ EXPORTS = [
     "ngicp_scan_context_set_params", "ngicp_scan_context_get_params", "ngicp_scan_context_tables", "ngicp_scan_context_compute",
     "ngicp_scan_context_add", "ngicp_scan_context_add_descriptor", "ngicp_scan_context_count", "ngicp_scan_context_get", "ngicp_scan_context_clear",
     "ngicp_scan_context_distances", "ngicp_scan_context_match", "ngicp_scan_context_kernel_ms",
+    "ngicp_voxel_pose_search", "ngicp_voxel_pose_search_scores", "ngicp_voxel_pose_search_kernel_ms",
 ]
 
 
@@ -257,6 +258,9 @@ def load_library() -> C.CDLL:
     L.ngicp_scan_context_distances.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, c_f64p, c_i32p]
     L.ngicp_scan_context_match.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, C.c_size_t, C.c_int, c_i32p, c_f64p, c_i32p, c_szp]
     L.ngicp_scan_context_kernel_ms.argtypes = [vp, c_f64p]
+    L.ngicp_voxel_pose_search.argtypes = [vp, C.c_size_t, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_szp]
+    L.ngicp_voxel_pose_search_scores.argtypes = [vp, c_i32p, C.c_size_t]
+    L.ngicp_voxel_pose_search_kernel_ms.argtypes = [vp, c_f64p]
     _lib = L
     return L
 
@@ -866,6 +870,78 @@ class NanoGICP:
         """device time of the kernels of the last scan context call (stats() is left alone)"""
         ms = C.c_double(0)
         self._ck(self._L.ngicp_scan_context_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # ---- voxel pose search (include/ngicp.h "voxel pose search"): the translation, and the best of several orientations, on the voxel map ----
+    POSE_SEARCH_MAX_TOP_K = 64
+
+    @staticmethod
+    def yawLattice(T0, n: int, step_rad: float) -> np.ndarray:
+        """-> (n, 4, 4) float32: T0 . Rz(k * step_rad), k = 0..n-1, the product taken in float64 and rounded once.  Base poses for
+        voxelPoseSearch; they are INPUT to the engine and to any host restatement alike, so how this helper rounds shows in no result."""
+        T0 = np.asarray(T0, np.float64)
+        if T0.shape != (4, 4):
+            raise NgicpError(-2, "yawLattice: T0 must be (4, 4)")
+        out = np.empty((max(int(n), 0), 4, 4), dtype=np.float32)
+        for k in range(out.shape[0]):
+            a = k * float(step_rad)
+            Rz = np.eye(4)
+            Rz[0, 0] = Rz[1, 1] = np.cos(a)
+            Rz[1, 0] = np.sin(a)
+            Rz[0, 1] = -Rz[1, 0]
+            out[k] = (T0 @ Rz).astype(np.float32)
+        return out
+
+    @staticmethod
+    def poseSearchCandidate(T, shift, res: float) -> np.ndarray:
+        """-> the 4x4 float32 candidate pose of a base pose T and a shift (sx, sy, sz) in voxels: T with its translation replaced, per
+        axis, by (float)((double)t + (double)s * res)."""
+        out = np.array(T, dtype=np.float32)
+        t = out[:3, 3].astype(np.float64) + np.asarray(shift, np.float64) * np.float64(res)
+        out[:3, 3] = t.astype(np.float32)
+        return out
+
+    def voxelPoseSearch(self, Ts, extent, top_k: int = 8):
+        """Score every pose of the lattice {Ts[b] shifted by (sx, sy, sz) voxels, |s| <= extent = (ex, ey, ez)} by the number of source
+        points that land in occupied voxels of the map in force, and return the first m = min(top_k, B |S|) of the ranking (descending
+        score, then ascending pose, then ascending shift index) -> (pose (m,) int32, shift (m, 3) int32, score (m,) int32,
+        T (m, 4, 4) float32: the candidate poses, for alignBatchVoxel).  The score is defined on cells (include/ngicp.h): the float
+        candidate pose may put a point near a cell border into another cell.  ex, ey <= 31, ez <= 7, |S| <= 12288, B |S| <= 2^24."""
+        t = np.asarray(Ts)
+        if t.ndim != 3 or t.shape[1:] != (4, 4):
+            raise NgicpError(-2, "voxelPoseSearch: Ts must be (B, 4, 4)")
+        ext = tuple(int(v) for v in extent)
+        if len(ext) != 3:
+            raise NgicpError(-2, "voxelPoseSearch: extent must be (ex, ey, ez)")
+        B = t.shape[0]
+        tf = np.ascontiguousarray(t, dtype=np.float32)
+        tc = np.ascontiguousarray(np.transpose(tf, (0, 2, 1))).reshape(B, 16)
+        k = int(top_k)
+        cap = min(max(k, 1), self.POSE_SEARCH_MAX_TOP_K)
+        pose = np.empty(cap, dtype=np.int32); shift = np.empty((cap, 3), dtype=np.int32); score = np.empty(cap, dtype=np.int32)
+        m = C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_pose_search(self._h, B, _p(tc, c_f32p) if B else None, ext[0], ext[1], ext[2], k, _p(pose, c_i32p), _p(shift, c_i32p),
+                                                 _p(score, c_i32p), C.byref(m)))
+        self._ps_shape = (B, 2 * ext[2] + 1, 2 * ext[1] + 1, 2 * ext[0] + 1)
+        n = m.value
+        res = self.getVoxelResolution()
+        cand = np.empty((n, 4, 4), dtype=np.float32)
+        for i in range(n):
+            cand[i] = self.poseSearchCandidate(tf[pose[i]], shift[i], res)
+        return pose[:n].copy(), shift[:n].copy(), score[:n].copy(), cand
+
+    def voxelPoseSearchScores(self) -> np.ndarray:
+        """-> the full score volume of the last voxelPoseSearch, (B, 2 ez + 1, 2 ey + 1, 2 ex + 1) int32; refused (NGICP_ERR_STATE) when
+        there has been no search or the map has changed since"""
+        shape = getattr(self, "_ps_shape", (1, 1, 1, 1))
+        out = np.empty(shape, dtype=np.int32)
+        self._ck(self._L.ngicp_voxel_pose_search_scores(self._h, _p(out, c_i32p), out.size))
+        return out
+
+    def voxelPoseSearchKernelMs(self) -> float:
+        """device time of the kernels of the last voxelPoseSearch (stats() is left alone)"""
+        ms = C.c_double(0)
+        self._ck(self._L.ngicp_voxel_pose_search_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
     def getFinalTransformation(self): return self.final_transformation_

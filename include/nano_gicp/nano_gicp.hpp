@@ -841,6 +841,75 @@ class NanoGICP {
     return ms;
   }
 
+  // ---- voxel pose search (include/ngicp.h "voxel pose search"): a lattice of poses - the base poses times a window of whole-voxel
+  //      shifts - scored by the number of source points that land in occupied voxels of the map in force; the best few come back with
+  //      their candidate poses, for alignBatchVoxel.  Scan context gives the yaw, this the translation.  On an error: a
+  //      line on stderr and an empty vector.  Recipe: INTEGRATION.md.
+  struct PoseSearchCandidate {
+    int pose;       // index into the base poses
+    int shift[3];   // (sx, sy, sz) in voxels
+    int score;      // source points in occupied voxels, counted on cells
+    Matrix4 T;      // the candidate pose: the base pose with its translation replaced by (float)((double)t + (double)s * resolution)
+  };
+  // T0 . Rz(k * step_rad), k = 0..n-1, the product taken in double and rounded once: base poses for voxelPoseSearch
+  static std::vector<Matrix4> yawLattice(const Matrix4& T0, int n, double step_rad) {
+    std::vector<Matrix4> out;
+    for (int k = 0; k < n; ++k) {
+      const double c = std::cos((double)k * step_rad), s = std::sin((double)k * step_rad);
+      Matrix4 T = T0;
+      for (int r = 0; r < 4; ++r) {
+        const double a = (double)T0(r, 0), b = (double)T0(r, 1);
+        T(r, 0) = (float)(a * c + b * s);
+        T(r, 1) = (float)(b * c - a * s);
+      }
+      out.push_back(T);
+    }
+    return out;
+  }
+  static Matrix4 poseSearchCandidate(const Matrix4& T, const int shift[3], double resolution) {
+    Matrix4 out = T;
+    for (int a = 0; a < 3; ++a) {
+      volatile double step = (double)shift[a] * resolution;  // (rounded on its own: never fused into the addition)
+      out(a, 3) = (float)((double)T(a, 3) + step);
+    }
+    return out;
+  }
+  // the first min(top_k, B |S|) entries by descending score, then ascending pose, then ascending shift index; top_k 1..64,
+  // ex, ey <= 31, ez <= 7, (2 ex + 1)(2 ey + 1)(2 ez + 1) <= 12288, B times that <= 2^24
+  std::vector<PoseSearchCandidate> voxelPoseSearch(const std::vector<Matrix4>& poses, int ex, int ey, int ez, int top_k = 8) {
+    std::vector<PoseSearchCandidate> out;
+    if (!h_) return out;
+    std::vector<float> T(poses.size() * 16);
+    for (size_t i = 0; i < poses.size(); ++i) std::memcpy(&T[i * 16], poses[i].data(), 16 * sizeof(float));
+    const size_t cap = (size_t)std::min(std::max(top_k, 1), 64);
+    std::vector<int> pose(cap), shift(3 * cap), score(cap);
+    size_t n = 0;
+    if (!check(ngicp_voxel_pose_search(h_, poses.size(), poses.empty() ? nullptr : T.data(), ex, ey, ez, top_k, pose.data(), shift.data(), score.data(), &n), "voxelPoseSearch"))
+      return out;
+    pose_search_entries_ = poses.size() * (size_t)(2 * ex + 1) * (size_t)(2 * ey + 1) * (size_t)(2 * ez + 1);
+    for (size_t i = 0; i < n; ++i) {
+      PoseSearchCandidate c;
+      c.pose = pose[i];
+      for (int a = 0; a < 3; ++a) c.shift[a] = shift[3 * i + a];
+      c.score = score[i];
+      c.T = poseSearchCandidate(poses[(size_t)pose[i]], c.shift, voxel_resolution_);
+      out.push_back(c);
+    }
+    return out;
+  }
+  // the last search's full volume [B][2 ez + 1][2 ey + 1][2 ex + 1]; empty when there has been none or the map has changed since
+  std::vector<int> voxelPoseSearchScores() {
+    std::vector<int> v(std::max<size_t>(pose_search_entries_, 1));
+    if (!h_ || !check(ngicp_voxel_pose_search_scores(h_, v.data(), v.size()), "voxelPoseSearchScores")) v.clear();
+    else v.resize(pose_search_entries_);
+    return v;
+  }
+  double voxelPoseSearchKernelMs() const {
+    double ms = 0.0;
+    if (h_) ngicp_voxel_pose_search_kernel_ms(h_, &ms);
+    return ms;
+  }
+
   // ---- extensions with no reference counterpart (include/ngicp.h "keyframe store", "rigid transform"): the keyframes and the
   //      submap stay on the GPU.  In DLO they replace odom.cc:1174 (`keyframe_normals.push_back(gicp_s2s.getSourceCovariances())`)
   //      and odom.cc:830-833 (`setInputTarget(submap_cloud); setTargetCovariances(submap_normals)`); see INTEGRATION.md ----
@@ -1046,6 +1115,7 @@ class NanoGICP {
   bool converged_ = false;
   int nr_iterations_ = 0;
   double voxel_resolution_ = 0.0;
+  size_t pose_search_entries_ = 0;  // B |S| of the last successful voxelPoseSearch: what voxelPoseSearchScores asks for
   bool voxel_rolling_ = false;
   mutable CovVector cache_src_, cache_tgt_;
 };

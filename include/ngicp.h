@@ -609,6 +609,55 @@ int ngicp_scan_context_match(ngicp_t* h, int which_or_minus1, const float* desc_
 /* device time of the kernels of the last compute / add / distances / match call (as ngicp_voxel_fitness_kernel_ms) */
 int ngicp_scan_context_kernel_ms(const ngicp_t* h, double* ms);
 
+/* --- voxel pose search: which translation (and which of several orientations) puts the source on the voxel map (no counterpart in
+ *     the reference; csrc/ngicp_pose_search.h) ---------------------------------------------------------------------
+ * Correlative scan matching in the manner of Olson (ICRA 2009): an exhaustive search over a lattice of poses - B base poses times a
+ * window of whole-voxel shifts - each scored by the number of source points that land in occupied voxels; the best few come back and
+ * are meant for ngicp_voxel_align_batch.  The score is an integer: sums are order-free, the result is deterministic and a host
+ * restates it exactly (tests/_pose_search_model.py).  The definition is the project's own:
+ *   inputs     B >= 1 base poses T_b (float 4x4, column-major); integer extents ex, ey, ez >= 0; top_k in 1..64; the source cloud (its
+ *              covariances are neither needed nor computed); the voxel map exactly as ngicp_voxel_fitness takes it (the target's, the
+ *              merged one or the rolling one; built if stale, at most once per call; an empty rolling map is NGICP_ERR_STATE).
+ *   the cell   c_b(p) = floorf(q * inv_res) of q = the float pose T_b times the source point p in the passes' order,
+ *              ((c0 x + c1 y) + c2 z) + c3 per row, nothing fused - as everywhere in the voxelized mode.  A point with a component at or
+ *              beyond 2^20 cells, or a NaN coordinate, has no cell.  A source cloud cannot hold a non-finite point (it is refused when
+ *              it is set), so q is NaN or infinite only through the pose: unlike most entries this one does NOT refuse a non-finite
+ *              T_b - the poses are not inspected on the host - and such a pose simply scores 0 wherever its points lose their cells.
+ *   shifts     s = (sx, sy, sz) with |sx| <= ex, |sy| <= ey, |sz| <= ez; the index of a shift is
+ *              ((sz + ez)(2 ey + 1) + (sy + ey))(2 ex + 1) + (sx + ex); |S| = (2 ex + 1)(2 ey + 1)(2 ez + 1) is their number.
+ *   score      score[b][s], int32 = the number of source points that have a cell, for which every component of c_b(p) + s lies strictly
+ *              inside (-2^20, 2^20) (the passes' neighbour rule), and whose voxel c_b(p) + s is in the map's table.  Duplicate points
+ *              count each time.  The neighbourhood setting (DIRECT1 / 7 / 27) is not consulted.
+ *   on cells   The score is defined ON CELLS: it moves the point's cell by s.  The float pose T_b translated by s * res may put a point
+ *              that lies near a cell border into another cell, so ngicp_voxel_fitness at a candidate pose need not report exactly
+ *              score[b][s] matched points.  At s = 0 it does: score[b][0] equals n_matched of ngicp_voxel_fitness_batch under DIRECT1
+ *              at T_b.
+ *   ranking    descending score, then ascending b, then ascending shift index; the result is the first min(top_k, B |S|) entries,
+ *              selected on the device, with one read-back.
+ *   candidate  the pose of entry (b, s), computed on the host by the caller (the C++ shim and the Python wrapper do): T_b with its
+ *              translation replaced, per axis, by (float)((double)t + (double)s * res), res the voxel resolution as a double.
+ *   caps       ex, ey <= 31 (a row of shifts is at most 63 bits wide), ez <= 7, |S| <= 12288 (48 KB of int32 in LDS), B |S| <= 2^24.
+ *              Anything beyond a cap is NGICP_ERR_ARG before anything is enqueued; tile a larger window with more base poses (sub-voxel
+ *              steps likewise: base poses offset by a fraction of a voxel).
+ * How: the map's cell bounding box and the source's over all base poses are computed on the device and read back together; the host
+ * plans a dense occupancy bit grid over map box INTERSECTED WITH (source box dilated by the extents), x along the bits of 64-bit words,
+ * rows padded with guard words; a grid beyond 256 MiB is NGICP_ERR_ARG (the one refusal that comes after kernels have run; it still
+ * changes nothing).  An empty intersection gives all-zero scores, ranked by index.
+ * A query: the robust kernel, the pose prior and max_correspondence_distance are not consulted and nothing is refused because they
+ * are set; the hooks' state, the results, trace and stats of the last ngicp_align and the lanes and traces of the last batch call are
+ * left untouched.  Errors: voxel mode off NGICP_ERR_STATE; no source as ngicp_align; empty rolling map NGICP_ERR_STATE; n_poses == 0, a
+ * null pointer, a cap or a bad top_k NGICP_ERR_ARG.  A refused call changes nothing.
+ * Outputs hold top_k entries each (shift_out_xyz: 3 ints per entry); *n_out = the number written. */
+int ngicp_voxel_pose_search(ngicp_t* h, size_t n_poses, const float* T_n16_colmajor, int ex, int ey, int ez, int top_k, int* pose_out, int* shift_out_xyz, int* score_out,
+                            size_t* n_out);
+/* The full volume of the last successful search, [B][2 ez + 1][2 ey + 1][2 ex + 1] int32 (the shift index order), capacity >= B |S|
+ * entries.  NGICP_ERR_STATE when there has been no search, or when the map has changed since (an insert, evict, clear, restore or move of
+ * the rolling map; another target, resolution or map setting). */
+int ngicp_voxel_pose_search_scores(ngicp_t* h, int* out, size_t capacity);
+/* device time of the kernels of the last search: the two box kernels, and - behind their read-back - the grid fill, the score kernel
+ * and the top-k levels (as ngicp_voxel_fitness_kernel_ms) */
+int ngicp_voxel_pose_search_kernel_ms(const ngicp_t* h, double* ms);
+
 /* The small FP64 routines of the engine evaluated on the device, one problem per thread (unit-test hook): which = 0 so3_exp
  * (gicp/so3.hpp:99-118 followed by Quaternion::toRotationMatrix; in: 3 doubles, out: R row-major 9), 1 the 6x6 LDLT solve that
  * stands in for Eigen::LDLT (impl/lsq_registration_impl.hpp:147-148,172-173; in: A row-major 36 + rhs 6, out: 6), 2 the
