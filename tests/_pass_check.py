@@ -320,9 +320,21 @@ def _shape_rig(ng, orc, shape, tuning=0.1, env=None):
     return Rig(ng, orc, src, tgt, 20, 1.0, SHAPE_SETTINGS, covs=covs, tuning=tuning, env=env), SHAPE_GUESS
 
 
+def _crowded_rig(ng, orc, case, tuning=None, env=None, gate=1.0):
+    """crowded_cell / crowded_row (tests/_index_history_cases.py): more than 65 535 target points in one cell / in front of a batch
+    box inside a grid row, the voxel pinned, fixed isotropic covariances as in _shape_rig."""
+    import _index_history_cases as ic
+    voxel, _, guess = ic.CROWDED[case]
+    src, tgt = ic.CROWDED_CLOUDS[case]()
+    covs = (np.repeat(ic.ISO_COV[None], len(src), 0), np.repeat(ic.ISO_COV[None], len(tgt), 0))
+    return Rig(ng, orc, src, tgt, 20, gate, ic.CROWDED_SETTINGS, covs=covs, tuning=voxel if tuning is None else tuning, env=env), guess
+
+
 def make_rig(ng, orc, case, tuning=None, env=None):
-    """(Rig, guess) of a named workload: a 10k scan-to-scan case of CASES, an adversarial shape (0.1 m voxel unless `tuning`), or
-    c3_fixed20 / c3_dlo (the bench's scan-to-submap, 100k -> 500k, per-keyframe target covariances)."""
+    """(Rig, guess) of a named workload: a 10k scan-to-scan case of CASES, an adversarial shape (0.1 m voxel unless `tuning`),
+    c3_fixed20 / c3_dlo (the bench's scan-to-submap, 100k -> 500k, per-keyframe target covariances), or crowded_cell / crowded_row."""
+    if case in ("crowded_cell", "crowded_row"):
+        return _crowded_rig(ng, orc, case, tuning, env, gate=None)  # no gate: the batches list their region's rows
     if case in SHAPES:
         return _shape_rig(ng, orc, case, 0.1 if tuning is None else tuning, env)
     if case in ("c3_fixed20", "c3_dlo"):
