@@ -280,6 +280,7 @@ std::shared_ptr<DeviceCloud> upload_and_index(ngicp* h, const float* xyz, size_t
 }
 
 void ensure_inv_perm(ngicp* h, DeviceCloud& dc) {
+  refuse_storage_only(dc, "inverse permutation");
   if (dc.has_inv) return;
   dc.inv_perm.ensure(dc.n * sizeof(int));
   hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)((dc.n + 255) / 256)), dim3(256), 0, h->stream, dc.perm.as<int>(), (int)dc.n, dc.inv_perm.as<int>());
@@ -288,7 +289,10 @@ void ensure_inv_perm(ngicp* h, DeviceCloud& dc) {
 
 void ensure_slot_ready(ngicp* h, Slot& s, const char* what) {
   if (!s.present) throw ArgError{NGICP_ERR_STATE, std::string("no ") + what + " cloud set"};
-  if (s.dev) return;
+  if (s.dev) {
+    refuse_storage_only(*s.dev, what);  // (every search starts from a slot; no slot can hold such a cloud today)
+    return;
+  }
   if (!s.host) throw ArgError{NGICP_ERR_STATE, std::string(what) + " cloud has no data"};
   s.dev = upload_and_index(h, s.host, s.n, s.stride);
 }
@@ -311,6 +315,7 @@ void launch_cov(ngicp* h, DeviceCloud& dc, int k, int reg, double* out, size_t l
 // covariances of the points at sorted positions [lo, hi) into `out` ([n][6], sorted order)
 void launch_cov_range(ngicp* h, DeviceCloud& dc, double* out, size_t lo, size_t hi, hipStream_t s) {
   const int k = h->p.k, reg = h->p.regularization;
+  refuse_storage_only(dc, "covariances");
   if (k <= 0) throw ArgError{NGICP_ERR_ARG, "k must be positive"};
   if (k > 32 || (size_t)k > dc.n) throw ArgError{NGICP_ERR_K_TOO_LARGE, "k exceeds the cloud size or the engine limit of 32"};
   if (k <= 10)
@@ -702,6 +707,8 @@ int ngicp_destroy(ngicp_t* h) {
   if (h->sc.ev_b) (void)hipEventDestroy(h->sc.ev_b);
   for (hipEvent_t e : h->ps.ev)
     if (e) (void)hipEventDestroy(e);
+  if (h->ev_kfm_a) (void)hipEventDestroy(h->ev_kfm_a);
+  if (h->ev_kfm_b) (void)hipEventDestroy(h->ev_kfm_b);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -1808,6 +1815,7 @@ int ngicp_keyframe_clear(ngicp_t* h) {
     h->keyframes.clear();
     h->submap_ids.clear();
     h->submap_cloud = nullptr;
+    h->submap_moved = false;
   });
 }
 
@@ -1824,7 +1832,7 @@ int ngicp_submap_set(ngicp_t* h, const int* ids, size_t n_ids, int* changed_out)
     // `if (submap_kf_idx_curr == submap_kf_idx_prev) submap_hasChanged = false` (odom.cc:1308-1310, 827): same keyframes, and the
     // submap built from them is still the target -> nothing to do
     if (h->tgt.present && h->tgt.dev && h->tgt.dev.get() == h->submap_cloud && h->submap_ids.size() == n_ids &&
-        std::equal(h->submap_ids.begin(), h->submap_ids.end(), ids) && h->tgt_covs.n == total)
+        std::equal(h->submap_ids.begin(), h->submap_ids.end(), ids) && h->tgt_covs.n == total && !h->submap_moved)
       return;
     const double t0 = now_ms();
     // concatenation in keyframe order (odom.cc:1318-1325): point g = offset_k + (original index inside keyframe k)
@@ -1863,6 +1871,7 @@ int ngicp_submap_set(ngicp_t* h, const int* ids, size_t n_ids, int* changed_out)
     h->tgt_covs.order = dc;
     h->submap_ids.assign(ids, ids + n_ids);
     h->submap_cloud = dc.get();
+    h->submap_moved = false;
     h->submap_covs = buf;
     drop_voxel_map(h);
     h->hook_valid = 0;
@@ -2340,3 +2349,6 @@ int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms) {
 
 // ---- voxel pose search: a lattice of poses scored by occupied-voxel hits, the best few returned (csrc/ngicp_pose_search.h) ----
 #include "ngicp_pose_search.h"  // (kernels and entries; behind everything else, for the same reason)
+
+// ---- moving keyframes after a loop closure, and reading one back (csrc/ngicp_keyframe_move.h) ----
+#include "ngicp_keyframe_move.h"  // (kernels and entries; behind everything else, for the same reason)

@@ -92,7 +92,16 @@ struct DeviceCloud {
   float bb_min[3] = {0.f, 0.f, 0.f}, bb_max[3] = {0.f, 0.f, 0.f};  // bounding box of the points (a submap's box is the union of its keyframes')
   double build_ms = 0.0;
   int device = 0;
+  // STORAGE ONLY (a keyframe that ngicp_keyframe_transform moved): `sorted` holds the points in the order the keyframe had
+  // before the move (w = original index; the pads unwritten), n and the box are valid, and NOTHING else is - no grid, no permutation, no
+  // batches.  Such a cloud is read by position only (ngicp_submap_set, the voxel part, ngicp_keyframe_get); refuse_storage_only() guards
+  // every place a cloud is about to be searched.  It is made outside the pool below and freed, not recycled, with its keyframe.
+  bool storage_only = false;
 };
+
+void refuse_storage_only(const DeviceCloud& dc, const char* what) {
+  if (dc.storage_only) throw ArgError{NGICP_ERR_STATE, std::string(what) + ": the cloud is a moved keyframe's storage and has no index"};
+}
 
 // Index objects are recycled: a LiDAR pipeline builds a new source index per scan, and hipMalloc / hipFree of its nine
 // buffers (both synchronise the device) cost more than building the index.  The last owner hands the object back to a
@@ -366,6 +375,7 @@ struct ngicp {
   std::vector<Keyframe> keyframes;
   std::vector<int> submap_ids;           // keyframes of the submap that is the current target (valid while submap_cloud is the target)
   const DeviceCloud* submap_cloud = nullptr;
+  bool submap_moved = false;             // ngicp_keyframe_transform moved a keyframe of submap_ids since ngicp_submap_set built the target from them
   std::weak_ptr<DevBuf> submap_covs;     // the covariance set ngicp_submap_set installed with it (weak: a recycled buffer is another object)
 
   // robust kernel (include/ngicp.h "robust kernel"): remembered across mode switches, read when a pass's arguments are filled
@@ -453,6 +463,11 @@ struct ngicp {
     bool stamp_rolling = false;          // ... computed against this map: the rolling one at generation stamp_gen, or build number stamp_gen of the target's
     long long stamp_gen = 0;
   } ps;
+  // moving keyframes (csrc/ngicp_keyframe_move.h): a call's table on the host (it outlives the asynchronous copy) and on the device
+  std::vector<unsigned char> kfm_host;
+  DevBuf kfm_table;
+  hipEvent_t ev_kfm_a = nullptr, ev_kfm_b = nullptr;  // around the kernel (created on first use; its own pair: ngicp_stats is left alone)
+  double kfm_kernel_ms = 0.0;            // ngicp_keyframe_transform_kernel_ms
 };
 
 namespace {

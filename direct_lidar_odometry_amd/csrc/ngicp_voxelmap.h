@@ -237,7 +237,8 @@ VoxelMapView voxel_map_view(const ngicp* h) {
 bool voxel_map_current(const ngicp* h) {
   const ngicp::VoxelMap& m = h->vmap;
   if (!h->tgt.dev || h->tgt_covs.n != h->tgt.dev->n) return false;
-  return m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && m.merged == (merged_route_applies(h) ? 1 : 0);
+  // (after ngicp_keyframe_transform moved a keyframe of the submap, the map of the unchanged target stands whichever route built it)
+  return m.valid && m.res == h->voxel_res && m.cloud == h->tgt.dev && m.covs == h->tgt_covs.data && (m.merged == (merged_route_applies(h) ? 1 : 0) || h->submap_moved);
 }
 
 // The voxel map of the current target, its covariances (computed if missing, as for align) and the resolution: built at the first use
@@ -253,7 +254,7 @@ VoxelMapView ensure_voxel_map(ngicp* h) {
   if (h->tgt_covs.n != h->tgt.dev->n) compute_covs(h, h->tgt, h->tgt_covs, "target");
   const double* covs = covs_for(h, h->tgt_covs, h->tgt.dev);
   ngicp::VoxelMap& m = h->vmap;
-  const int merged = merged_route_applies(h) ? 1 : 0;
+  const int merged = merged_route_applies(h) && !h->submap_moved ? 1 : 0;  // (moved keyframes' parts no longer add up to this target)
   if (voxel_map_current(h)) return voxel_map_view(h);
   m.invalidate();
   if (merged) build_voxel_map_merged(h);

@@ -107,6 +107,7 @@ EXPORTS = [
     "ngicp_scan_context_add", "ngicp_scan_context_add_descriptor", "ngicp_scan_context_count", "ngicp_scan_context_get", "ngicp_scan_context_clear",
     "ngicp_scan_context_distances", "ngicp_scan_context_match", "ngicp_scan_context_kernel_ms",
     "ngicp_voxel_pose_search", "ngicp_voxel_pose_search_scores", "ngicp_voxel_pose_search_kernel_ms",
+    "ngicp_keyframe_get", "ngicp_keyframe_transform", "ngicp_keyframe_transform_kernel_ms",
 ]
 
 
@@ -196,6 +197,9 @@ def load_library() -> C.CDLL:
     L.ngicp_keyframe_count.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.ngicp_keyframe_size.argtypes = [vp, C.c_int, C.POINTER(C.c_size_t)]
     L.ngicp_keyframe_clear.argtypes = [vp]
+    L.ngicp_keyframe_get.argtypes = [vp, C.c_int, c_f32p, C.c_size_t, c_f64p, C.POINTER(C.c_size_t)]
+    L.ngicp_keyframe_transform.argtypes = [vp, c_i32p, C.c_size_t, c_f32p, c_i32p]
+    L.ngicp_keyframe_transform_kernel_ms.argtypes = [vp, c_f64p]
     L.ngicp_submap_set.argtypes = [vp, c_i32p, C.c_size_t, c_i32p]
     L.ngicp_get_target_points.argtypes = [vp, c_f32p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ngicp_transform_source.argtypes = [vp, c_f32p, c_f32p, C.c_size_t]
@@ -1081,6 +1085,35 @@ class NanoGICP:
         return n.value
 
     def clearKeyframes(self): self._ck(self._L.ngicp_keyframe_clear(self._h))
+
+    # ---- moving keyframes after a loop closure (include/ngicp.h "moving keyframes") ----
+    def getKeyframe(self, kid: int):
+        """-> (points (n, 3) float32, covs (n, 4, 4)) of keyframe `kid`, both in its ORIGINAL point order."""
+        n = C.c_size_t(0)
+        self._ck(self._L.ngicp_keyframe_get(self._h, int(kid), None, 0, None, C.byref(n)))
+        pts = np.empty((n.value, 3), dtype=np.float32)
+        c16 = np.empty((n.value, 16), dtype=np.float64)
+        if n.value:
+            self._ck(self._L.ngicp_keyframe_get(self._h, int(kid), _p(pts, c_f32p), 12, _p(c16, c_f64p), C.byref(n)))
+        return pts, c16.reshape(n.value, 4, 4).transpose(0, 2, 1).copy()
+
+    def transformKeyframes(self, ids, Ts) -> bool:
+        """Keyframe ids[j] := Ts[j] applied to it (points by the float matrix as pcl::transformPointCloud, covariances rotated by its 3x3
+        block, nothing recomputed), for all j in one launch on the device; all or nothing.  The current target is left as it is.  True
+        when a moved keyframe belongs to the submap that is the target: the next setSubmapKeyframes rebuilds it, even with the same list."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        t = np.asarray(Ts, dtype=np.float32)
+        if t.ndim != 3 or t.shape[1:] != (4, 4) or t.shape[0] != a.shape[0]:
+            raise ValueError("Ts must have shape (len(ids), 4, 4)")
+        t = np.ascontiguousarray(t.transpose(0, 2, 1)).reshape(-1)  # column-major, one matrix after the other
+        stale = C.c_int(0)
+        self._ck(self._L.ngicp_keyframe_transform(self._h, _p(a, c_i32p), a.shape[0], _p(t, c_f32p), C.byref(stale)))
+        return bool(stale.value)
+
+    def keyframeTransformKernelMs(self) -> float:
+        ms = C.c_double(0.0)
+        self._ck(self._L.ngicp_keyframe_transform_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def setSubmapKeyframes(self, ids) -> bool:
         """target := concatenation of the keyframes `ids` (cloud + covariances), on the device.  True when rebuilt."""

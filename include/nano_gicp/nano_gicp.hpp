@@ -942,6 +942,45 @@ class NanoGICP {
     }
     return changed != 0;
   }
+  // ---- moving keyframes after a loop closure (include/ngicp.h "moving keyframes"; no counterpart in the reference) ----
+  // keyframe ids[j] := Ts[j] applied to it, for all j in one launch on the device: the points by the float matrix as
+  // pcl::transformPointCloud, the covariances rotated by its 3x3 block (nothing is recomputed).  All or nothing: false and a message on
+  // stderr when the call is refused, and then no keyframe has changed.  The current target is left as it is; *submap_stale (optional)
+  // is set when a moved keyframe belongs to the submap that is the target - the next setSubmapKeyframes rebuilds it, even with the same ids.
+  bool transformKeyframes(const std::vector<int>& ids, const std::vector<Matrix4>& Ts, bool* submap_stale = nullptr) {
+    if (submap_stale) *submap_stale = false;
+    if (!h_) return false;
+    if (ids.size() != Ts.size()) {
+      std::fprintf(stderr, "[NanoGICP] transformKeyframes: one transform per id\n");
+      return false;
+    }
+    std::vector<float> flat(Ts.size() * 16);
+    for (size_t j = 0; j < Ts.size(); ++j)
+      for (int e = 0; e < 16; ++e) flat[j * 16 + e] = Ts[j].data()[e];  // (column-major, as Eigen stores it)
+    int stale = 0;
+    if (!check(ngicp_keyframe_transform(h_, ids.data(), ids.size(), flat.data(), &stale), "transformKeyframes")) return false;
+    if (submap_stale) *submap_stale = stale != 0;
+    return true;
+  }
+  // keyframe `id` as the store holds it, in its original point order: the points (x, y, z; data[3] = 1) and the covariances
+  bool getKeyframe(int id, PointCloudSource& cloud, CovVector& covs) {
+    size_t n = 0;
+    if (!h_ || !check(ngicp_keyframe_get(h_, id, nullptr, 0, nullptr, &n), "getKeyframe")) return false;
+    std::vector<float> xyz(n * 3);
+    covs.resize(n);
+    if (n && !check(ngicp_keyframe_get(h_, id, xyz.data(), 12, reinterpret_cast<double*>(covs.data()), &n), "getKeyframe")) return false;
+    cloud.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      PointSource& p = cloud.points[i];
+      p.data[0] = xyz[i * 3 + 0]; p.data[1] = xyz[i * 3 + 1]; p.data[2] = xyz[i * 3 + 2]; p.data[3] = 1.0f;
+    }
+    return true;
+  }
+  double keyframeTransformKernelMs() const {
+    double ms = 0.0;
+    if (h_) ngicp_keyframe_transform_kernel_ms(h_, &ms);
+    return ms;
+  }
   // dlo::OdomNode::preprocessPoints (odom.cc:443-465): removeNaN -> CropBox(negative, +-crop_size) -> VoxelGrid(voxel_res), each
   // optional (crop_size / voxel_res <= 0: off), on the GPU; `cloud` is replaced by the filtered cloud (x, y, z, intensity;
   // data[3] = 1).  With set_as_source the filtered cloud, still on the device, also becomes this instance's input source.

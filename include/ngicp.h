@@ -771,6 +771,42 @@ int ngicp_submap_set(ngicp_t* h, const int* ids, size_t n_ids, int* changed_out_
  * xyz_out may be NULL to query the size only. */
 int ngicp_get_target_points(ngicp_t* h, float* xyz_out_or_null, size_t out_stride_bytes, size_t* n_out_or_null);
 
+/* --- moving keyframes: re-pose keyframes of the store after a loop closure, and read one back (no counterpart in the reference, which
+ *     keeps its keyframes on the host; csrc/ngicp_keyframe_move.h) ------------------------------------------------------
+ * A keyframe is held in the world frame at the pose it was added with.  After a pose-graph correction ngicp_keyframe_transform applies a
+ * rigid correction to any subset of the store, on the device, in one kernel launch; ngicp_keyframe_get hands a keyframe to the host.  The
+ * project's own definition, every operation spelled out (tests/_keyframe_move_model.py restates it; the engine is held to it bit for bit):
+ *   the points        of keyframe ids[j] under the float matrix T_j (column-major):  p' = T_j p  as pcl::transformPointCloud,
+ *                     x*c0 + (y*c1 + (z*c2 + c3)) per row in float32, nothing fused.  A point keeps its original index.
+ *   the covariances   C' = R_j C R_j^T with R_j the float 3x3 block of T_j widened to double, evaluated as the rolling insert evaluates it:
+ *                     RA = R C row by row, each entry (r0 a0 + r1 a1) + r2 a2, then the upper triangle of RA R^T the same way, in FP64.
+ *                     One rotation per point.  The covariances are NOT recomputed from the moved points: under a rigid motion a
+ *                     regularised covariance keeps its eigenvalues, and no neighbour search runs.
+ *   the box           the exact float min / max of the moved points.
+ *   the voxel part    (merged voxel map) is dropped and rebuilt lazily from the moved points and covariances.
+ *   copy on move      a keyframe may share its buffers with a producer's source slot (ngicp_keyframe_add adopts them without a copy): a
+ *                     move always writes fresh buffers and swaps them in at the end.  Nothing another handle or slot sees changes.  PEAK
+ *                     DEVICE MEMORY IS TWICE THE MOVED KEYFRAMES (64 bytes per point more until the call returns).
+ *   no index          nothing searches a keyframe, so a moved keyframe keeps its storage order and gets no index build: its points
+ *                     (16 bytes each) and covariances (48) are all it holds from then on.  Later index builds on the handle behave as if the move had not happened.
+ *   the target        is not touched: it owns its buffers; its points, covariances, voxel map, correspondences, the hooks' state and the
+ *                     last alignment's results stay bit for bit.  If a moved id is in the list the current target was built from, the
+ *                     no-op memo of ngicp_submap_set is forgotten and *submap_stale_out = 1: the next ngicp_submap_set, even with the
+ *                     same list, rebuilds and reports changed = 1.  Otherwise the memo stays and *submap_stale_out = 0.
+ *   all or nothing    NGICP_ERR_ARG, and nothing changes (keyframes, voxel parts, the memo, the target), for: null ids or T, n_ids == 0;
+ *                     an unknown id; an id listed twice (the message names both positions); a matrix entry that is not finite; a last row
+ *                     other than (0, 0, 0, 1); any moved coordinate that is not finite (found on the device, with a flag of its own).
+ *                     Rigidity is not checked, as by no other entry that takes a float pose.
+ * One host synchronisation per call (the boxes and the flag are read back before the swap).  Moving a keyframe twice is two roundings,
+ * not the rounding of the composed matrix.
+ * ngicp_keyframe_get: the keyframe's points in ORIGINAL point order (what ngicp_get_target_points gives for a one-keyframe submap) and its
+ * covariances as ngicp_get_source_covs formats them (n x 16 doubles, column-major 4x4, last row and column zero, original order).
+ * Either array may be NULL.  Unknown id, or (with xyz_out) a stride below 12 or not a multiple of 4: NGICP_ERR_ARG. */
+int ngicp_keyframe_get(ngicp_t* h, int id, float* xyz_out_or_null, size_t out_stride_bytes, double* covs_n16_or_null, size_t* n_out_or_null);
+int ngicp_keyframe_transform(ngicp_t* h, const int* ids, size_t n_ids, const float* T_colmajor_n16, int* submap_stale_out_or_null);
+/* device time (HIP events on the handle's stream) of the kernel of the last ngicp_keyframe_transform that ran one, refused or not */
+int ngicp_keyframe_transform_kernel_ms(const ngicp_t* h, double* ms);
+
 /* --- rigid transform of clouds ------------------------------------ */
 /* pcl::transformPointCloud(in, out, Eigen::Matrix4f) — impl/lsq_registration_impl.hpp:114, src/dlo/odom.cc:484,971-974.
  * ngicp_transform_source: the handle's current source cloud (already on the device) -> host, original point order;
