@@ -709,6 +709,9 @@ int ngicp_destroy(ngicp_t* h) {
     if (e) (void)hipEventDestroy(e);
   if (h->ev_kfm_a) (void)hipEventDestroy(h->ev_kfm_a);
   if (h->ev_kfm_b) (void)hipEventDestroy(h->ev_kfm_b);
+  if (h->pg.ev_a) (void)hipEventDestroy(h->pg.ev_a);
+  if (h->pg.ev_b) (void)hipEventDestroy(h->pg.ev_b);
+  if (h->pg.pin) (void)hipHostFree(h->pg.pin);
   h->vmap.invalidate();
   ngk_filter_free(&h->fws);
   ngk_filter_free(&h->vox_ws);
@@ -2352,3 +2355,5 @@ int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms) {
 
 // ---- moving keyframes after a loop closure, and reading one back (csrc/ngicp_keyframe_move.h) ----
 #include "ngicp_keyframe_move.h"  // (kernels and entries; behind everything else, for the same reason)
+
+#include "ngicp_pose_graph.h"  // (kernels and entries; behind everything else, for the same reason)

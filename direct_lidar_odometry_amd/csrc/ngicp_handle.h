@@ -468,6 +468,25 @@ struct ngicp {
   DevBuf kfm_table;
   hipEvent_t ev_kfm_a = nullptr, ev_kfm_b = nullptr;  // around the kernel (created on first use; its own pair: ngicp_stats is left alone)
   double kfm_kernel_ms = 0.0;            // ngicp_keyframe_transform_kernel_ms
+  // pose graph (csrc/ngicp_pose_graph.h): the graph as given on the host (what the getters return), its device images and the
+  // optimiser's workspace, grow-only.  Independent of the clouds; nothing of an alignment lives here
+  struct PoseGraph {
+    std::vector<double> poses, snapshot;   // [n][16] column-major: the current poses; those at the start of the last optimize
+    std::vector<unsigned char> fixed, eflag;  // [n] fixed flags, [m] robust flags
+    std::vector<int> ij;                   // [m][2]
+    std::vector<double> Z, info;           // [m][16] column-major, [m][36]
+    int robust_kind = NGICP_ROBUST_NONE;
+    double robust_width = 1.0;
+    bool topo_dirty = true, poses_dirty = true;  // the device images of edges / flags / lists, of the poses, are older than the host's
+    int cur = 0;                           // which of d_poses holds the current poses
+    DevBuf d_ij, d_Z, d_info, d_eflag, d_fixed, d_off, d_ent;  // the graph: edges, flags, the incidence lists
+    DevBuf d_lin[2], d_poses[2];           // [m][36] linearised edges of the current / the trial poses; [n][12] poses likewise
+    DevBuf d_diag, d_grad, d_minv, d_x, d_r, d_z, d_p, d_q;  // [n][36] / [n][6] per-node arrays of the normal equations and of CG
+    DevBuf d_part, d_sc, d_corr;           // block results; the PgScalars record; a corrections call's poses and result
+    unsigned char* pin = nullptr;          // pinned: the CG's done word (first 4 bytes), the scalars' read-back image (from byte 64)
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;  // around an optimize (created on first use; its own pair: ngicp_stats is left alone)
+    double kernel_ms = 0.0;                // ngicp_pose_graph_kernel_ms
+  } pg;
 };
 
 namespace {

@@ -108,7 +108,27 @@ EXPORTS = [
     "ngicp_scan_context_distances", "ngicp_scan_context_match", "ngicp_scan_context_kernel_ms",
     "ngicp_voxel_pose_search", "ngicp_voxel_pose_search_scores", "ngicp_voxel_pose_search_kernel_ms",
     "ngicp_keyframe_get", "ngicp_keyframe_transform", "ngicp_keyframe_transform_kernel_ms",
+    "ngicp_pose_graph_clear", "ngicp_pose_graph_size", "ngicp_pose_graph_add_nodes", "ngicp_pose_graph_add_edges", "ngicp_pose_graph_get_edges",
+    "ngicp_pose_graph_set_fixed", "ngicp_pose_graph_get_fixed", "ngicp_pose_graph_set_robust", "ngicp_pose_graph_get_poses", "ngicp_pose_graph_set_poses",
+    "ngicp_pose_graph_linearize", "ngicp_pose_graph_multiply", "ngicp_pose_graph_optimize", "ngicp_pose_graph_corrections", "ngicp_pose_graph_kernel_ms",
 ]
+
+
+PG_TRACE_CAP = 256  # NGICP_PG_TRACE_CAP
+
+
+class PgOptions(C.Structure):
+    """ngicp_pg_options (include/ngicp.h, "pose graph")."""
+    _fields_ = [("max_iterations", C.c_int), ("rot_eps", C.c_double), ("trans_eps", C.c_double), ("cg_tol", C.c_double), ("cg_max_iterations", C.c_int)]
+
+
+class PgResult(C.Structure):
+    """ngicp_pg_result."""
+    _fields_ = [("initial_chi2", C.c_double), ("final_chi2", C.c_double), ("iterations", C.c_int), ("accepted", C.c_int), ("cg_iterations", C.c_longlong),
+                ("converged", C.c_int), ("n_trace", C.c_int), ("trace", C.c_double * (PG_TRACE_CAP * 5))]
+
+
+PG_DEFAULTS = dict(max_iterations=64, rot_eps=2e-3, trans_eps=5e-4, cg_tol=1e-8, cg_max_iterations=1000)
 
 
 class VoxelFitness(C.Structure):
@@ -265,6 +285,22 @@ def load_library() -> C.CDLL:
     L.ngicp_voxel_pose_search.argtypes = [vp, C.c_size_t, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_szp]
     L.ngicp_voxel_pose_search_scores.argtypes = [vp, c_i32p, C.c_size_t]
     L.ngicp_voxel_pose_search_kernel_ms.argtypes = [vp, c_f64p]
+    c_u8p = C.POINTER(C.c_ubyte)
+    L.ngicp_pose_graph_clear.argtypes = [vp]
+    L.ngicp_pose_graph_size.argtypes = [vp, c_szp, c_szp]
+    L.ngicp_pose_graph_add_nodes.argtypes = [vp, c_f64p, c_u8p, C.c_size_t, c_i32p]
+    L.ngicp_pose_graph_add_edges.argtypes = [vp, c_i32p, c_f64p, c_f64p, c_u8p, C.c_size_t, c_i32p]
+    L.ngicp_pose_graph_get_edges.argtypes = [vp, C.c_int, C.c_size_t, c_i32p, c_f64p, c_f64p, c_u8p]
+    L.ngicp_pose_graph_set_fixed.argtypes = [vp, c_i32p, c_u8p, C.c_size_t]
+    L.ngicp_pose_graph_get_fixed.argtypes = [vp, C.c_int, C.c_size_t, c_u8p]
+    L.ngicp_pose_graph_set_robust.argtypes = [vp, C.c_int, C.c_double]
+    L.ngicp_pose_graph_get_poses.argtypes = [vp, C.c_int, C.c_size_t, c_f64p]
+    L.ngicp_pose_graph_set_poses.argtypes = [vp, C.c_int, C.c_size_t, c_f64p]
+    L.ngicp_pose_graph_linearize.argtypes = [vp, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]
+    L.ngicp_pose_graph_multiply.argtypes = [vp, C.c_double, c_f64p, c_f64p]
+    L.ngicp_pose_graph_optimize.argtypes = [vp, C.POINTER(PgOptions), C.POINTER(PgResult)]
+    L.ngicp_pose_graph_corrections.argtypes = [vp, c_i32p, C.c_size_t, c_f64p, c_f32p]
+    L.ngicp_pose_graph_kernel_ms.argtypes = [vp, c_f64p]
     _lib = L
     return L
 
@@ -1114,6 +1150,155 @@ class NanoGICP:
         ms = C.c_double(0.0)
         self._ck(self._L.ngicp_keyframe_transform_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    # ---- pose graph (include/ngicp.h "pose graph") ----
+    @staticmethod
+    def _poses16(T) -> np.ndarray:
+        """(n, 4, 4) or (4, 4) row-major as numpy holds them -> n x 16 column-major doubles"""
+        t = np.asarray(T, dtype=np.float64)
+        if t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3 or t.shape[1:] != (4, 4):
+            raise ValueError("poses must have shape (n, 4, 4)")
+        return np.ascontiguousarray(t.transpose(0, 2, 1)).reshape(-1)
+
+    def poseGraphClear(self): self._ck(self._L.ngicp_pose_graph_clear(self._h))
+
+    def poseGraphSize(self):
+        """-> (nodes, edges)"""
+        n, m = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.ngicp_pose_graph_size(self._h, C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    def poseGraphAddNodes(self, T, fixed=None) -> int:
+        """Append nodes at the world poses T (n, 4, 4); fixed: a flag per node (default: none).  -> the first new id.  All or nothing."""
+        t = self._poses16(T)
+        n = t.shape[0] // 16
+        f = None if fixed is None else np.ascontiguousarray(np.broadcast_to(np.asarray(fixed, dtype=bool), (n,)), dtype=np.uint8)
+        first = C.c_int(-1)
+        self._ck(self._L.ngicp_pose_graph_add_nodes(self._h, _p(t, c_f64p), None if f is None else _p(f, C.POINTER(C.c_ubyte)), n, C.byref(first)))
+        return first.value
+
+    def poseGraphAddEdges(self, ij, Z, info, robust=None) -> int:
+        """Append edges (i, j) with measurements Z (n, 4, 4) = T_i^-1 T_j and information matrices (n, 6, 6), exactly symmetric, rotation
+        first; robust: a flag per edge (default: none).  -> the first new edge id.  All or nothing."""
+        a = np.ascontiguousarray(ij, dtype=np.int32).reshape(-1, 2)
+        z = self._poses16(Z)
+        L = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 36)
+        n = a.shape[0]
+        if z.shape[0] != 16 * n or L.shape[0] != n:
+            raise ValueError("one Z and one information matrix per edge")
+        f = None if robust is None else np.ascontiguousarray(np.broadcast_to(np.asarray(robust, dtype=bool), (n,)), dtype=np.uint8)
+        first = C.c_int(-1)
+        self._ck(self._L.ngicp_pose_graph_add_edges(self._h, _p(a, c_i32p), _p(z, c_f64p), _p(L, c_f64p), None if f is None else _p(f, C.POINTER(C.c_ubyte)), n,
+                                                    C.byref(first)))
+        return first.value
+
+    def poseGraphEdges(self):
+        """-> (ij (m, 2), Z (m, 4, 4), info (m, 6, 6), robust flags (m,)) as the graph holds them"""
+        _, m = self.poseGraphSize()
+        ij, z, L, f = np.zeros((m, 2), np.int32), np.zeros((m, 16)), np.zeros((m, 6, 6)), np.zeros(m, np.uint8)
+        if m:
+            self._ck(self._L.ngicp_pose_graph_get_edges(self._h, 0, m, _p(ij, c_i32p), _p(z, c_f64p), _p(L, c_f64p), _p(f, C.POINTER(C.c_ubyte))))
+        return ij, z.reshape(m, 4, 4).transpose(0, 2, 1).copy(), L, f.astype(bool)
+
+    def poseGraphSetFixed(self, ids, flags):
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(flags, dtype=bool), a.shape), dtype=np.uint8)
+        self._ck(self._L.ngicp_pose_graph_set_fixed(self._h, _p(a, c_i32p), _p(f, C.POINTER(C.c_ubyte)), a.shape[0]))
+
+    def poseGraphFixed(self) -> np.ndarray:
+        n, _ = self.poseGraphSize()
+        f = np.zeros(n, np.uint8)
+        if n:
+            self._ck(self._L.ngicp_pose_graph_get_fixed(self._h, 0, n, _p(f, C.POINTER(C.c_ubyte))))
+        return f.astype(bool)
+
+    def poseGraphSetRobust(self, kind: int, width: float = 1.0):
+        """The kernel of the FLAGGED edges: ROBUST_NONE / HUBER / CAUCHY / GEMAN_MCCLURE with a width (in the residual's whitened units)."""
+        self._ck(self._L.ngicp_pose_graph_set_robust(self._h, int(kind), float(width)))
+
+    def poseGraphPoses(self, first: int = 0, n: int = None) -> np.ndarray:
+        """-> (n, 4, 4) float64 poses of the nodes first .. first + n (default: all)"""
+        if n is None:
+            n = self.poseGraphSize()[0] - first
+        out = np.zeros((n, 16))
+        if n:
+            self._ck(self._L.ngicp_pose_graph_get_poses(self._h, int(first), n, _p(out, c_f64p)))
+        return out.reshape(n, 4, 4).transpose(0, 2, 1).copy()
+
+    def poseGraphSetPoses(self, first: int, T):
+        t = self._poses16(T)
+        self._ck(self._L.ngicp_pose_graph_set_poses(self._h, int(first), t.shape[0] // 16, _p(t, c_f64p)))
+
+    def poseGraphLinearize(self) -> dict:
+        """Test hook: the linearisation at the current poses, which stay.  -> dict(chi2, r (m, 6), s (m,), w (m,), grad (n, 6), diag (n, 6, 6));
+        gradient and diagonal blocks of fixed nodes are zero."""
+        n, m = self.poseGraphSize()
+        chi2 = C.c_double(0.0)
+        r, sw, grad, diag = np.zeros((m, 6)), np.zeros((m, 2)), np.zeros((n, 6)), np.zeros((n, 6, 6))
+        self._ck(self._L.ngicp_pose_graph_linearize(self._h, C.byref(chi2), _p(r, c_f64p), _p(sw, c_f64p), _p(grad, c_f64p), _p(diag, c_f64p)))
+        return dict(chi2=chi2.value, r=r, s=sw[:, 0].copy(), w=sw[:, 1].copy(), grad=grad, diag=diag)
+
+    def poseGraphMultiply(self, lam: float, x) -> np.ndarray:
+        """Test hook: (H + lam I) x at the current poses' linearisation, (n, 6); rows of fixed nodes are zero."""
+        n, _ = self.poseGraphSize()
+        xa = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if xa.shape[0] != 6 * n:
+            raise ValueError("x must have 6 entries per node")
+        y = np.zeros((n, 6))
+        self._ck(self._L.ngicp_pose_graph_multiply(self._h, float(lam), _p(xa, c_f64p), _p(y, c_f64p)))
+        return y
+
+    def poseGraphOptimize(self, **options) -> dict:
+        """Levenberg-Marquardt on the whole graph, on the device.  Options: max_iterations, rot_eps, trans_eps, cg_tol, cg_max_iterations
+        (PG_DEFAULTS).  -> dict(initial_chi2, final_chi2, iterations, accepted, cg_iterations, converged, trace (tries, 5): chi2 of the
+        try, lambda, gain ratio, CG iterations, accepted)."""
+        unknown = set(options) - set(PG_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown options {sorted(unknown)}")
+        o = dict(PG_DEFAULTS)
+        o.update(options)
+        opt = PgOptions(int(o["max_iterations"]), float(o["rot_eps"]), float(o["trans_eps"]), float(o["cg_tol"]), int(o["cg_max_iterations"]))
+        res = PgResult()
+        self._ck(self._L.ngicp_pose_graph_optimize(self._h, C.byref(opt), C.byref(res)))
+        trace = np.array(res.trace[:res.n_trace * 5], dtype=np.float64).reshape(res.n_trace, 5)
+        return dict(initial_chi2=res.initial_chi2, final_chi2=res.final_chi2, iterations=res.iterations, accepted=res.accepted,
+                    cg_iterations=int(res.cg_iterations), converged=bool(res.converged), trace=trace)
+
+    def poseGraphCorrections(self, ids, T_old=None) -> np.ndarray:
+        """-> (len(ids), 4, 4) float32: C_k = T_k * T_k_old^-1, what transformKeyframes / transformVoxelMap take.  T_old: (len(ids), 4, 4),
+        or None for the poses the last poseGraphOptimize started from."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        old = None if T_old is None else self._poses16(T_old)
+        if old is not None and old.shape[0] != 16 * a.shape[0]:
+            raise ValueError("one T_old per id")
+        out = np.zeros((a.shape[0], 16), np.float32)
+        self._ck(self._L.ngicp_pose_graph_corrections(self._h, _p(a, c_i32p), a.shape[0], None if old is None else _p(old, c_f64p), _p(out, c_f32p)))
+        return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+
+    def poseGraphKernelMs(self) -> float:
+        ms = C.c_double(0.0)
+        self._ck(self._L.ngicp_pose_graph_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def edgeFromAlignment(T_i, T_aligned, H):
+        """The edge an alignment yields: scan j aligned against keyframe i, which is held in the world frame at T_i, ended at the world pose
+        T_aligned with getFinalHessian() = H (in the aligner's left perturbation of the world pose).  -> (Z, Lambda): Z = T_i^-1 T_aligned and
+        Lambda = J^-T H J^-1, H in the edge's residual coordinates (r = J d at the measurement, J = [[A, 0], [-A [t]x, A]] with A = R_aligned^T,
+        t = t_aligned), symmetrised exactly."""
+        Ti, Ta, Hm = np.asarray(T_i, np.float64), np.asarray(T_aligned, np.float64), np.asarray(H, np.float64)
+        Ri, ti = Ti[:3, :3], Ti[:3, 3]
+        Z = np.eye(4)
+        Z[:3, :3] = Ri.T @ Ta[:3, :3]
+        Z[:3, 3] = Ri.T @ (Ta[:3, 3] - ti)
+        At, t = Ta[:3, :3], Ta[:3, 3]
+        S = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+        Jinv = np.zeros((6, 6))
+        Jinv[:3, :3], Jinv[3:, :3], Jinv[3:, 3:] = At, S @ At, At
+        Lam = Jinv.T @ Hm @ Jinv
+        return Z, 0.5 * (Lam + Lam.T)
 
     def setSubmapKeyframes(self, ids) -> bool:
         """target := concatenation of the keyframes `ids` (cloud + covariances), on the device.  True when rebuilt."""

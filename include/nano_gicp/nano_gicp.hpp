@@ -981,6 +981,158 @@ class NanoGICP {
     if (h_) ngicp_keyframe_transform_kernel_ms(h_, &ms);
     return ms;
   }
+  // ---- pose graph (include/ngicp.h "pose graph"; no counterpart in the reference) ----
+  // Loop-closure edges in, corrected keyframe poses out, on the device: nodes are world poses (double, column-major 4x4), edges carry the
+  // measured T_i^-1 T_j and a symmetric 6x6 information matrix (rotation first).  The graph lives on this instance, survives alignments
+  // and touches nothing of them.  Every call is all or nothing: false (or -1) and a line on stderr when it is refused.
+  // The array forms come first; the matrix forms below them take types::Matrix4d / Matrix6d (Eigen's, or the stand-ins without Eigen).
+  void poseGraphClear() {
+    if (h_) check(ngicp_pose_graph_clear(h_), "poseGraphClear");
+  }
+  void poseGraphSize(size_t* nodes, size_t* edges) const {
+    if (nodes) *nodes = 0;
+    if (edges) *edges = 0;
+    if (h_) ngicp_pose_graph_size(h_, nodes, edges);
+  }
+  // -> the first new id, or -1
+  int poseGraphAddNodes(const double* T_colmajor_n16, const unsigned char* fixed_or_null, size_t n) {
+    int first = -1;
+    if (!h_ || !check(ngicp_pose_graph_add_nodes(h_, T_colmajor_n16, fixed_or_null, n, &first), "poseGraphAddNodes")) return -1;
+    return first;
+  }
+  // info: n x 36, each exactly symmetric.  -> the first new edge id, or -1
+  int poseGraphAddEdges(const int* ij_n2, const double* Z_colmajor_n16, const double* info_n36, const unsigned char* robust_or_null, size_t n) {
+    int first = -1;
+    if (!h_ || !check(ngicp_pose_graph_add_edges(h_, ij_n2, Z_colmajor_n16, info_n36, robust_or_null, n, &first), "poseGraphAddEdges")) return -1;
+    return first;
+  }
+  bool poseGraphGetEdges(int first, size_t n, int* ij_n2, double* Z_colmajor_n16, double* info_n36, unsigned char* robust) {
+    return h_ && check(ngicp_pose_graph_get_edges(h_, first, n, ij_n2, Z_colmajor_n16, info_n36, robust), "poseGraphGetEdges");
+  }
+  bool poseGraphSetFixed(const std::vector<int>& ids, const std::vector<unsigned char>& flags) {
+    if (!h_ || ids.size() != flags.size()) return false;
+    return check(ngicp_pose_graph_set_fixed(h_, ids.data(), flags.data(), ids.size()), "poseGraphSetFixed");
+  }
+  bool poseGraphGetFixed(int first, size_t n, unsigned char* flags) { return h_ && check(ngicp_pose_graph_get_fixed(h_, first, n, flags), "poseGraphGetFixed"); }
+  // the kernel of the FLAGGED edges: NGICP_ROBUST_NONE / _HUBER / _CAUCHY / _GEMAN_MCCLURE and its width (whitened residual units)
+  bool poseGraphSetRobust(int kind, double width) { return h_ && check(ngicp_pose_graph_set_robust(h_, kind, width), "poseGraphSetRobust"); }
+  bool poseGraphGetPoses(int first, size_t n, double* T_colmajor_n16) { return h_ && check(ngicp_pose_graph_get_poses(h_, first, n, T_colmajor_n16), "poseGraphGetPoses"); }
+  bool poseGraphSetPoses(int first, size_t n, const double* T_colmajor_n16) {
+    return h_ && check(ngicp_pose_graph_set_poses(h_, first, n, T_colmajor_n16), "poseGraphSetPoses");
+  }
+  // test hooks: the linearisation at the current poses (any output may be null), and y = (H + lambda I) x
+  bool poseGraphLinearize(double* chi2, double* edge_r_m6, double* edge_s_w_m2, double* grad_n6, double* diag_n36) {
+    return h_ && check(ngicp_pose_graph_linearize(h_, chi2, edge_r_m6, edge_s_w_m2, grad_n6, diag_n36), "poseGraphLinearize");
+  }
+  bool poseGraphMultiply(double lambda, const double* x_n6, double* y_n6) { return h_ && check(ngicp_pose_graph_multiply(h_, lambda, x_n6, y_n6), "poseGraphMultiply"); }
+  // Levenberg-Marquardt on the whole graph (options null: the defaults); refused while a connected component holds no fixed node
+  bool poseGraphOptimize(const ngicp_pg_options* options, ngicp_pg_result* result) {
+    return h_ && check(ngicp_pose_graph_optimize(h_, options, result), "poseGraphOptimize");
+  }
+  // C_k = T_k * T_k_old^-1 as float column-major 4x4s, what transformKeyframes / transformVoxelMap take; T_old null: the poses the last
+  // poseGraphOptimize started from
+  bool poseGraphCorrections(const int* ids, size_t n, const double* T_old_colmajor_n16_or_null, float* C_colmajor_n16) {
+    return h_ && check(ngicp_pose_graph_corrections(h_, ids, n, T_old_colmajor_n16_or_null, C_colmajor_n16), "poseGraphCorrections");
+  }
+  double poseGraphKernelMs() const {
+    double ms = 0.0;
+    if (h_) ngicp_pose_graph_kernel_ms(h_, &ms);
+    return ms;
+  }
+  // the matrix forms
+  struct PoseGraphEdge {
+    int i, j;
+    types::Matrix4d Z;       // the measured T_i^-1 T_j
+    types::Matrix6d info;    // exactly symmetric
+    bool robust;
+  };
+  int poseGraphAddNodes(const std::vector<types::Matrix4d>& T, const std::vector<unsigned char>& fixed = std::vector<unsigned char>()) {
+    if (!fixed.empty() && fixed.size() != T.size()) return -1;
+    std::vector<double> flat(T.size() * 16);
+    for (size_t k = 0; k < T.size(); ++k)
+      for (int e = 0; e < 16; ++e) flat[k * 16 + e] = T[k].data()[e];
+    return poseGraphAddNodes(flat.data(), fixed.empty() ? nullptr : fixed.data(), T.size());
+  }
+  int poseGraphAddEdges(const std::vector<PoseGraphEdge>& edges) {
+    const size_t n = edges.size();
+    std::vector<int> ij(n * 2);
+    std::vector<double> Z(n * 16), L(n * 36);
+    std::vector<unsigned char> f(n);
+    for (size_t e = 0; e < n; ++e) {
+      ij[2 * e] = edges[e].i, ij[2 * e + 1] = edges[e].j;
+      for (int q = 0; q < 16; ++q) Z[e * 16 + q] = edges[e].Z.data()[q];
+      for (int a = 0; a < 6; ++a)
+        for (int b = 0; b < 6; ++b) L[e * 36 + a * 6 + b] = edges[e].info(a, b);
+      f[e] = edges[e].robust ? 1 : 0;
+    }
+    return poseGraphAddEdges(ij.data(), Z.data(), L.data(), f.data(), n);
+  }
+  bool poseGraphPoses(std::vector<types::Matrix4d>& out) {
+    size_t n = 0;
+    poseGraphSize(&n, nullptr);
+    out.assign(n, types::Matrix4d::Identity());
+    if (n == 0) return h_ != nullptr;
+    std::vector<double> flat(n * 16);
+    if (!poseGraphGetPoses(0, n, flat.data())) return false;
+    for (size_t k = 0; k < n; ++k)
+      for (int e = 0; e < 16; ++e) out[k].data()[e] = flat[k * 16 + e];
+    return true;
+  }
+  bool poseGraphCorrections(const std::vector<int>& ids, std::vector<Matrix4>& Cs, const std::vector<types::Matrix4d>* T_old = nullptr) {
+    if (T_old && T_old->size() != ids.size()) return false;
+    std::vector<double> old(T_old ? ids.size() * 16 : 0);
+    for (size_t k = 0; T_old && k < ids.size(); ++k)
+      for (int e = 0; e < 16; ++e) old[k * 16 + e] = (*T_old)[k].data()[e];
+    std::vector<float> flat(ids.size() * 16);
+    if (!poseGraphCorrections(ids.data(), ids.size(), T_old ? old.data() : nullptr, flat.data())) return false;
+    Cs.assign(ids.size(), Matrix4::Identity());
+    for (size_t k = 0; k < ids.size(); ++k)
+      for (int e = 0; e < 16; ++e) Cs[k].data()[e] = flat[k * 16 + e];
+    return true;
+  }
+  // The edge an alignment yields.  Scan j was aligned against keyframe i, which is held in the world frame at T_i; the alignment ended at the
+  // world pose T_aligned with getFinalHessian() = H, the information in the aligner's left perturbation of the world pose.  Z = T_i^-1
+  // T_aligned, and Lambda = J^-T H J^-1 expresses H in the edge's residual coordinates: at the measurement r = J d with
+  // J = [[A, 0], [-A [t]x, A]], A = R_aligned^T, t = t_aligned, so J^-1 = [[A^T, 0], [[t]x A^T, A^T]].  Lambda is
+  // symmetrised exactly, as poseGraphAddEdges demands.
+  static void edgeFromAlignment(const types::Matrix4d& T_i, const types::Matrix4d& T_aligned, const types::Matrix6d& H, types::Matrix4d& Z, types::Matrix6d& Lambda) {
+    Z = types::Matrix4d::Identity();
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) {
+        double s = 0.0;
+        for (int k = 0; k < 3; ++k) s += T_i(k, r) * T_aligned(k, c);
+        Z(r, c) = s;
+      }
+      double s = 0.0;
+      for (int k = 0; k < 3; ++k) s += T_i(k, r) * (T_aligned(k, 3) - T_i(k, 3));
+      Z(r, 3) = s;
+    }
+    const double t[3] = {T_aligned(0, 3), T_aligned(1, 3), T_aligned(2, 3)};
+    const double S[3][3] = {{0.0, -t[2], t[1]}, {t[2], 0.0, -t[0]}, {-t[1], t[0], 0.0}};
+    double Ji[6][6] = {};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        Ji[r][c] = Ji[3 + r][3 + c] = T_aligned(r, c);
+        double s = 0.0;
+        for (int k = 0; k < 3; ++k) s += S[r][k] * T_aligned(k, c);
+        Ji[3 + r][c] = s;
+      }
+    double HJ[6][6], L[6][6];
+    for (int a = 0; a < 6; ++a)
+      for (int b = 0; b < 6; ++b) {
+        double s = 0.0;
+        for (int k = 0; k < 6; ++k) s += H(a, k) * Ji[k][b];
+        HJ[a][b] = s;
+      }
+    for (int a = 0; a < 6; ++a)
+      for (int b = 0; b < 6; ++b) {
+        double s = 0.0;
+        for (int k = 0; k < 6; ++k) s += Ji[k][a] * HJ[k][b];
+        L[a][b] = s;
+      }
+    for (int a = 0; a < 6; ++a)
+      for (int b = 0; b < 6; ++b) Lambda(a, b) = 0.5 * (L[a][b] + L[b][a]);
+  }
   // dlo::OdomNode::preprocessPoints (odom.cc:443-465): removeNaN -> CropBox(negative, +-crop_size) -> VoxelGrid(voxel_res), each
   // optional (crop_size / voxel_res <= 0: off), on the GPU; `cloud` is replaced by the filtered cloud (x, y, z, intensity;
   // data[3] = 1).  With set_as_source the filtered cloud, still on the device, also becomes this instance's input source.

@@ -807,6 +807,83 @@ int ngicp_keyframe_transform(ngicp_t* h, const int* ids, size_t n_ids, const flo
 /* device time (HIP events on the handle's stream) of the kernel of the last ngicp_keyframe_transform that ran one, refused or not */
 int ngicp_keyframe_transform_kernel_ms(const ngicp_t* h, double* ms);
 
+/* --- pose graph: turn loop-closure edges into corrected keyframe poses, on the device (no counterpart in the reference;
+ *     csrc/ngicp_pose_graph.h, csrc/ngicp_pose_graph_plan.h) -----------------------------------------------------------
+ * The step between "scan j is keyframe i, at this relative pose, with this information" (ngicp_scan_context_match, ngicp_voxel_pose_search,
+ * ngicp_voxel_align_batch, the final Hessian) and ngicp_keyframe_transform / ngicp_voxel_rolling_transform.  The graph lives on the
+ * handle, survives alignments and is independent of the clouds.  The project's own definition, restated by tests/_pose_graph_model.py:
+ *   nodes         world poses T_k = (R_k, t_k) in FP64, column-major 4x4 with last row (0, 0, 0, 1).  Ids are dense, in order of insertion
+ *                 (as the scan-context database's).  Each node has a `fixed` flag.
+ *   edges         (i, j, Z, Lambda, robust flag): Z the measured T_i^-1 T_j (column-major 4x4), Lambda a symmetric 6x6 information matrix
+ *                 (row-major; rotation first, then translation - the project's twist order).  Ids dense, in order of insertion.
+ *   residual      E = Z^-1 T_i^-1 T_j,  r = (so3_log(R_E), t_E).  so3_log (csrc/ngicp_math.h) is valid to 3 rad: a residual rotation
+ *                 beyond that gives a finite but unspecified result - start an optimisation closer than that.
+ *   perturbation  the project's own: T_k <- (so3_exp(d[0:3]), d[3:6]) * T_k.  With A = Z^-1 T_i^-1 the exact Jacobians are
+ *                 J_j = [[Jl^-1(phi) R_A, 0], [-R_A [t_j]x, R_A]] and J_i = -J_j (DESIGN.md 4.22 derives them).
+ *   cost          chi2 = sum_e rho(s_e), s_e = r_e^T Lambda_e r_e.  rho is the identity unless the edge's robust flag is set AND a kernel is
+ *                 chosen for the graph (ngicp_pose_graph_set_robust: NGICP_ROBUST_*, width c; the functions of "robust kernel" above).  The
+ *                 weight w(s_e) then scales Lambda_e in the normal equations (iteratively re-weighted least squares, as the passes do).
+ *                 Flag loop edges and leave odometry edges unflagged, and one false loop edge cannot fold the map.
+ *   gauge         columns of fixed nodes are dropped.  ngicp_pose_graph_optimize refuses (NGICP_ERR_ARG, nothing changed) while any connected
+ *                 component of the graph holds no fixed node (a node without edges is a component of its own).
+ *   refused       at add time, all or nothing per call, NGICP_ERR_ARG: n == 0 or a null array; a self-edge; an unknown node id; an entry that
+ *                 is not finite; a last row other than (0, 0, 0, 1); an asymmetric Lambda - mirrored entries must be EXACTLY equal; more
+ *                 than 2^20 nodes or 2^22 edges in the graph.  Several edges between one pair, and an edge given as (j, i) with j > i, are legal.
+ *   optimise      Levenberg-Marquardt on the whole graph with the aligner's schedule (csrc/ngicp_lm.h): H + lambda I; the first lambda is
+ *                 1e-9 times the largest diagonal entry of H; a rejected try multiplies lambda by nu (2, doubling); an accepted one by
+ *                 max(1/3, 1 - (2 rho - 1)^3); a try is accepted unless its gain ratio rho is negative; ten tries per outer iteration.
+ *                 It stops after max_iterations outer iterations, or when a try's largest per-node |so3_exp(d_w) - I| entry is below rot_eps
+ *                 and its largest |d_t| entry below trans_eps (is_converged's two thresholds), or when ten tries in a row were rejected.
+ *                 An accepted step changes the poses; a call that runs out of tries leaves the last accepted poses.
+ *   linear solve  (H + lambda I) delta = -b by conjugate gradients from delta = 0, preconditioned by the inverses of the damped 6x6
+ *                 diagonal blocks (ldlt6_solve), stopped when |res| <= cg_tol |b| or after cg_max_iterations; decided on the device.
+ *   determinism   every sum has a written order (per node: its incident edges in ascending edge id; dot products: a fixed tree); no
+ *                 floating-point atomics.  Two runs on the same input are bit-equal.
+ * ngicp_pose_graph_linearize (test hook; the poses stay): chi2; per edge r (m x 6) and (s, w) (m x 2); per node the gradient (n x 6) and the
+ * diagonal block of H (n x 36, row-major) - both ZERO for fixed nodes.  ngicp_pose_graph_multiply (test hook): y = (H + lambda I) x at the
+ * current poses' linearisation; rows of fixed nodes are zero and their x is not read.
+ * ngicp_pose_graph_corrections: for the listed nodes C_k = T_k * T_k_old^-1 in FP64 - T_old^-1 = (R^T, -(R^T t)), every sum
+ * (a0 b0 + a1 b1) + a2 b2, then the product the same way - rounded to the float column-major 4x4 ngicp_keyframe_transform and
+ * ngicp_voxel_rolling_transform take.  T_old: the caller's array (one per listed id), or NULL for the poses the last
+ * ngicp_pose_graph_optimize started from (NGICP_ERR_ARG for a node added since, or when none has run).
+ * A refused call changes nothing.  No entry here touches the source, the target, the keyframes, the voxel maps, the hooks' state or the
+ * last alignment's results. */
+#define NGICP_PG_TRACE_CAP 256
+typedef struct ngicp_pg_options {
+  int max_iterations;      /* outer iterations (64) */
+  double rot_eps;          /* 2e-3 */
+  double trans_eps;        /* 5e-4 */
+  double cg_tol;           /* 1e-8 */
+  int cg_max_iterations;   /* 1000 */
+} ngicp_pg_options;        /* NULL: the defaults in brackets */
+typedef struct ngicp_pg_result {
+  double initial_chi2, final_chi2;
+  int iterations;          /* outer iterations begun */
+  int accepted;            /* accepted steps */
+  long long cg_iterations; /* over all tries */
+  int converged;           /* the step-size test was met */
+  int n_trace;             /* rows of trace, at most NGICP_PG_TRACE_CAP (later tries are not recorded) */
+  double trace[NGICP_PG_TRACE_CAP * 5]; /* per try: chi2 of the trial poses, lambda, gain ratio rho, CG iterations, accepted (1 / 0) */
+} ngicp_pg_result;
+int ngicp_pose_graph_clear(ngicp_t* h);
+int ngicp_pose_graph_size(const ngicp_t* h, size_t* nodes_or_null, size_t* edges_or_null);
+int ngicp_pose_graph_add_nodes(ngicp_t* h, const double* T_colmajor_n16, const unsigned char* fixed_or_null, size_t n, int* first_id_out_or_null);
+int ngicp_pose_graph_add_edges(ngicp_t* h, const int* ij_n2, const double* Z_colmajor_n16, const double* info_n36, const unsigned char* robust_flags_or_null, size_t n,
+                               int* first_edge_out_or_null);
+int ngicp_pose_graph_get_edges(ngicp_t* h, int first, size_t n, int* ij_n2_or_null, double* Z_colmajor_n16_or_null, double* info_n36_or_null,
+                               unsigned char* robust_flags_or_null);
+int ngicp_pose_graph_set_fixed(ngicp_t* h, const int* ids, const unsigned char* flags, size_t n);
+int ngicp_pose_graph_get_fixed(ngicp_t* h, int first, size_t n, unsigned char* flags_out);
+int ngicp_pose_graph_set_robust(ngicp_t* h, int kind, double width);
+int ngicp_pose_graph_get_poses(ngicp_t* h, int first, size_t n, double* T_colmajor_n16);
+int ngicp_pose_graph_set_poses(ngicp_t* h, int first, size_t n, const double* T_colmajor_n16);
+int ngicp_pose_graph_linearize(ngicp_t* h, double* chi2_out_or_null, double* edge_r_m6_or_null, double* edge_s_w_m2_or_null, double* grad_n6_or_null, double* diag_n36_or_null);
+int ngicp_pose_graph_multiply(ngicp_t* h, double lambda, const double* x_n6, double* y_n6);
+int ngicp_pose_graph_optimize(ngicp_t* h, const ngicp_pg_options* options_or_null, ngicp_pg_result* result);
+int ngicp_pose_graph_corrections(ngicp_t* h, const int* ids, size_t n, const double* T_old_colmajor_n16_or_null, float* C_colmajor_n16);
+/* device time (HIP events on the handle's stream) of the last ngicp_pose_graph_optimize, its read-backs included */
+int ngicp_pose_graph_kernel_ms(const ngicp_t* h, double* ms);
+
 /* --- rigid transform of clouds ------------------------------------ */
 /* pcl::transformPointCloud(in, out, Eigen::Matrix4f) — impl/lsq_registration_impl.hpp:114, src/dlo/odom.cc:484,971-974.
  * ngicp_transform_source: the handle's current source cloud (already on the device) -> host, original point order;
