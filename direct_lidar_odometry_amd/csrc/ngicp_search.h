@@ -127,11 +127,15 @@ struct WaveStage {
   // needed one row would idle.  Results meet in qkey by a 64-bit atomic min on (distance bits, position): the total order.
   unsigned long long qkey[32];  // per query: nearest so far
   float4 qtab[32];              // per query: transformed coordinates
-  // a unit: ring 1: {query | row code << 5 | (start - run start) << 9, run start, run end, (y,z) gap}; beyond: {query | listed row << 5}
+  // a unit, of ring 1 and of a listed row alike: {query | row code << 5 | (start - run start) << 9, run start, run end, (y,z) gap}; row code:
+  // 0..8 the row's place in the 3 x 3 window, 9 a listed row (whose run is the whole row).  Written by whoever queues the unit, so that the
+  // drain needs nothing but the unit and its query's two words.
   int unit_q[kUnitCap], unit_s[kUnitCap], unit_e[kUnitCap];
   float unit_g[kUnitCap];
   int q_tail, q_head;
 };
+static_assert(sizeof(WaveStage) <= 9872 && 4 * sizeof(WaveStage) + 4 * 32 * sizeof(double) <= 40 * 1024 + 512,
+              "four of these and the block's row of sums are the pass kernel's 40 KB of LDS per block: more, and a CU holds a block less");
 
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
