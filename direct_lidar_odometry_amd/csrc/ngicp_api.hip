@@ -32,6 +32,7 @@
 #include "ngicp_voxel.h"
 #include "ngicp_voxel_batch.h"
 #include "ngicp_voxel_roll.h"
+#include "ngicp_voxel_ray.h"
 #include "ngicp_robust.h"
 
 using namespace ngk;
@@ -1389,6 +1390,17 @@ int ngicp_voxel_rolling_insert_map(ngicp_t* h, ngicp_t* from, const float T_colm
 
 int ngicp_voxel_rolling_transform(ngicp_t* h, const float T_colmajor[16], size_t* n_vox_after) {
   return guarded(h, [&] { roll_transform(h, T_colmajor, n_vox_after); });
+}
+
+// ---- clearing the rolling map along a scan's rays (include/ngicp.h "rolling voxel map: clearing along rays"; ngicp_voxel_ray.h) ----
+int ngicp_voxel_rolling_ray_clear(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], const float* origin_or_null, const ngicp_ray_clear_options* options_or_null,
+                                  ngicp_ray_clear_result* result_out) {
+  if (!from) return NGICP_ERR_ARG;
+  return guarded(h, [&] { roll_ray_clear(h, from, T_colmajor, origin_or_null, options_or_null, result_out); });
+}
+
+int ngicp_voxel_rolling_ray_counts(ngicp_t* h, uint32_t* miss_n, uint32_t* hit_n, size_t capacity, size_t* n_out) {
+  return guarded(h, [&] { roll_ray_counts(h, miss_n, hit_n, capacity, n_out); });
 }
 
 int ngicp_target_knn(ngicp_t* h, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {

@@ -432,6 +432,14 @@ struct ngicp {
   DevBuf roll_up, roll_seg_stamp;
   hipEvent_t ev_rec_a = nullptr, ev_rec_b = nullptr;  // around a record insert, whose commit is left in the stream:
   bool rec_time_pending = false;                      // its time is read when it is next asked for (roll_resolve_time)
+  // clearing along rays (csrc/ngicp_voxel_ray.h): two grow-only pairs of per-voxel counters {miss [n], hit [n]} - a call
+  // counts into the pair that does not hold the last accepted call's, so a refused call leaves those readable - and the totals
+  // {counted steps, occupied, misses} as three 64-bit integers
+  DevBuf roll_ray[2], roll_ray_tot;
+  int ray_cur = 0;                       // the pair of the last accepted call
+  bool ray_valid = false;                // a call has been accepted ...
+  long long ray_gen = 0;                 // ... and left the map at this generation (anything else that writes the map moves it on)
+  size_t ray_n = 0;                      // voxels before that call's removal: the length of its counters
   // motion deskew (csrc/ngicp_deskew.h): the separately uploaded times, the uploaded trajectory and the table k_deskew_prepare makes of it
   DevBuf dsk_times, dsk_in, dsk_table;
   std::vector<double> dsk_host;          // the trajectory as uploaded: [M times][M x 16 poses][16 T_ref] (outlives the asynchronous copy)

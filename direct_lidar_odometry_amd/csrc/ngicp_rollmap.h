@@ -1,6 +1,7 @@
 // The rolling voxel map's host code (ngicp_voxel_roll.h; include/ngicp.h "rolling voxel map"): insert, evict, clear and the growth of its
 // arrays and table; behind them the record routes: restore, insert of records, handle-to-handle insert,
-// move in place.  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose size_voxel_work /
+// move in place; and the clearing along a scan's rays (ngicp_voxel_ray.h), which shares the eviction's tail
+// (roll_remove_unkept).  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose size_voxel_work /
 // voxel_segments / read_count / exclusive_scan_flags number a scan's voxels).
 #pragma once
 
@@ -326,18 +327,14 @@ void roll_set(ngicp* h, size_t n, const int* ijk, const double* sum_n3, const do
   }
 }
 
-// Evict: flags, the scan, a stable compaction into the workspace, copies back, the table rebuilt.  One host synchronisation (the
-// survivors' count).
-void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_stamp, size_t* n_removed_out) {
-  roll_require_on(h, "ngicp_voxel_rolling_evict");
-  if (!centre) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_rolling_evict: null centre"};
-  if (std::isnan(max_dist)) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_rolling_evict: max_dist is not a number"};
+// The tail every removal shares.  `launch_flags(keep)` has written keep[v] = 0 / 1 for the n (> 0) voxels of the map; then the scan, a
+// stable compaction into the workspace, ONE host synchronisation - the survivors' count, with whatever `queue_reads` queues beside it -
+// then `before_write()`, which refuses by throwing, and the copies back and the table rebuilt, both left in the stream.  A refused call
+// has written only workspace.  Returns the survivors' count.
+template <class Flags, class Reads, class BeforeWrite>
+int roll_remove_unkept(ngicp* h, const char* what, Flags&& launch_flags, Reads&& queue_reads, BeforeWrite&& before_write) {
   ngicp::RollMap& r = h->roll;
-  h->hook_valid = 0;
-  ++h->roll.gen;
-  if (n_removed_out) *n_removed_out = 0;
   const int n = (int)r.n_vox;
-  if (n == 0) return;
   size_voxel_work(h, (size_t)n);
   const size_t rec_bytes = (size_t)n * kVoxRec * sizeof(double);
   h->roll_tmp.ensure(2 * rec_bytes + (size_t)n * 16);
@@ -348,14 +345,14 @@ void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_
   double* rec_o = sums_o + (size_t)n * kVoxRec;
   unsigned long long* vkeys_o = reinterpret_cast<unsigned long long*>(rec_o + (size_t)n * kVoxRec);
   long long* stamps_o = reinterpret_cast<long long*>(vkeys_o + n);
-  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
-  hipLaunchKernelGGL(k_roll_evict_flags, dim3(blocks), dim3(256), 0, h->stream, (const unsigned long long*)r.vkeys.as<unsigned long long>(), (const long long*)r.stamps.as<long long>(), n,
-                     h->voxel_res, (double)centre[0], (double)centre[1], (double)centre[2], max_dist, min_stamp, keep);
+  launch_flags(keep);
   exclusive_scan_flags(h, keep, n, rank);
   hipLaunchKernelGGL(k_roll_compact, dim3(blocks), dim3(256), 0, h->stream, (const int*)keep, (const int*)rank, n, (const double*)r.sums.as<double>(), (const double*)r.rec.as<double>(),
                      (const unsigned long long*)r.vkeys.as<unsigned long long>(), (const long long*)r.stamps.as<long long>(), sums_o, rec_o, vkeys_o, stamps_o);
+  queue_reads();
   const int n_keep = read_count(h, rank + n).count;
-  if (n_keep < 0 || n_keep > n) throw ArgError{NGICP_ERR_HIP, "rolling voxel map evict: inconsistent count of survivors"};
+  before_write();
+  if (n_keep < 0 || n_keep > n) throw ArgError{NGICP_ERR_HIP, std::string(what) + ": inconsistent count of survivors"};
   if (n_keep < n) {
     const size_t k = (size_t)n_keep;
     if (k) {
@@ -367,12 +364,160 @@ void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_
     r.n_vox = k;
     roll_refill_table(h);
   }
+  return n_keep;
+}
+
+// Evict: flags, then the shared tail.  One host synchronisation (the survivors' count) and the wait for the time.
+void roll_evict(ngicp* h, const float centre[3], double max_dist, long long min_stamp, size_t* n_removed_out) {
+  roll_require_on(h, "ngicp_voxel_rolling_evict");
+  if (!centre) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_rolling_evict: null centre"};
+  if (std::isnan(max_dist)) throw ArgError{NGICP_ERR_ARG, "ngicp_voxel_rolling_evict: max_dist is not a number"};
+  ngicp::RollMap& r = h->roll;
+  h->hook_valid = 0;
+  ++h->roll.gen;
+  if (n_removed_out) *n_removed_out = 0;
+  const int n = (int)r.n_vox;
+  if (n == 0) return;
+  size_voxel_work(h, (size_t)n);  // (before the first event: growing a buffer waits for the device)
+  h->roll_tmp.ensure(2 * (size_t)n * kVoxRec * sizeof(double) + (size_t)n * 16);
+  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+  const int n_keep = roll_remove_unkept(
+      h, "rolling voxel map evict",
+      [&](int* keep) {
+        hipLaunchKernelGGL(k_roll_evict_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const unsigned long long*)r.vkeys.as<unsigned long long>(),
+                           (const long long*)r.stamps.as<long long>(), n, h->voxel_res, (double)centre[0], (double)centre[1], (double)centre[2], max_dist, min_stamp, keep);
+      },
+      [] {}, [] {});
   HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
   HIP_TRY(hipEventSynchronize(h->ev_vox_b));  // (the time; the next alignment would wait for this work anyway)
   HIP_TRY(hipGetLastError());
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess) r.last_evict_ms = ms;
   if (n_removed_out) *n_removed_out = (size_t)(n - n_keep);
+}
+
+// ---- clearing along a scan's rays (ngicp_voxel_ray.h; include/ngicp.h "rolling voxel map: clearing along rays") ----
+ngicp_ray_clear_options roll_ray_defaults() {
+  ngicp_ray_clear_options o;
+  o.near_cells = 1;
+  o.back_cells = 2;
+  o.max_steps = 4096;
+  o.min_miss = 2;
+  o.radius_cells = 0.25;
+  o.keep_stamp = 0;
+  o.dry_run = 0;
+  return o;
+}
+
+// Count `from`'s source cloud at the float pose T against the map, then remove the voxels seen through (the eviction's tail).  One host
+// synchronisation: the refusal flag, the totals and the survivors' count in one read-back, behind the compaction into the workspace and
+// before anything is copied back.  The counters go into the pair that does not hold the last accepted call's.
+void roll_ray_clear(ngicp* h, ngicp* from, const float T[16], const float* origin, const ngicp_ray_clear_options* opt_or_null, ngicp_ray_clear_result* out) {
+  const char* entry = "ngicp_voxel_rolling_ray_clear";
+  roll_require_on(h, entry);
+  if (!T) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null transform"};
+  const ngicp_ray_clear_options o = opt_or_null ? *opt_or_null : roll_ray_defaults();
+  if (o.near_cells < 1) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": near_cells below 1"};
+  if (o.back_cells < 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": back_cells below 0"};
+  if (o.max_steps < 1 || o.max_steps > 65536) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": max_steps outside 1 .. 65536"};
+  if (o.min_miss < 1) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": min_miss below 1"};
+  if (!(o.radius_cells >= 0.0)) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": radius_cells is negative or not a number"};
+  if (h->device != from->device) throw ArgError{NGICP_ERR_ARG, std::string(entry) + " across devices is not supported"};
+  if (!from->src.present) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the producer has no source cloud"};
+  ensure_slot_ready(from, from->src, "source");
+  if (from != h) stream_wait_for(h, from);  // the producer's stream may still be writing the cloud
+  const std::shared_ptr<DeviceCloud> cloud = from->src.dev;  // held until the kernel that reads it has been waited for
+  const int n_pts = (int)cloud->n;
+  if (n_pts <= 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": empty source cloud"};
+  ngicp::RollMap& r = h->roll;
+  const int n = (int)r.n_vox;
+  const bool remove = !o.dry_run && n > 0;
+  RollRayArgs a;
+  for (int k = 0; k < 3; ++k) a.o[k] = origin ? origin[k] : T[12 + k];
+  a.inv_res = 1.0f / (float)h->voxel_res;
+  a.res = h->voxel_res;
+  a.near_cells = o.near_cells;
+  a.back_cells = o.back_cells;
+  a.max_steps = o.max_steps;
+  a.use_radius = o.radius_cells > 0.0 ? 1 : 0;
+  const double rad = o.radius_cells * h->voxel_res;
+  a.r2 = rad * rad;
+  // every buffer before the first launch: growing one waits for the device
+  DevBuf& cnt = h->roll_ray[1 - h->ray_cur];
+  cnt.ensure((size_t)std::max(n, 1) * 2 * sizeof(unsigned int));
+  h->roll_ray_tot.ensure(3 * sizeof(unsigned long long));
+  size_voxel_work(h, (size_t)std::max(n, 1));
+  if (remove) h->roll_tmp.ensure(2 * (size_t)n * kVoxRec * sizeof(double) + (size_t)n * 16);
+  unsigned int* miss = cnt.as<unsigned int>();
+  unsigned int* hit = miss + n;
+  if (n) HIP_TRY(hipMemsetAsync(cnt.p, 0, (size_t)n * 2 * sizeof(unsigned int), h->stream));
+  HIP_TRY(hipMemsetAsync(h->roll_ray_tot.p, 0, 3 * sizeof(unsigned long long), h->stream));
+  HIP_TRY(hipMemsetAsync(h->vox_flag.p, 0, sizeof(int), h->stream));
+  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+  const bool probe = r.slots && n;
+  hipLaunchKernelGGL(k_roll_ray_count, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, h->stream, cloud->pts(), n_pts, roll_pose(T), a,
+                     probe ? (const ulonglong2*)r.table.as<ulonglong2>() : (const ulonglong2*)nullptr, (unsigned int)(r.slots ? r.slots - 1 : 0), (const double*)r.rec.as<double>(), miss,
+                     hit, h->roll_ray_tot.as<unsigned long long>(), h->vox_flag.as<int>());
+  HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
+  unsigned long long totals[3] = {0, 0, 0};
+  int bad = 0;
+  const auto queue_reads = [&] {
+    HIP_TRY(hipMemcpyAsync(totals, h->roll_ray_tot.p, sizeof(totals), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  };
+  // called behind the one synchronisation: the refusal, or - from here on the map is written - what an eviction drops
+  const auto accept = [&] {
+    if (bad)
+      throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the origin or a transformed point lies 2^20 voxels or more from the map's origin on some axis (or is not finite); nothing was changed"};
+    if (!o.dry_run) {
+      h->hook_valid = 0;
+      ++h->roll.gen;
+    }
+  };
+  int n_keep = n;
+  if (remove) {
+    n_keep = roll_remove_unkept(
+        h, entry,
+        [&](int* keep) {
+          hipLaunchKernelGGL(k_roll_ray_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const unsigned int*)miss, (const unsigned int*)hit,
+                             (const long long*)r.stamps.as<long long>(), n, (unsigned int)o.min_miss, (long long)o.keep_stamp, keep);
+        },
+        queue_reads, accept);
+  } else {
+    queue_reads();
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipGetLastError());
+    accept();
+  }
+  h->ray_cur = 1 - h->ray_cur;
+  h->ray_valid = true;
+  h->ray_gen = h->roll.gen;
+  h->ray_n = (size_t)n;
+  float ms = 0.f;
+  const bool timed = hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess;
+  if (out) {
+    out->n_removed = (size_t)(n - n_keep);
+    out->steps = (long long)totals[0];
+    out->occupied = (long long)totals[1];
+    out->misses = (long long)totals[2];
+    out->kernel_ms = timed ? (double)ms : 0.0;
+  }
+}
+
+// the counters of the last accepted clear, in the numbering from before its removal
+void roll_ray_counts(ngicp* h, unsigned int* miss_n, unsigned int* hit_n, size_t capacity, size_t* n_out) {
+  const char* entry = "ngicp_voxel_rolling_ray_counts";
+  if (!h->ray_valid) throw ArgError{NGICP_ERR_STATE, std::string(entry) + ": no ngicp_voxel_rolling_ray_clear has been accepted"};
+  if (h->ray_gen != h->roll.gen) throw ArgError{NGICP_ERR_STATE, std::string(entry) + ": the map has been changed since the last ngicp_voxel_rolling_ray_clear"};
+  const size_t n = h->ray_n;
+  if (n_out) *n_out = n;
+  if ((!miss_n && !hit_n) || n == 0) return;
+  if (capacity < n) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the arrays are shorter than the " + std::to_string(n) + " voxels of that call"};
+  const unsigned int* dev = h->roll_ray[h->ray_cur].as<unsigned int>();
+  if (miss_n) HIP_TRY(hipMemcpyAsync(miss_n, dev, n * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  if (hit_n) HIP_TRY(hipMemcpyAsync(hit_n, dev + n, n * sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
 }
 
 }  // namespace

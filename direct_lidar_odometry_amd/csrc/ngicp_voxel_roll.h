@@ -26,6 +26,8 @@
 //                        twice the size before a commit that would cross the limit, after an eviction and after a restore.
 //   evict                k_roll_evict_flags (keep = 0 / 1 per voxel), the same scan, k_roll_compact into a workspace (stable: the survivors
 //                        keep their order), copies back, table rebuild.
+//   clear along rays     ngicp_voxel_ray.h: k_roll_ray_count walks the map along a scan's rays and counts misses and hits
+//                        per voxel, k_roll_ray_flags turns them into keep flags, and the removal is the eviction's from the scan on.
 // Lookup and commit are separate launches: no probe races an insertion.  Distinct threads own distinct voxels and nothing is added
 // atomically: nothing depends on the order in which threads arrive.  Nothing walks the existing map.
 #pragma once

@@ -99,6 +99,7 @@ EXPORTS = [
     "ngicp_set_voxel_rolling", "ngicp_get_voxel_rolling", "ngicp_voxel_rolling_insert", "ngicp_voxel_rolling_evict", "ngicp_voxel_rolling_clear",
     "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
     "ngicp_voxel_rolling_set", "ngicp_voxel_rolling_insert_voxels", "ngicp_voxel_rolling_insert_map", "ngicp_voxel_rolling_transform",
+    "ngicp_voxel_rolling_ray_clear", "ngicp_voxel_rolling_ray_counts",
     "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
     "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
     "ngicp_deskew_cloud", "ngicp_preprocess_scan_deskewed",
@@ -112,6 +113,18 @@ EXPORTS = [
     "ngicp_pose_graph_set_fixed", "ngicp_pose_graph_get_fixed", "ngicp_pose_graph_set_robust", "ngicp_pose_graph_get_poses", "ngicp_pose_graph_set_poses",
     "ngicp_pose_graph_linearize", "ngicp_pose_graph_multiply", "ngicp_pose_graph_optimize", "ngicp_pose_graph_corrections", "ngicp_pose_graph_kernel_ms",
 ]
+
+
+class RayClearOptions(C.Structure):
+    """ngicp_ray_clear_options (include/ngicp.h, "rolling voxel map: clearing along rays")."""
+    _fields_ = [("near_cells", C.c_int), ("back_cells", C.c_int), ("max_steps", C.c_int), ("min_miss", C.c_int), ("radius_cells", C.c_double),
+                ("keep_stamp", C.c_longlong), ("dry_run", C.c_int)]
+    DEFAULTS = dict(near_cells=1, back_cells=2, max_steps=4096, min_miss=2, radius_cells=0.25, keep_stamp=0, dry_run=0)
+
+
+class RayClearResult(C.Structure):
+    """ngicp_ray_clear_result."""
+    _fields_ = [("n_removed", C.c_size_t), ("steps", C.c_longlong), ("occupied", C.c_longlong), ("misses", C.c_longlong), ("kernel_ms", C.c_double)]
 
 
 PG_TRACE_CAP = 256  # NGICP_PG_TRACE_CAP
@@ -260,6 +273,9 @@ def load_library() -> C.CDLL:
     L.ngicp_voxel_rolling_insert_voxels.argtypes = [vp, C.c_size_t, c_f64p, c_f64p, c_i32p, c_f32p, c_szp, c_szp]
     L.ngicp_voxel_rolling_insert_map.argtypes = [vp, vp, c_f32p, c_szp, c_szp]
     L.ngicp_voxel_rolling_transform.argtypes = [vp, c_f32p, c_szp]
+    c_u32p = C.POINTER(C.c_uint32)
+    L.ngicp_voxel_rolling_ray_clear.argtypes = [vp, vp, c_f32p, c_f32p, C.POINTER(RayClearOptions), C.POINTER(RayClearResult)]
+    L.ngicp_voxel_rolling_ray_counts.argtypes = [vp, c_u32p, c_u32p, C.c_size_t, c_szp]
     L.ngicp_set_robust_kernel.argtypes = [vp, C.c_int, C.c_double]
     L.ngicp_get_robust_kernel.argtypes = [vp, c_i32p, c_f64p]
     L.ngicp_robust_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, C.c_size_t, c_i32p]
@@ -556,6 +572,36 @@ class NanoGICP:
         t = _colmajor16(T, np.float32); n = C.c_size_t(0)
         self._ck(self._L.ngicp_voxel_rolling_transform(self._h, _p(t, c_f32p), C.byref(n)))
         return n.value
+
+    # ---- clearing the rolling map along a scan's rays (include/ngicp.h "rolling voxel map: clearing along rays") ----
+    def clearVoxelMapAlongRays(self, producer: "NanoGICP", T, origin=None, **options) -> dict:
+        """Count, per voxel of the rolling map, the rays of the producer's source cloud at the float pose T that pass through it (miss)
+        and that end in it (hit) - from `origin` (three floats in the map frame; None: T's translation) - and remove the voxels with
+        at least min_miss misses, no hit and (keep_stamp > 0) a stamp below keep_stamp.  Options (defaults): near_cells (1), back_cells
+        (2), max_steps (4096), min_miss (2), radius_cells (0.25), keep_stamp (0), dry_run (0: count and remove; else count only).
+        -> {n_removed, steps, occupied, misses, kernel_ms}.  A refused call raises and changes nothing."""
+        unknown = set(options) - set(RayClearOptions.DEFAULTS)
+        if unknown:
+            raise TypeError(f"clearVoxelMapAlongRays: unknown options {sorted(unknown)}")
+        o = {**RayClearOptions.DEFAULTS, **options}
+        opt = RayClearOptions(int(o["near_cells"]), int(o["back_cells"]), int(o["max_steps"]), int(o["min_miss"]), float(o["radius_cells"]),
+                              int(o["keep_stamp"]), int(o["dry_run"]))
+        t = _colmajor16(T, np.float32)
+        org = None if origin is None else np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+        res = RayClearResult()
+        self._ck(self._L.ngicp_voxel_rolling_ray_clear(self._h, producer._h, _p(t, c_f32p), None if org is None else _p(org, c_f32p), C.byref(opt), C.byref(res)))
+        return dict(n_removed=res.n_removed, steps=res.steps, occupied=res.occupied, misses=res.misses, kernel_ms=res.kernel_ms)
+
+    def voxelMapRayCounts(self) -> tuple:
+        """-> (miss (V,) uint32, hit (V,) uint32) of the last clearVoxelMapAlongRays, in the numbering from before its removal.  Raises
+        (NGICP_ERR_STATE) when no call has been accepted or anything else has changed the map since."""
+        nv = C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_ray_counts(self._h, None, None, 0, C.byref(nv)))
+        n = nv.value
+        miss = np.zeros(n, dtype=np.uint32); hit = np.zeros(n, dtype=np.uint32)
+        c_u32p = C.POINTER(C.c_uint32)
+        self._ck(self._L.ngicp_voxel_rolling_ray_counts(self._h, _p(miss, c_u32p), _p(hit, c_u32p), n, C.byref(nv)))
+        return miss, hit
 
     def setRobustKernel(self, kind, width: float = 1.0):
         """A robust kernel on every term of the cost (include/ngicp.h "robust kernel"): HUBER, CAUCHY or GEMAN_MCCLURE of the given width

@@ -644,6 +644,59 @@ class NanoGICP {
     if (ok) *ok = good;
     return n;
   }
+  // ---- clearing the rolling map along a scan's rays (include/ngicp.h "rolling voxel map: clearing along rays") ----
+  // Per voxel of the map: the rays of `producer`'s current source cloud at the float pose T that pass through it (miss) and that end in
+  // it (hit), from `origin` (three floats in the map frame; nullptr: T's translation).  The voxels with at least min_miss misses, no hit
+  // and (keep_stamp > 0) a stamp below keep_stamp are removed.  In a frame loop: align, clear with the aligned scan, then insert it.
+  struct RayClearOptions {
+    int near_cells = 1;         // the first counted step of a ray
+    int back_cells = 2;         // steps before the end cell that are not counted
+    int max_steps = 4096;       // the last step a ray may count (1 .. 65536): what bounds a ray's cost
+    int min_miss = 2;
+    double radius_cells = 0.25; // a miss needs the voxel's mean within radius_cells * res of the ray's line; 0: every occupied cell
+    long long keep_stamp = 0;
+    bool dry_run = false;       // count only: the map, the correspondences and the hooks' state stay
+  };
+  struct RayClearResult {
+    bool ok = false;            // false: refused, nothing changed
+    size_t n_removed = 0;
+    long long steps = 0, occupied = 0, misses = 0;  // counted steps; of them in occupied cells; of those, misses
+    double kernel_ms = 0.0;
+  };
+  RayClearResult clearVoxelMapAlongRays(NanoGICP& producer, const Matrix4& T, const float* origin = nullptr, const RayClearOptions& options = RayClearOptions()) {
+    RayClearResult r;
+    ngicp_ray_clear_options o;
+    o.near_cells = options.near_cells;
+    o.back_cells = options.back_cells;
+    o.max_steps = options.max_steps;
+    o.min_miss = options.min_miss;
+    o.radius_cells = options.radius_cells;
+    o.keep_stamp = options.keep_stamp;
+    o.dry_run = options.dry_run ? 1 : 0;
+    ngicp_ray_clear_result res;
+    r.ok = h_ && check(ngicp_voxel_rolling_ray_clear(h_, producer.h_, T.data(), origin, &o, &res), "clearVoxelMapAlongRays");
+    if (r.ok) {
+      r.n_removed = res.n_removed;
+      r.steps = res.steps;
+      r.occupied = res.occupied;
+      r.misses = res.misses;
+      r.kernel_ms = res.kernel_ms;
+    }
+    return r;
+  }
+  // miss and hit of the last clearVoxelMapAlongRays, per voxel in the numbering from before its removal; false (and both empty) when
+  // no call has been accepted or anything else has changed the map since
+  bool voxelMapRayCounts(std::vector<uint32_t>& miss, std::vector<uint32_t>& hit) {
+    miss.clear(); hit.clear();
+    size_t n = 0;
+    if (!h_ || !check(ngicp_voxel_rolling_ray_counts(h_, nullptr, nullptr, 0, &n), "voxelMapRayCounts")) return false;
+    miss.resize(n); hit.resize(n);
+    if (!check(ngicp_voxel_rolling_ray_counts(h_, miss.data(), hit.data(), n, &n), "voxelMapRayCounts")) {
+      miss.clear(); hit.clear();
+      return false;
+    }
+    return true;
+  }
 
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
   // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN

@@ -379,6 +379,75 @@ int ngicp_voxel_rolling_insert_voxels(ngicp_t* h, size_t n_rec, const double* su
                                       size_t* n_touched_or_null);
 int ngicp_voxel_rolling_insert_map(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], size_t* n_new_or_null, size_t* n_touched_or_null);
 int ngicp_voxel_rolling_transform(ngicp_t* h, const float T_colmajor[16], size_t* n_vox_after_or_null);
+/* --- rolling voxel map: clearing along rays - drop what the sensor now sees through (csrc/ngicp_voxel_ray.h) ---------
+ * Eviction removes voxels by distance and by age; nothing else removes a voxel whose content has moved away.  This entry counts, per
+ * map voxel, the rays of a scan that pass through it (miss) and that end in it (hit), and removes the voxels seen through often enough.
+ * It changes nothing else; while it is not called every other result is bit for bit what it was.  The project's own definition.
+ *   rays                       A is `from`'s current source cloud (`from` may be h); q_j = T a_j exactly as ngicp_voxel_rolling_insert
+ *                              computes it (float, in the order of ngicp_transform_source).  The origin o is three floats in the map
+ *                              frame; NULL means T's float translation.  c0 is the cell of o and c1 the cell of q_j by the mode's rule,
+ *                              floorf(x * inv_res), |i| < 2^20.  A q_j or an o without a cell (2^20 cells or more from the map's origin
+ *                              on an axis, or not finite): NGICP_ERR_ARG and nothing changes - map, numbering, stamps, insert counter,
+ *                              table, the hooks' state and the counts of the last accepted call all stay.
+ *   the walk                   in double, nothing fused.  od = (double)o, qd = (double)q_j, d = qd - od.  Per axis a:
+ *                              n_a = |c1_a - c0_a|, s_a = sign(c1_a - c0_a), inv_a = 1.0 / d_a (used only where n_a > 0; there d_a != 0
+ *                              and has the sign of s_a).  The ray takes exactly N = n_x + n_y + n_z steps.  Before a step it is in cell
+ *                              cur and has taken k_a steps along axis a; the candidates are the axes with k_a < n_a, with the
+ *                              parameters t_a = ((double)(cur_a + (s_a > 0 ? 1 : 0)) * res - od_a) * inv_a.  The step goes along the
+ *                              candidate with the smallest t_a - a tie goes to the lowest axis, x before y before z - and sets
+ *                              cur_a += s_a.  The cell behind step N is c1 by construction: the walk is 6-connected, and its length is
+ *                              set by the cells, not by floating point.  A diagonal through exact corners steps x, y, z, x, y, z, ...
+ *   counted steps              step j (1 .. N; "its cell" is the cell behind it) is counted when
+ *                              near_cells <= j <= min(N - 1 - back_cells, max_steps).  The origin's cell and the end cell are never
+ *                              among them.  The walk stops behind its last counted step: a ray's cost is bounded by max_steps, not by
+ *                              how far away its point lies.
+ *   a miss                     at a counted step the cell's key is looked up in the map's table; without a voxel there nothing
+ *                              happens.  With voxel v and radius_cells > 0: m = the mean in v's record (S_v / n_v), w = m - od,
+ *                              dd = (d_x*d_x + d_y*d_y) + d_z*d_z, ts = ((w_x*d_x + w_y*d_y) + w_z*d_z) / dd, e = w - ts * d per axis;
+ *                              the step is a miss when ((e_x*e_x + e_y*e_y) + e_z*e_z) <= r*r, r = radius_cells * res: the distance
+ *                              of the mean from the infinite line, ts not clamped.  With radius_cells == 0 every counted step in an
+ *                              occupied cell is a miss.  miss[v] counts the misses; hit[v] counts the rays whose c1 is v's cell
+ *                              (whether or not the walk was cut short).  Why a radius: a ray that descends to a floor far away runs
+ *                              through the CELLS of the floor layer for metres, above the floor itself; the mean of such a voxel lies
+ *                              on the surface, and the ray does not come near it.
+ *   removal                    voxel v goes when miss[v] >= min_miss and hit[v] == 0 and (keep_stamp <= 0 or t_v < keep_stamp).
+ *                              Survivors keep their relative order and are renumbered densely; stamps and the insert counter stay; the
+ *                              table is rebuilt.  The correspondences and the hooks' state are dropped as an eviction drops them
+ *                              (whether or not a voxel went).  dry_run != 0 counts and removes nothing: map, table, correspondences and
+ *                              hooks are left byte for byte alone.
+ *   results                    n_removed; the numbers of counted steps, of counted steps in occupied cells and of misses over all rays
+ *                              (integer sums: exact, whatever the order); the device event time of the counting kernel.  miss and hit
+ *                              of the last accepted call stay on the device in the numbering from BEFORE that call's removal:
+ *                              ngicp_voxel_rolling_ray_counts reads them back (*n_out voxels; NULL arrays ask for the size only;
+ *                              NGICP_ERR_ARG when capacity < *n_out).  It returns NGICP_ERR_STATE when no call has been accepted, or
+ *                              when anything else has written the map since (insert, evict, clear, restore, move, a change of
+ *                              resolution).  An empty map: 0 removed, the steps counted, no counts to read (*n_out == 0).
+ * Errors of _ray_clear: NGICP_ERR_STATE unless the rolling setting is on and res > 0.  NGICP_ERR_ARG: near_cells < 1, back_cells < 0,
+ * max_steps outside 1 .. 65536, min_miss < 1, radius_cells negative or not a number, a null T, a producer without a source cloud,
+ * handles on different devices.
+ * One host synchronisation per call - the refusal flag, the survivors' count and the totals in one read-back, behind the compaction into
+ * a workspace and before anything is copied back; the copies and the table rebuild are left in the handle's stream.  Device memory: 16
+ * bytes per voxel (two pairs of 32-bit counters: a refused call counts into the pair the last accepted call does not occupy) and the
+ * eviction's workspace.
+ * Not here: miss counters that persist across scans (the dry run's counts let a caller keep its own), a Mahalanobis test against the
+ * voxel's covariance, clearing of the target-based or merged maps, sharded and batch entries. */
+typedef struct ngicp_ray_clear_options {
+  int near_cells;        /* the first counted step (1) */
+  int back_cells;        /* steps before the end cell that are not counted (2) */
+  int max_steps;         /* the last step a ray may count, 1 .. 65536 (4096) */
+  int min_miss;          /* misses that remove a voxel without a hit (2) */
+  double radius_cells;   /* r / res of the miss test; 0: the cell test alone (0.25) */
+  long long keep_stamp;  /* > 0: voxels with a stamp of at least this stay (0) */
+  int dry_run;           /* != 0: count only (0) */
+} ngicp_ray_clear_options;   /* NULL: the defaults in brackets */
+typedef struct ngicp_ray_clear_result {
+  size_t n_removed;
+  long long steps, occupied, misses;  /* counted steps; of them in occupied cells; of those, misses */
+  double kernel_ms;                   /* device event time of the counting kernel */
+} ngicp_ray_clear_result;
+int ngicp_voxel_rolling_ray_clear(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], const float* origin_or_null, const ngicp_ray_clear_options* options_or_null,
+                                  ngicp_ray_clear_result* result_out_or_null);
+int ngicp_voxel_rolling_ray_counts(ngicp_t* h, uint32_t* miss_n_or_null, uint32_t* hit_n_or_null, size_t capacity, size_t* n_out_or_null);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
