@@ -1403,6 +1403,16 @@ int ngicp_voxel_rolling_ray_counts(ngicp_t* h, uint32_t* miss_n, uint32_t* hit_n
   return guarded(h, [&] { roll_ray_counts(h, miss_n, hit_n, capacity, n_out); });
 }
 
+// ---- the gated insert into the rolling map (include/ngicp.h "rolling voxel map: gated insert"; ngicp_voxel_gate.h) ----
+int ngicp_voxel_rolling_insert_gated(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], const ngicp_gate_options* options_or_null, ngicp_gate_result* result_out) {
+  if (!from) return NGICP_ERR_ARG;
+  return guarded(h, [&] { roll_insert_gated(h, from, T_colmajor, options_or_null, result_out); });
+}
+
+int ngicp_voxel_rolling_insert_classes(ngicp_t* h, uint8_t* cls_n, size_t capacity, size_t* n_out) {
+  return guarded(h, [&] { roll_gate_classes(h, cls_n, capacity, n_out); });
+}
+
 int ngicp_target_knn(ngicp_t* h, const float* q, size_t nq, size_t stride, int k, int* idx, float* d2) {
   return guarded(h, [&] { knn_impl(h, 1, q, nq, stride, k, idx, d2); });
 }
@@ -2369,3 +2379,23 @@ int ngicp_voxel_fitness_kernel_ms(const ngicp_t* h, double* ms) {
 #include "ngicp_keyframe_move.h"  // (kernels and entries; behind everything else, for the same reason)
 
 #include "ngicp_pose_graph.h"  // (kernels and entries; behind everything else, for the same reason)
+
+// ---- the gated insert's kernels (csrc/ngicp_voxel_gate.h) and their launches, which roll_insert_gated (ngicp_rollmap.h) calls ----
+#include "ngicp_voxel_gate.h"  // (behind everything else, for the same reason)
+
+namespace {
+
+void launch_roll_gate(ngicp* h, const RollGateArgs& a, const RollPose& P) {
+  const dim3 grid((unsigned)((a.n + kGateBlock - 1) / kGateBlock)), block(kGateBlock);
+  switch (h->voxel_nbr) {
+    case NGICP_VOX_DIRECT1: hipLaunchKernelGGL((k_roll_gate<1>), grid, block, 0, h->stream, a, P); break;
+    case NGICP_VOX_DIRECT7: hipLaunchKernelGGL((k_roll_gate<7>), grid, block, 0, h->stream, a, P); break;
+    default: hipLaunchKernelGGL((k_roll_gate<27>), grid, block, 0, h->stream, a, P); break;
+  }
+}
+
+void launch_roll_gate_scatter(ngicp* h, const int* keep, const int* rank, int n, const unsigned long long* keys_in, const int* vals_in, unsigned long long* keys, int* vals) {
+  hipLaunchKernelGGL((k_roll_gate_scatter<1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, keep, rank, n, keys_in, vals_in, keys, vals);
+}
+
+}  // namespace

@@ -440,6 +440,13 @@ struct ngicp {
   bool ray_valid = false;                // a call has been accepted ...
   long long ray_gen = 0;                 // ... and left the map at this generation (anything else that writes the map moves it on)
   size_t ray_n = 0;                      // voxels before that call's removal: the length of its counters
+  // the gated insert (csrc/ngicp_voxel_gate.h): two grow-only class arrays (one byte per scan point, original order) - a
+  // call classifies into the one that does not hold the last accepted call's, so a refused call leaves those readable - and the four
+  // class counts behind a flag word of their own
+  DevBuf roll_gate_cls[2], roll_gate_cnt;
+  int gate_cur = 0;                      // the array of the last accepted call
+  bool gate_valid = false;               // a call has been accepted since the last ngicp_voxel_rolling_clear
+  size_t gate_n = 0;                     // the points of that call's scan
   // motion deskew (csrc/ngicp_deskew.h): the separately uploaded times, the uploaded trajectory and the table k_deskew_prepare makes of it
   DevBuf dsk_times, dsk_in, dsk_table;
   std::vector<double> dsk_host;          // the trajectory as uploaded: [M times][M x 16 poses][16 T_ref] (outlives the asynchronous copy)

@@ -1,8 +1,8 @@
 // The rolling voxel map's host code (ngicp_voxel_roll.h; include/ngicp.h "rolling voxel map"): insert, evict, clear and the growth of its
 // arrays and table; behind them the record routes: restore, insert of records, handle-to-handle insert,
-// move in place; and the clearing along a scan's rays (ngicp_voxel_ray.h), which shares the eviction's tail
-// (roll_remove_unkept).  Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose size_voxel_work /
-// voxel_segments / read_count / exclusive_scan_flags number a scan's voxels).
+// move in place; the clearing along a scan's rays (ngicp_voxel_ray.h), which shares the eviction's tail
+// (roll_remove_unkept); and the gated insert (ngicp_voxel_gate.h), next to the plain one.
+// Part of ngicp_api.hip's translation unit (included there, after ngicp_voxelmap.h, whose size_voxel_work / voxel_segments / read_count / exclusive_scan_flags number a scan's voxels).
 #pragma once
 
 namespace {
@@ -65,6 +65,7 @@ bool roll_reserve_table(ngicp* h, size_t need) {
 void roll_clear(ngicp* h) {
   h->roll.n_vox = 0;
   h->roll.inserts = 0;
+  h->gate_valid = false;  // (the classes of the last gated insert are read up to here)
   if (h->roll.slots) roll_refill_table(h);  // (memory stays with the handle)
   h->hook_valid = 0;
   ++h->roll.gen;
@@ -147,6 +148,156 @@ void roll_insert(ngicp* h, ngicp* from, const float T[16], size_t* n_new_out, si
   h->rec_time_pending = false;  // (a record insert's time that nobody asked for is superseded)
   if (n_new_out) *n_new_out = (size_t)n_new;
   if (n_touched_out) *n_touched_out = (size_t)n_seg;
+}
+
+// ---- the gated insert (ngicp_voxel_gate.h; include/ngicp.h "rolling voxel map: gated insert") ----
+// the two launches of its own; defined behind the kernels, at the end of ngicp_api.hip
+void launch_roll_gate(ngicp* h, const RollGateArgs& a, const RollPose& P);
+void launch_roll_gate_scatter(ngicp* h, const int* keep, const int* rank, int n, const unsigned long long* keys_in, const int* vals_in, unsigned long long* keys, int* vals);
+
+// NULL options: no gate (max_mahalanobis has no default of its own; DBL_MAX keeps every judged point) and the defaults of include/ngicp.h
+ngicp_gate_options roll_gate_defaults() {
+  ngicp_gate_options o;
+  o.max_mahalanobis = std::numeric_limits<double>::max();
+  o.min_voxel_count = 1;
+  o.insert_new = 1;
+  o.insert_unjudged = 1;
+  o.dry_run = 0;
+  return o;
+}
+
+// Classify `from`'s source cloud against the map at the float pose T and insert the kept points as roll_insert inserts a scan.  Three
+// host synchronisations, one more than roll_insert: FIRST the refusal flag (judged on every point), the class counts and the kept
+// points' count in one read-back, behind the classification, the scan over the keep flags and the scatter, all of which write workspace
+// only; then roll_insert's two - the kept points' voxel count, and the number of new voxels behind the commit.  Every refusal comes
+// before the first write to the map.  The classes go into the array that does not hold the last accepted call's.
+void roll_insert_gated(ngicp* h, ngicp* from, const float T[16], const ngicp_gate_options* opt, ngicp_gate_result* out) {
+  const char* entry = "ngicp_voxel_rolling_insert_gated";
+  roll_require_on(h, entry);
+  if (!T) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": null transform"};
+  const ngicp_gate_options o = opt ? *opt : roll_gate_defaults();
+  if (!(o.max_mahalanobis >= 0.0) || std::isinf(o.max_mahalanobis))
+    throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": max_mahalanobis must be >= 0 and finite (DBL_MAX: no gate)"};
+  if (o.min_voxel_count < 1) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": min_voxel_count below 1"};
+  if (h->device != from->device) throw ArgError{NGICP_ERR_ARG, std::string(entry) + " across devices is not supported"};
+  if (!from->src.present) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": empty source cloud"};
+  ensure_slot_ready(from, from->src, "source");
+  if (from->src_covs.n != from->src.dev->n) compute_covs(from, from->src, from->src_covs, "source");  // (as roll_insert)
+  const double* covs = covs_for(from, from->src_covs, from->src.dev);
+  if (from != h) stream_wait_for(h, from);
+  const std::shared_ptr<DeviceCloud> cloud = from->src.dev;  // held until the last kernel that reads it has been waited for
+  const std::shared_ptr<DevBuf> cov_hold = from->src_covs.data;
+  ngicp::RollMap& r = h->roll;
+  const int n = (int)cloud->n;
+  if (n <= 0) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": empty source cloud"};
+  const RollPose P = roll_pose(T);
+  // every buffer before the first launch: growing one waits for the device
+  size_voxel_work(h, (size_t)n);
+  h->roll_q.ensure((size_t)n * sizeof(float4));
+  h->roll_sums.ensure((size_t)n * kVoxRec * sizeof(double));
+  h->roll_hit.ensure((size_t)n * sizeof(int));
+  DevBuf& cls = h->roll_gate_cls[1 - h->gate_cur];
+  cls.ensure((size_t)n);
+  h->roll_gate_cnt.ensure(4 * sizeof(int));
+  unsigned long long* keys_a = h->vox_keys.as<unsigned long long>();  // (2 n entries: the uncompacted pairs go into the second half)
+  int* vals_a = h->vox_vals.as<int>();
+  int* keep = h->vox_scan.as<int>();  // (as roll_remove_unkept: flags, then n + 1 + kCellPad ranks; voxel_segments takes the buffer over behind the scatter)
+  int* keep_rank = keep + n;
+  const bool probe = r.slots && r.n_vox;
+  RollGateArgs a{};
+  a.pts = cloud->pts();
+  a.covs = covs;
+  a.n = n;
+  a.inv_res = 1.0f / (float)h->voxel_res;
+  a.table = probe ? (const ulonglong2*)r.table.as<ulonglong2>() : (const ulonglong2*)nullptr;
+  a.mask = (unsigned int)(r.slots ? r.slots - 1 : 0);
+  a.rec = r.rec.as<double>();
+  a.max_m = o.max_mahalanobis;
+  a.min_count = (double)o.min_voxel_count;
+  a.keep_new = o.insert_new ? 1 : 0;
+  a.keep_unjudged = o.insert_unjudged ? 1 : 0;
+  a.qpts = h->roll_q.as<float4>();
+  a.keys = keys_a + n;
+  a.vals = vals_a + n;
+  a.cls = cls.as<unsigned char>();
+  a.keep = keep;
+  a.counts = h->roll_gate_cnt.as<int>();
+  a.bad = h->vox_flag.as<int>();
+  HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+  HIP_TRY(hipMemsetAsync(h->vox_flag.p, 0, sizeof(int), h->stream));
+  HIP_TRY(hipMemsetAsync(h->roll_gate_cnt.p, 0, 4 * sizeof(int), h->stream));
+  launch_roll_gate(h, a, P);
+  if (!o.dry_run) {
+    exclusive_scan_flags(h, keep, n, keep_rank);
+    launch_roll_gate_scatter(h, keep, keep_rank, n, a.keys, a.vals, keys_a, vals_a);
+  }
+  HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
+  int counts[4] = {0, 0, 0, 0}, bad = 0, n_scan = -1;
+  HIP_TRY(hipMemcpyAsync(counts, h->roll_gate_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, h->vox_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (!o.dry_run) HIP_TRY(hipMemcpyAsync(&n_scan, keep_rank + n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
+  // the plain insert's refusal, judged on every point of the scan: map, counter, stamps and the last accepted call's classes stay
+  if (bad)
+    throw ArgError{NGICP_ERR_ARG, "rolling voxel map: a transformed point lies 2^20 voxels or more from the origin on some axis (or is not finite); nothing was inserted"};
+  const int n_kept = counts[kGateExplained] + (a.keep_new ? counts[kGateNew] : 0) + (a.keep_unjudged ? counts[kGateUnjudged] : 0);
+  if (counts[0] + counts[1] + counts[2] + counts[3] != n || (!o.dry_run && n_scan != n_kept)) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent class counts"};
+  h->gate_cur = 1 - h->gate_cur;
+  h->gate_valid = true;
+  h->gate_n = (size_t)n;
+  float ms = 0.f, ms_tail = 0.f;
+  bool timed = hipEventElapsedTime(&ms, h->ev_vox_a, h->ev_vox_b) == hipSuccess;
+  size_t n_new_out = 0, n_touched_out = 0;
+  if (!o.dry_run && n_kept > 0) {
+    // ---- roll_insert from its numbering step on, over the n_kept pairs at the front of vox_keys / vox_vals ----
+    HIP_TRY(hipEventRecord(h->ev_vox_a, h->stream));
+    const VoxelSegments sg = voxel_segments(h, n_kept);
+    const int n_seg = read_count(h, sg.n_seg_dev).count;
+    if (n_seg <= 0 || n_seg > n_kept) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent voxel count"};
+    if (r.n_vox + (size_t)n_seg > (size_t)0x7fffff00) throw ArgError{NGICP_ERR_ARG, "rolling voxel map: too many voxels for int indices"};
+    roll_reserve(h, r.n_vox + (size_t)n_seg);
+    roll_reserve_table(h, r.n_vox + (size_t)n_seg);
+    int* is_new = h->vox_scan.as<int>();  // (as roll_insert; the pairs number n_kept, so n_kept is what places the arrays)
+    int* rank = is_new + n_kept;
+    hipLaunchKernelGGL(k_roll_lookup, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, h->stream, sg.keys, sg.order, sg.seg_start, n_seg, (const float4*)h->roll_q.as<float4>(), covs,
+                       P, (const ulonglong2*)r.table.as<ulonglong2>(), (unsigned int)(r.slots - 1), h->roll_sums.as<double>(), h->roll_hit.as<int>(), is_new);
+    exclusive_scan_flags(h, is_new, n_seg, rank);
+    roll_launch_commit(h, sg, n_seg, rank, r.n_vox, nullptr);
+    HIP_TRY(hipEventRecord(h->ev_vox_b, h->stream));
+    h->hook_valid = 0;
+    ++h->roll.gen;  // (from here on the map is being written)
+    const int n_new = read_count(h, rank + n_seg).count;
+    if (n_new < 0 || n_new > n_seg) throw ArgError{NGICP_ERR_HIP, std::string(entry) + ": inconsistent count of new voxels"};
+    r.n_vox += (size_t)n_new;
+    ++r.inserts;
+    timed = timed && hipEventElapsedTime(&ms_tail, h->ev_vox_a, h->ev_vox_b) == hipSuccess;
+    if (timed) r.last_insert_ms = (double)ms + (double)ms_tail;
+    h->rec_time_pending = false;
+    n_new_out = (size_t)n_new;
+    n_touched_out = (size_t)n_seg;
+  }
+  if (out) {
+    out->n_points = (size_t)n;
+    for (int k = 0; k < 4; ++k) out->n_class[k] = (size_t)counts[k];
+    out->n_kept = (size_t)n_kept;
+    out->n_new = n_new_out;
+    out->n_touched = n_touched_out;
+    out->kernel_ms = timed ? (double)ms + (double)ms_tail : 0.0;
+  }
+}
+
+// the classes of the last accepted gated call, in the scan's original order
+void roll_gate_classes(ngicp* h, unsigned char* cls_n, size_t capacity, size_t* n_out) {
+  const char* entry = "ngicp_voxel_rolling_insert_classes";
+  if (!h->gate_valid) throw ArgError{NGICP_ERR_STATE, std::string(entry) + ": no ngicp_voxel_rolling_insert_gated has been accepted since the map was last cleared"};
+  const size_t n = h->gate_n;
+  if (n_out) *n_out = n;
+  if (!cls_n || n == 0) return;
+  if (capacity < n) throw ArgError{NGICP_ERR_ARG, std::string(entry) + ": the array is shorter than the " + std::to_string(n) + " points of that call"};
+  HIP_TRY(hipMemcpyAsync(cls_n, h->roll_gate_cls[h->gate_cur].p, n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipGetLastError());
 }
 
 // ---- the record routes (include/ngicp.h "rolling voxel map: records") ----

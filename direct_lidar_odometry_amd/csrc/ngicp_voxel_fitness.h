@@ -15,8 +15,9 @@
 //                                  value best = +inf; in ascending slot, slot s wins when m_s < best (ties to the lower slot, a NaN never
 //                                        wins).  No winner among the occupied slots: m = d = +inf, v = -1, matched and never an inlier.
 //                                  inlier  m <= max_m
-//                                Slots are looked up and evaluated one after the other in ONE rolled loop: no thread holds K voxel
-//                                numbers, so there is no LDS column per thread and no scratch.  The block's partial is four doubles
+//                                Slots are looked up and evaluated one after the other in ONE rolled loop (vox_fit_best_slot, which the
+//                                gated insert's k_roll_gate shares, ngicp_voxel_gate.h): no thread holds K voxel numbers, so there is
+//                                no LDS column per thread and no scratch.  The block's partial is four doubles
 //                                {sum m, sum d over the inliers, inliers, matched} (counts as doubles: exact), reduced in a fixed order:
 //                                a lane's value, the wave's butterflies (wave_sum, ngicp_query.h), the four waves in order.
 //                                POINTS (single pose): also m, d, v by ORIGINAL index (p.w); unmatched is -1 / -1 / -1 (the convention
@@ -60,6 +61,40 @@ __device__ __forceinline__ int vox_fit_off(int s, int axis) {
   else return vox_nbr_off<K>(s, axis);
 }
 
+// The slots of a point whose cell is c, looked up and evaluated one after the other in ONE rolled loop (the head of this file: slot,
+// term, value).  ta = T a in FP64, rcr = R C_a R^T.  COUNT (the gated insert, ngicp_voxel_gate.h): an occupied slot is evaluated only
+// when its voxel's count is at least min_count.  Returns whether any slot is occupied; best / best_d / best_v keep the winner's.
+template <int K, bool COUNT>
+__device__ __forceinline__ bool vox_fit_best_slot(int cx, int cy, int cz, const ulonglong2* __restrict__ table, unsigned int mask, const double* __restrict__ rec, double tax,
+                                                  double tay, double taz, const double (&rcr)[6], double min_count, double& best, double& best_d, int& best_v) {
+  bool matched = false;
+  unsigned int probes = 0;  // (voxel_lookup counts them; nobody asks here)
+#pragma unroll 1
+  for (int s = 0; s < K; ++s) {
+    const int nx = cx + vox_fit_off<K>(s, 0), ny = cy + vox_fit_off<K>(s, 1), nz = cz + vox_fit_off<K>(s, 2);
+    if (!(nx > -kVoxBias && nx < kVoxBias && ny > -kVoxBias && ny < kVoxBias && nz > -kVoxBias && nz < kVoxBias)) continue;
+    const int v = voxel_lookup(table, mask, voxel_pack(nx, ny, nz), probes);
+    if (v < 0) continue;
+    matched = true;
+    const double* rv = rec + (size_t)v * kVoxRec;
+    if constexpr (COUNT) {
+      if (!(rv[9] >= min_count)) continue;
+    }
+    double S[6], M[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) S[e] = rv[3 + e] + rcr[e];
+    inv3_sym(S, M);
+    const double ex = rv[0] - tax, ey = rv[1] - tay, ez = rv[2] - taz;
+    const double m = err_term(ex, ey, ez, M);
+    if (m < best) {
+      best = m;
+      best_d = (ex * ex + ey * ey) + ez * ez;
+      best_v = v;
+    }
+  }
+  return matched;
+}
+
 template <int K, bool POINTS>
 __global__ void __launch_bounds__(kVoxFitBlock) k_voxel_fitness(VoxelFitnessArgs a) {
   static_assert(K == 1 || K == 7 || K == 27, "DIRECT1, DIRECT7 or DIRECT27");
@@ -94,27 +129,7 @@ __global__ void __launch_bounds__(kVoxFitBlock) k_voxel_fitness(VoxelFitnessArgs
 #pragma unroll
       for (int e = 0; e < 6; ++e) ca[e] = CA[e];
       rotate_sym(R, ca, rcr);
-      unsigned int probes = 0;  // (voxel_lookup counts them; nobody asks here)
-#pragma unroll 1
-      for (int s = 0; s < K; ++s) {
-        const int nx = cx + vox_fit_off<K>(s, 0), ny = cy + vox_fit_off<K>(s, 1), nz = cz + vox_fit_off<K>(s, 2);
-        if (!(nx > -kVoxBias && nx < kVoxBias && ny > -kVoxBias && ny < kVoxBias && nz > -kVoxBias && nz < kVoxBias)) continue;
-        const int v = voxel_lookup(a.table, a.mask, voxel_pack(nx, ny, nz), probes);
-        if (v < 0) continue;
-        matched = true;
-        const double* rv = a.rec + (size_t)v * kVoxRec;
-        double S[6], M[6];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) S[e] = rv[3 + e] + rcr[e];
-        inv3_sym(S, M);
-        const double ex = rv[0] - tax, ey = rv[1] - tay, ez = rv[2] - taz;
-        const double m = err_term(ex, ey, ez, M);
-        if (m < best) {
-          best = m;
-          best_d = (ex * ex + ey * ey) + ez * ez;
-          best_v = v;
-        }
-      }
+      matched = vox_fit_best_slot<K, false>(cx, cy, cz, a.table, a.mask, a.rec, tax, tay, taz, rcr, 0.0, best, best_d, best_v);
     }
     if (matched) {
       n_match = 1.0;

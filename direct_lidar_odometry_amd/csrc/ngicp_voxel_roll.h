@@ -28,6 +28,8 @@
 //                        keep their order), copies back, table rebuild.
 //   clear along rays     ngicp_voxel_ray.h: k_roll_ray_count walks the map along a scan's rays and counts misses and hits
 //                        per voxel, k_roll_ray_flags turns them into keep flags, and the removal is the eviction's from the scan on.
+//   gated insert         ngicp_voxel_gate.h: k_roll_gate classifies a scan's points against the map and does k_roll_keys' work
+//                        beside it, k_roll_gate_scatter compacts the kept pairs, and the insert is the one above from its numbering step on.
 // Lookup and commit are separate launches: no probe races an insertion.  Distinct threads own distinct voxels and nothing is added
 // atomically: nothing depends on the order in which threads arrive.  Nothing walks the existing map.
 #pragma once
@@ -265,5 +267,30 @@ __global__ void __launch_bounds__(256) k_rollrec_fill(const int* __restrict__ ij
   voxel_record_from_sums(S, rec + (size_t)v * kVoxRec);
   vkeys[v] = voxel_pack(ijk[3 * v + 0], ijk[3 * v + 1], ijk[3 * v + 2]);
 }
+
+// ---- the gated insert: what its classification takes.  The kernels are in ngicp_voxel_gate.h, behind every other kernel
+// of the library; the host code (ngicp_rollmap.h) fills this in front of them. ----
+constexpr int kGateBlock = 256;
+constexpr int kGateNew = 0, kGateExplained = 1, kGateConflict = 2, kGateUnjudged = 3;  // ngicp.h NGICP_GATE_*
+
+struct RollGateArgs {
+  const float4* pts;        // the producer's source in the index's sorted order, w = original index
+  const double* covs;       // [n][6], the same order
+  int n;
+  float inv_res;
+  const ulonglong2* table;  // the rolling map's table (null: a map that never had one - no slot is occupied), mask and records
+  unsigned int mask;
+  const double* rec;
+  double max_m;             // the gate
+  double min_count;         // (double)min_voxel_count: counts are stored as doubles, exact
+  int keep_new, keep_unjudged;
+  float4* qpts;             // [n] by sorted position: the insert's transformed points
+  unsigned long long* keys; // [n] by original index: the insert's keys, uncompacted
+  int* vals;                // [n] by original index: sorted positions
+  unsigned char* cls;       // [n] by original index
+  int* keep;                // [n] by original index: 0 / 1
+  int* counts;              // [4] class counts, cleared by the caller
+  int* bad;
+};
 
 }  // namespace ngk

@@ -100,6 +100,7 @@ EXPORTS = [
     "ngicp_voxel_rolling_get", "ngicp_voxel_rolling_stats",
     "ngicp_voxel_rolling_set", "ngicp_voxel_rolling_insert_voxels", "ngicp_voxel_rolling_insert_map", "ngicp_voxel_rolling_transform",
     "ngicp_voxel_rolling_ray_clear", "ngicp_voxel_rolling_ray_counts",
+    "ngicp_voxel_rolling_insert_gated", "ngicp_voxel_rolling_insert_classes",
     "ngicp_set_robust_kernel", "ngicp_get_robust_kernel", "ngicp_robust_terms",
     "ngicp_set_pose_prior", "ngicp_get_pose_prior", "ngicp_pose_prior_terms",
     "ngicp_deskew_cloud", "ngicp_preprocess_scan_deskewed",
@@ -126,6 +127,20 @@ class RayClearResult(C.Structure):
     """ngicp_ray_clear_result."""
     _fields_ = [("n_removed", C.c_size_t), ("steps", C.c_longlong), ("occupied", C.c_longlong), ("misses", C.c_longlong), ("kernel_ms", C.c_double)]
 
+
+class GateOptions(C.Structure):
+    """ngicp_gate_options (include/ngicp.h, "rolling voxel map: gated insert"); max_mahalanobis has no default."""
+    _fields_ = [("max_mahalanobis", C.c_double), ("min_voxel_count", C.c_int), ("insert_new", C.c_int), ("insert_unjudged", C.c_int), ("dry_run", C.c_int)]
+    DEFAULTS = dict(min_voxel_count=1, insert_new=1, insert_unjudged=1, dry_run=0)
+
+
+class GateResult(C.Structure):
+    """ngicp_gate_result."""
+    _fields_ = [("n_points", C.c_size_t), ("n_class", C.c_size_t * 4), ("n_kept", C.c_size_t), ("n_new", C.c_size_t), ("n_touched", C.c_size_t),
+                ("kernel_ms", C.c_double)]
+
+
+GATE_NEW, GATE_EXPLAINED, GATE_CONFLICT, GATE_UNJUDGED = 0, 1, 2, 3  # NGICP_GATE_*: the classes of a gated insert
 
 PG_TRACE_CAP = 256  # NGICP_PG_TRACE_CAP
 
@@ -276,6 +291,8 @@ def load_library() -> C.CDLL:
     c_u32p = C.POINTER(C.c_uint32)
     L.ngicp_voxel_rolling_ray_clear.argtypes = [vp, vp, c_f32p, c_f32p, C.POINTER(RayClearOptions), C.POINTER(RayClearResult)]
     L.ngicp_voxel_rolling_ray_counts.argtypes = [vp, c_u32p, c_u32p, C.c_size_t, c_szp]
+    L.ngicp_voxel_rolling_insert_gated.argtypes = [vp, vp, c_f32p, C.POINTER(GateOptions), C.POINTER(GateResult)]
+    L.ngicp_voxel_rolling_insert_classes.argtypes = [vp, C.POINTER(C.c_uint8), C.c_size_t, c_szp]
     L.ngicp_set_robust_kernel.argtypes = [vp, C.c_int, C.c_double]
     L.ngicp_get_robust_kernel.argtypes = [vp, c_i32p, c_f64p]
     L.ngicp_robust_terms.argtypes = [vp, c_f64p, c_f64p, c_f64p, C.c_size_t, c_i32p]
@@ -602,6 +619,35 @@ class NanoGICP:
         c_u32p = C.POINTER(C.c_uint32)
         self._ck(self._L.ngicp_voxel_rolling_ray_counts(self._h, _p(miss, c_u32p), _p(hit, c_u32p), n, C.byref(nv)))
         return miss, hit
+
+    # ---- the gated insert into the rolling map (include/ngicp.h "rolling voxel map: gated insert") ----
+    def insertIntoVoxelMapGated(self, producer: "NanoGICP", T, max_mahalanobis: float, **options) -> dict:
+        """insertIntoVoxelMap of the points the rolling map does not contradict: every point of the producer's source cloud is classified
+        against the map at the float pose T - NEW (0, no occupied slot), EXPLAINED (1, best m <= max_mahalanobis), CONFLICT (2, best m
+        above it), UNJUDGED (3, occupied slots but no voxel of at least min_voxel_count points gave a finite m) - and the EXPLAINED
+        points, the NEW ones (insert_new) and the UNJUDGED ones (insert_unjudged) are inserted exactly as insertIntoVoxelMap would insert
+        them alone.  m is voxel_fitness_points' (no voxel-count factor: a chi-square-like value with 3 degrees of freedom).  Options
+        (defaults): min_voxel_count (1), insert_new (1), insert_unjudged (1), dry_run (0: classify and insert; else classify only).
+        -> {n_points, n_class (4 ints), n_kept, n_new, n_touched, kernel_ms}.  A refused call raises and changes nothing."""
+        unknown = set(options) - set(GateOptions.DEFAULTS)
+        if unknown:
+            raise TypeError(f"insertIntoVoxelMapGated: unknown options {sorted(unknown)}")
+        o = {**GateOptions.DEFAULTS, **options}
+        opt = GateOptions(float(max_mahalanobis), int(o["min_voxel_count"]), int(o["insert_new"]), int(o["insert_unjudged"]), int(o["dry_run"]))
+        t = _colmajor16(T, np.float32)
+        res = GateResult()
+        self._ck(self._L.ngicp_voxel_rolling_insert_gated(self._h, producer._h, _p(t, c_f32p), C.byref(opt), C.byref(res)))
+        return dict(n_points=res.n_points, n_class=[int(c) for c in res.n_class], n_kept=res.n_kept, n_new=res.n_new, n_touched=res.n_touched,
+                    kernel_ms=res.kernel_ms)
+
+    def voxelMapInsertClasses(self) -> np.ndarray:
+        """-> (n,) uint8: the classes of the last insertIntoVoxelMapGated, dry or not, in the scan's original order.  Raises
+        (NGICP_ERR_STATE) before the first such call and after clearVoxelMap."""
+        nv = C.c_size_t(0)
+        self._ck(self._L.ngicp_voxel_rolling_insert_classes(self._h, None, 0, C.byref(nv)))
+        cls = np.zeros(nv.value, dtype=np.uint8)
+        self._ck(self._L.ngicp_voxel_rolling_insert_classes(self._h, _p(cls, C.POINTER(C.c_uint8)), nv.value, C.byref(nv)))
+        return cls
 
     def setRobustKernel(self, kind, width: float = 1.0):
         """A robust kernel on every term of the cost (include/ngicp.h "robust kernel"): HUBER, CAUCHY or GEMAN_MCCLURE of the given width

@@ -697,6 +697,63 @@ class NanoGICP {
     }
     return true;
   }
+  // ---- the gated insert into the rolling map (include/ngicp.h "rolling voxel map: gated insert") ----
+  // insertIntoVoxelMap of the points the map does not contradict: every point of `producer`'s current source cloud is classified against
+  // the rolling map at the float pose T, and the EXPLAINED points, the NEW ones (insert_new) and the UNJUDGED ones (insert_unjudged) are
+  // inserted exactly as insertIntoVoxelMap would insert them alone.  In a frame loop: align, clearVoxelMapAlongRays, insertIntoVoxelMapGated.
+  enum InsertClass : uint8_t {
+    INSERT_NEW = NGICP_GATE_NEW,              // no occupied slot around the point
+    INSERT_EXPLAINED = NGICP_GATE_EXPLAINED,  // the best Mahalanobis term against the map is within the gate
+    INSERT_CONFLICT = NGICP_GATE_CONFLICT,    // it is above the gate: never inserted
+    INSERT_UNJUDGED = NGICP_GATE_UNJUDGED     // occupied slots, but no voxel of min_voxel_count points gave a finite term
+  };
+  struct GatedInsertOptions {
+    double max_mahalanobis = std::numeric_limits<double>::max();  // the gate on voxelFitness' m (chi-square-like, 3 degrees of freedom); the largest double: no gate
+    int min_voxel_count = 1;      // a voxel judges only with at least this many points
+    bool insert_new = true;
+    bool insert_unjudged = true;
+    bool dry_run = false;         // classify only: the map, the counter, the correspondences and the hooks' state stay
+  };
+  struct GatedInsert {
+    bool ok = false;              // false: refused, nothing changed
+    size_t n_points = 0;
+    size_t n_class[4] = {0, 0, 0, 0};  // by InsertClass
+    size_t n_kept = 0, n_new = 0, n_touched = 0;
+    double kernel_ms = 0.0;
+  };
+  GatedInsert insertIntoVoxelMapGated(NanoGICP& producer, const Matrix4& T, const GatedInsertOptions& options) {
+    GatedInsert r;
+    ngicp_gate_options o;
+    o.max_mahalanobis = options.max_mahalanobis;
+    o.min_voxel_count = options.min_voxel_count;
+    o.insert_new = options.insert_new ? 1 : 0;
+    o.insert_unjudged = options.insert_unjudged ? 1 : 0;
+    o.dry_run = options.dry_run ? 1 : 0;
+    ngicp_gate_result res;
+    r.ok = h_ && check(ngicp_voxel_rolling_insert_gated(h_, producer.h_, T.data(), &o, &res), "insertIntoVoxelMapGated");
+    if (r.ok) {
+      r.n_points = res.n_points;
+      for (int k = 0; k < 4; ++k) r.n_class[k] = res.n_class[k];
+      r.n_kept = res.n_kept;
+      r.n_new = res.n_new;
+      r.n_touched = res.n_touched;
+      r.kernel_ms = res.kernel_ms;
+    }
+    return r;
+  }
+  // the classes (InsertClass values) of the last insertIntoVoxelMapGated, dry or not, in the scan's original order; false (and empty)
+  // before the first such call and after clearVoxelMap
+  bool voxelMapInsertClasses(std::vector<uint8_t>& classes) {
+    classes.clear();
+    size_t n = 0;
+    if (!h_ || !check(ngicp_voxel_rolling_insert_classes(h_, nullptr, 0, &n), "voxelMapInsertClasses")) return false;
+    classes.resize(n);
+    if (!check(ngicp_voxel_rolling_insert_classes(h_, classes.data(), n, &n), "voxelMapInsertClasses")) {
+      classes.clear();
+      return false;
+    }
+    return true;
+  }
 
   // ---- the spaciousness metric (dlo::OdomNode::computeSpaciousness, odom.cc:990-1010) without downloading the scan ----
   // rangeSelect: the range (float)sqrt((double)x*x + y*y + z*z) of 0-based rank `rank` among the cloud's ranges in ascending order (NaN

@@ -448,6 +448,78 @@ typedef struct ngicp_ray_clear_result {
 int ngicp_voxel_rolling_ray_clear(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], const float* origin_or_null, const ngicp_ray_clear_options* options_or_null,
                                   ngicp_ray_clear_result* result_out_or_null);
 int ngicp_voxel_rolling_ray_counts(ngicp_t* h, uint32_t* miss_n_or_null, uint32_t* hit_n_or_null, size_t capacity, size_t* n_out_or_null);
+/* --- rolling voxel map: gated insert - keep what the map contradicts out (csrc/ngicp_voxel_gate.h) ------------------
+ * ngicp_voxel_rolling_insert adds every point of a scan, the points of a passer-by among them.  This entry classifies the scan's points
+ * against the rolling map at the pose and inserts only the points the map explains, or that fall where it holds nothing - in one call,
+ * on the device.  It changes nothing else; while it is not called every other result is bit for bit what it was.  The project's own
+ * definition.
+ *   inputs                     ngicp_voxel_rolling_insert's: `from`'s current source cloud A (`from` may be h) with its covariances C_j
+ *                              (computed if missing, as the insert does) and the float pose T.
+ *   per point j, in its ORIGINAL index:
+ *   slots                      exactly voxel fitness's ("voxel fitness" below), under the neighbourhood in force on h (DIRECT1 / 7 / 27):
+ *                              q = the float pose times the point in the passes' order, ((c0 x + c1 y) + c2 z) + c3; its cell by the
+ *                              mode's rule; slot s is cell + offset s, in range on the integers; a slot is OCCUPIED when the rolling map
+ *                              has that voxel.  A point whose q has no cell has no slots.
+ *   judging slots              the occupied slots whose voxel count n_v is >= min_voxel_count.  The term m_s is voxel fitness's,
+ *                              e^T (cov_v + R C_a R^T)^-1 e in FP64 in the same order of operations (no factor n_v).  best = +inf; in
+ *                              ascending slot a judging slot wins when m_s < best: ties go to the lower slot, NaN and +inf never win.
+ *   class                      NGICP_GATE_NEW (0): no occupied slot.  NGICP_GATE_EXPLAINED (1): a winner exists and
+ *                              best <= max_mahalanobis.  NGICP_GATE_CONFLICT (2): a winner exists and best > max_mahalanobis.
+ *                              NGICP_GATE_UNJUDGED (3): occupied slots exist but none won.
+ *   kept                       EXPLAINED always; NEW iff insert_new; UNJUDGED iff insert_unjudged; CONFLICT never.
+ *   the map afterwards         what ngicp_voxel_rolling_insert's definition gives for the kept points alone, in ascending original index,
+ *                              with their covariances: the insert's own transform (x*c0 + (y*c1 + (z*c2 + c3)), which is NOT the gate's
+ *                              q), the same keys, the same ascending-index sums per voxel, one rotation of the covariance sum, the same
+ *                              numbering of new voxels, the same stamp; the counter advances by one.
+ *   refusal                    the plain insert's, judged on EVERY point of the scan, kept or not, before anything is written: a
+ *                              transformed point (the insert's) that is not finite or lies 2^20 voxels out returns NGICP_ERR_ARG and
+ *                              changes nothing - map, counter, stamps, table, the hooks' state and the classes of the last accepted
+ *                              call all stay.
+ *   nothing kept               the call succeeds, changes nothing of the map and does NOT advance the insert counter (the classes and
+ *                              the result are those of this call).
+ *   dry_run != 0               classifies only: map, counter, stamps, hooks, stats and traces are untouched.  n_new = n_touched = 0.
+ * Consequences: with min_voxel_count == 1 the classes follow from ngicp_voxel_fitness_points(T): v = -1 and m = -1 is NEW, m = +inf is
+ * UNJUDGED, otherwise m is compared with the gate.  With max_mahalanobis == DBL_MAX and the default flags the call is
+ * ngicp_voxel_rolling_insert bit for bit.  On an empty map every point is NEW.
+ * In numpy (map: the model of the rolling map; slot_terms: voxel fitness's per-slot terms, NaN where a slot is empty):
+ *     slots, m, _ = slot_terms(A, C, map, T, K);   occ = slots >= 0;   judge = occ & (map.count[slots] >= min_voxel_count)
+ *     best = +inf;  won = False;  for s in range(K): w = judge[:, s] & (m[:, s] < best); best = where(w, m[:, s], best); won |= w
+ *     cls = where(~occ.any(1), 0, where(~won, 3, where(best <= max_mahalanobis, 1, 2)))
+ *     keep = (cls == 1) | ((cls == 0) & insert_new) | ((cls == 3) & insert_unjudged)
+ *     if keep.any() and not dry_run: map.insert(A[keep], C[keep], T)
+ * ngicp_voxel_rolling_insert_gated: options NULL means no gate (max_mahalanobis = DBL_MAX, which has no default of its own) and the
+ * defaults in brackets.  The result: the scan's points, the points per class, the kept points, the voxels created and the voxels of the
+ * kept points (created or added to), and the device event time of all launches of the call.
+ * ngicp_voxel_rolling_insert_classes: the classes (one byte per point, the values above) of the last accepted gated call, dry or not, in
+ * the scan's original order; *n_out points; a NULL array asks for the size only; NGICP_ERR_ARG when capacity < *n_out.  They stay
+ * readable until the next accepted gated call or ngicp_voxel_rolling_clear (NGICP_ERR_STATE before the first call and after a clear); a
+ * refused gated call leaves them as they were.
+ * Errors of _insert_gated: NGICP_ERR_STATE unless the rolling setting is on and res > 0.  NGICP_ERR_ARG: max_mahalanobis negative, NaN
+ * or infinite, min_voxel_count < 1, a null T, handles on different devices, an empty source cloud.
+ * Host synchronisations: three, one more than ngicp_voxel_rolling_insert - first the refusal flag, the class counts and the kept points'
+ * count in one read-back (a dry run, or a call that keeps nothing, ends here), then the plain insert's two.  Every refusal comes before
+ * the first write to the map.  Device memory on top of the insert's: two bytes per scan point (two class arrays).
+ * Not here: a gate on the robust weights, gating of the record inserts (_insert_voxels, _insert_map). */
+#define NGICP_GATE_NEW 0
+#define NGICP_GATE_EXPLAINED 1
+#define NGICP_GATE_CONFLICT 2
+#define NGICP_GATE_UNJUDGED 3
+typedef struct ngicp_gate_options {
+  double max_mahalanobis;  /* the gate on m: >= 0, finite; DBL_MAX keeps every judged point (no default) */
+  int min_voxel_count;     /* a voxel judges only with at least this many points, >= 1 (1) */
+  int insert_new;          /* != 0: NEW points are kept (1) */
+  int insert_unjudged;     /* != 0: UNJUDGED points are kept (1) */
+  int dry_run;             /* != 0: classify only (0) */
+} ngicp_gate_options;
+typedef struct ngicp_gate_result {
+  size_t n_points;         /* the scan's points */
+  size_t n_class[4];       /* of them NEW, EXPLAINED, CONFLICT, UNJUDGED */
+  size_t n_kept;
+  size_t n_new, n_touched; /* voxels created; voxels of the kept points (created or added to) */
+  double kernel_ms;        /* device event time, all launches of the call */
+} ngicp_gate_result;
+int ngicp_voxel_rolling_insert_gated(ngicp_t* h, ngicp_t* from, const float T_colmajor[16], const ngicp_gate_options* options_or_null, ngicp_gate_result* result_out_or_null);
+int ngicp_voxel_rolling_insert_classes(ngicp_t* h, uint8_t* cls_n_or_null, size_t capacity, size_t* n_out_or_null);
 /* LM trace of the last align(): rows of 8 doubles {outer, trial, y0, yi, rho, lambda, |d|, accepted}
  * (the columns setDebugPrint prints, impl/lsq_registration_impl.hpp:183-189). */
 int ngicp_get_lm_trace(ngicp_t* h, double* rows8_or_null, size_t max_rows, size_t* n_rows);
